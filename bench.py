@@ -2,7 +2,7 @@
 """
 bench.py -- headline benchmark of the MI355X-native RIME hot path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2] [--nt NT]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2] [--nt NT] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): visibilities/s = Nbl x Ntimes x Nfreqs per wall second of one
 forward + backward pass of RIME (loss = sum |V|^2, gradients w.r.t. sky and beam parameters),
@@ -34,11 +34,25 @@ unsharded float64 model (1e-5 / 1e-4; a worker that fails it exits non-zero).
 BENCH_FORCE_DIST=1 runs the same code path on ONE rank (RCCL initialised, every collective executed
 with world size 1, supervisor + workers + self-check) to rehearse it on a one-GPU box.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields), including
-  roofline     -- dominant kernel (fused fringe sum): algorithmic flops / measured kernel time
-                  (HIP events on the launch stream) against the fp32 peak, and
-  cpu_baseline -- the CPU oracle (op-for-op torch restatement of the reference path) timed on
-                  the host cores on a bounded sample of the same workload.
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).  A plain run sets up, warms up,
+times the K steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).
+--full adds what takes measurements of its own, after the timed region:
+  roofline        -- dominant kernel (fused fringe sum): algorithmic flops / measured kernel time
+                     (HIP events on the launch stream) against the fp32 peak, the vendor GEMM rate and
+                     the committed PMC summary,
+  cpu_baseline    -- the CPU oracle (op-for-op torch restatement of the reference path) timed on
+                     the host cores on a bounded sample of the same workload (skip: --no-cpu-baseline),
+  other_workloads -- N = 1, default workload: short runs of configs 3, 2, 5 (rank share) and C4 variants
+                     in child processes (skip: --no-other-workloads).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed in its LAST step as
+DIR/<name>.npy (float32; float64 for a float64 array): loss.npy (the step's loss), vis.npy (the
+visibilities) and grad_<parameter>.npy (the gradient of every leaf parameter: sky, points, beam).
+Complex arrays are stored as (..., 2) real / imaginary pairs.  An array of more than DUMP_MAX_VALUES
+real values is stored flattened, as a fixed sample of its entries (complex: of its pairs) at the sorted
+indices that numpy's default_rng(DUMP_SEED) draws -- the same entries in every run of the same arguments
+(all inputs and parameters are seeded), so that two builds can be compared output for output.
+N > 1: rank 0 writes (with both partitions measured, the one measured last stays in DIR).
 """
 import argparse
 import json
@@ -666,6 +680,32 @@ def selfcheck_reference(inp, dev, bls, sample, first_times):
         torch.set_default_dtype(old)
 
 
+DUMP_MAX_VALUES = 2 ** 21          # real values per dumped array: <= 8 MB in float32, the whole dump stays far below 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outdir, arrays):
+    """
+    --dump-outputs: write {name: tensor} as outdir/<name>.npy -- float32 (float64 kept as float64), complex as (..., 2)
+    real / imaginary pairs, arrays of more than DUMP_MAX_VALUES real values as a seeded sample of their flattened entries
+    (see the module docstring).  Outside the timed region.
+    """
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        cplx = t.is_complex()
+        if cplx:
+            t = torch.view_as_real(t.resolve_conj())
+        if t.dtype != torch.float64:
+            t = t.float()
+        if t.numel() > DUMP_MAX_VALUES:
+            rows = t.reshape(-1, 2) if cplx else t.reshape(-1)
+            n = DUMP_MAX_VALUES // (2 if cplx else 1)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=n, replace=False))
+            t = rows.index_select(0, torch.as_tensor(idx, device=rows.device))
+        np.save(os.path.join(outdir, name + '.npy'), t.cpu().numpy())
+
+
 OTHER_WORKLOADS = (('c3', [], None), ('c2', ['--steps', '20', '--warmup', '5'], None),
                    ('c5', ['--nf', '64', '--steps', '3', '--warmup', '2'], None),
                    # the headline array is a 127-antenna hexagon + outrigger: 63 mirror pairs + the outrigger + the hub, served by the
@@ -698,7 +738,7 @@ def other_workloads(budget_s, timeout_each=150.0, script=None):
         if left < 20.0:
             out.append(dict(workload=tag, skipped='time budget of the default run used up'))
             continue
-        cmd = [sys.executable, script or os.path.abspath(__file__), '--workload', wl, '--no-cpu-baseline', '--no-other-workloads'] + \
+        cmd = [sys.executable, script or os.path.abspath(__file__), '--workload', wl, '--full', '--no-cpu-baseline', '--no-other-workloads'] + \
               (extra if extra else ['--steps', '5', '--warmup', '3'])
         t1 = time.perf_counter()
         try:
@@ -746,9 +786,14 @@ def main():
     ap.add_argument('--workload', default='c4', choices=sorted(WORKLOADS))
     ap.add_argument('--nt', type=int, default=None, help='time steps per step (minibatch)')
     ap.add_argument('--nf', type=int, default=None, help='override the number of channels (e.g. one rank\'s share of c5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also measure the kernel roofline, the CPU baseline and (N = 1, default '
+                         'workload) the other workloads; a plain run only times the steps and prints the headline line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss, visibilities and parameter gradients of the last timed step as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-other-workloads', action='store_true',
-                    help='N = 1, default workload: skip the short runs of BASELINE configs 3, 2 and the config-5 rank share that '
+                    help='--full, N = 1, default workload: skip the short runs of BASELINE configs 3, 2 and the config-5 rank share that '
                          'follow the timed region and the CPU baseline (`other_workloads` in the JSON line); also skipped '
                          'with --no-cpu-baseline (kernel measurements, profiler runs)')
     ap.add_argument('--redundant', action='store_true',
@@ -766,6 +811,12 @@ def main():
     # GPU (no torch.cuda call yet); the ranks are fresh child processes, this process only relays the result
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
+    if args.warmup < 0:
+        raise SystemExit('--warmup must be >= 0')
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         rc, _ = launch_ranks(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:],
                              timeout=float(os.environ.get('BENCH_LAUNCH_TIMEOUT', '2400')), out=sys.stdout)
@@ -904,12 +955,16 @@ def main():
             else:
                 # registration order = collective order: the sky gradient (the large one) is final last (dist.grad_hook_order)
                 gsync = rdist.GradSync(shared=params[1:] + params[:1])
+        # the kernel names of the timed steps decide `dtype` (matrix-core path or not); --full also reports their times
         prof = []
         ops.PROFILE = prof
+        keep = {}                     # --dump-outputs: the last timed step's visibilities (per time chunk)
 
         def chisq_loss(vis, k):
             # sum |V|^2 through the fused chi-square epilogue (one pass forward, one pass backward);
             # the torch composition (vis.real ** 2 + vis.imag ** 2).sum() costs ten small launches and 0.3 ms per C4 step
+            if 'on' in keep:
+                keep[k] = vis
             return ops.chisq(vis)
 
         def step(loss_fn=chisq_loss):
@@ -951,8 +1006,12 @@ def main():
             collective_timeout = eff if eff is not None else collective_timeout
         prof.clear()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            if args.dump_outputs and i == args.steps - 1:
+                keep['on'] = True
+                keep['loss'] = step()
+            else:
+                step()
         sync()
         dt = time.perf_counter() - t0
         if distributed:
@@ -961,6 +1020,16 @@ def main():
             dt = float(tt.item())
         ops.PROFILE = None
         dbg('mode %s: timed steps done, %.1f ms/step' % (shard, dt / args.steps * 1e3))
+        if args.dump_outputs and rank == 0:
+            # what a caller of the timed path receives from its last step (before the self-check step below replaces the
+            # gradients): the loss, the (gathered) visibilities, the gradient of every leaf parameter
+            names = ['sky'] + (['points'] if cfg['Npt'] > 0 else []) + ['beam']
+            assert len(names) == len(params), (names, len(params))
+            outs = dict(loss=keep['loss'], vis=torch.cat([keep[k] for k in range(nchunks)], dim=3))
+            outs.update(('grad_' + nm, p.grad) for nm, p in zip(names, params))
+            dump_outputs(args.dump_outputs, outs)
+            dbg('mode %s: outputs written to %s' % (shard, args.dump_outputs))
+        keep.clear()
 
         # ---- value self-check, OUTSIDE the timed region: one more step of the SAME sharded model with the loss
         # restricted to sampled baselines x the first time step of every chunk x all channels; rank 0 compares the
@@ -1019,7 +1088,7 @@ def main():
         dbg('self-check: vis %.2e grad %.2e' % (vis_rel, grad_rel))
     best['check'] = None
 
-    # kernel-level roofline from the HIP events recorded around each C-ABI launch
+    # kernel-level statistics from the HIP events recorded around each C-ABI launch (the roofline: --full)
     kstat = {}
     for name, e0, e1, elems, mflops, abytes in prof:
         ms = e0.elapsed_time(e1)
@@ -1035,7 +1104,7 @@ def main():
         big = [m for a, m in k[6] if a == k[4]]
         k[5] = sum(big) / len(big)
     roof = None
-    if kstat:
+    if kstat and args.full:
         # dominant kernel = the one with the largest total time over the timed region, nothing else; the hot kernel with
         # the LOWEST fraction of its roof is named beside it (min_frac_kernel / min_frac)
         dom = max(kstat, key=lambda nm: kstat[nm][1])
@@ -1182,7 +1251,7 @@ def main():
                                selfcheck=selfcheck,
                                overlap='vis all-gather of chunk k runs under the kernels of chunk k+1; gradient '
                                        'collectives start from autograd hooks inside the last backward')
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(inp)
             out['cpu_baseline'] = cb
             out['speedup_vs_cpu_baseline'] = out['value'] / cb['value']

@@ -113,3 +113,42 @@ def test_one_rank_under_the_launcher_over_rccl_uses_the_launcher_store():
     res = json.loads(lines[0])
     assert res['n_gpus'] == 1 and res['dist']['backend'] == 'nccl' and res['dist']['selfcheck']['ok']
     assert res['alt'][0]['selfcheck']['ok'] and {res['dist']['shard'], res['alt'][0]['shard']} == {'freq', 'bl'}
+
+
+def test_plain_run_times_the_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` on one GPU: ONE JSON line with the headline fields and the requested step
+    count, none of what --full adds; --dump-outputs writes the loss, the visibilities and every parameter gradient of the
+    last timed step (float32, within 64 MB); a --full run of the same arguments adds the kernel roofline and dumps the
+    same outputs (same seeded inputs and parameters)"""
+    import subprocess
+    import numpy as np
+    e = dict(os.environ)
+    for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'BENCH_FORCE_DIST', 'BENCH_SELFCHECK'):
+        e.pop(k, None)
+    base = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--workload', 'c2', '--nt', '4', '--steps', '3',
+            '--warmup', '1']
+    lines = {}
+    for tag, extra in (('plain', []), ('full', ['--full', '--no-cpu-baseline'])):
+        r = subprocess.run(base + extra + ['--dump-outputs', str(tmp_path / tag)], env=e, capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        out = r.stdout.decode().splitlines()
+        assert len(out) == 1
+        lines[tag] = json.loads(out[0])
+    plain, full = lines['plain'], lines['full']
+    for res in (plain, full):
+        assert res['steps'] == 3 and res['warmup'] == 1 and res['n_gpus'] == 1 and res['higher_is_better'] is True
+        assert res['unit'] == 'vis/s' and res['ms_per_step'] > 0 and res['dtype'].startswith('f32')
+        assert abs(res['value'] - res['config']['Nbl'] * 4 * res['config']['Nfreqs'] / (res['ms_per_step'] * 1e-3)) < 1e-6 * res['value']
+    assert plain['roofline'] is None and 'cpu_baseline' not in plain and 'other_workloads' not in plain
+    assert full['roofline'] is not None and full['roofline']['kernels']
+    names = {'loss', 'vis', 'grad_sky', 'grad_beam'}
+    assert {f[:-4] for f in os.listdir(str(tmp_path / 'plain'))} == names
+    total = 0
+    for n in sorted(names):
+        a, b = np.load(str(tmp_path / 'plain' / (n + '.npy'))), np.load(str(tmp_path / 'full' / (n + '.npy')))
+        total += a.nbytes
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), n
+        assert np.abs(a - b).max() <= 1e-5 * max(np.abs(b).max(), 1e-30), n
+    assert total <= 64 * 2 ** 20
+    vis = np.load(str(tmp_path / 'plain' / 'vis.npy'))
+    assert vis.shape == (1, 1, plain['config']['Nbl'], 4, plain['config']['Nfreqs'], 2)

@@ -94,8 +94,9 @@ def test_bench_main_becomes_the_launcher_before_touching_the_gpu(tmp_path):
 
 
 def test_other_workloads_are_child_runs_that_cannot_lose_the_line(tmp_path):
-    """after the timed region the N = 1 default run measures configs 3, 2, the config-5 rank share and the
-    headline workload without mirror pairs in CHILD processes of the same script and attaches what they report; a child that
+    """after the timed region the N = 1 --full run measures configs 3, 2, the config-5 rank share and the
+    headline workload without mirror pairs in CHILD processes of the same script (themselves run with --full, for the kernel
+    figures they report) and attaches what they report; a child that
     fails, prints nothing or hangs becomes an entry that says so, the budget stops further starts, the environment of the
     no-mirror run reaches its child -- driven here with a stub in place of bench.py"""
     stub = _stub(tmp_path, """
@@ -104,8 +105,9 @@ def test_other_workloads_are_child_runs_that_cannot_lose_the_line(tmp_path):
         ap.add_argument('--workload'); ap.add_argument('--nf'); ap.add_argument('--steps', type=int, default=5)
         ap.add_argument('--warmup', type=int, default=3)
         ap.add_argument('--no-cpu-baseline', action='store_true'); ap.add_argument('--no-other-workloads', action='store_true')
+        ap.add_argument('--full', action='store_true')
         a = ap.parse_args()
-        assert a.no_cpu_baseline and a.no_other_workloads
+        assert a.full and a.no_cpu_baseline and a.no_other_workloads
         if a.workload == 'c2':
             sys.exit(3)
         if a.workload == 'c5':
@@ -135,6 +137,38 @@ def test_rank_process_refuses_a_world_size_other_than_gpus():
     env = dict(os.environ, WORLD_SIZE='1', RANK='0', LOCAL_RANK='0')
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '4'], env=env, capture_output=True, timeout=300)
     assert r.returncode != 0 and b'WORLD_SIZE=1' in r.stderr and r.stdout.strip() == b''
+
+
+def test_bench_refuses_a_step_count_below_one():
+    """--steps sets the number of timed steps and ms_per_step divides by it: 0 is refused before anything starts"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0', '--full', '--dump-outputs', 'unused'],
+                       capture_output=True, timeout=300)
+    assert r.returncode != 0 and b'--steps must be >= 1' in r.stderr and r.stdout.strip() == b''
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones_the_same_way(tmp_path):
+    """--dump-outputs: float32 (float64 kept), complex as real / imaginary pairs, arrays over DUMP_MAX_VALUES values as
+    the same seeded sample in every call, well within 64 MB in all"""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(1)
+    arrays = dict(loss=torch.tensor(2.5, dtype=torch.float64),
+                  vis=torch.randn(1, 1, 300, 8, 1024, dtype=torch.complex64, generator=g),
+                  grad_sky=torch.randn(1, 1, 64, 40000, generator=g), grad_points=torch.randn(1, 1, 2, 100, generator=g))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(str(tmp_path / 'a' / (n + '.npy'))) for n in arrays}
+    assert got['loss'].dtype == np.float64 and float(got['loss']) == 2.5
+    assert got['vis'].dtype == np.float32 and got['vis'].shape == (bench.DUMP_MAX_VALUES // 2, 2)
+    assert got['grad_sky'].shape == (bench.DUMP_MAX_VALUES,)
+    assert np.array_equal(got['grad_points'], arrays['grad_points'].numpy())
+    # a sample of whole entries: every dumped (re, im) pair is a pair of the original array
+    flat = torch.view_as_real(arrays['vis']).reshape(-1, 2).numpy()
+    assert np.isin(got['vis'][:, 0], flat[:, 0]).all()
+    assert set(map(tuple, got['vis'][:1000])) <= set(map(tuple, flat))
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(str(tmp_path / 'b' / (n + '.npy'))))
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (n + '.npy'))) for n in arrays) < 64 * 2 ** 20
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -24,5 +24,5 @@ import torch
 a, b = torch.load('/tmp/g0.pt'), torch.load('/tmp/g1.pt')
 print('bitwise equal gradients:', [bool(torch.equal(x, y)) for x, y in zip(a, b)], 'max rel diff', max(float((x - y).abs().max() / x.abs().max()) for x, y in zip(a, b)))
 E
-for r in 1 2; do for pz in 0 1; do RIME_BWD_PIPE=$pz python bench.py --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python -c "
+for r in 1 2; do for pz in 0 1; do RIME_BWD_PIPE=$pz python bench.py --full --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernels']; print('c4 pipe=$pz', round(d['ms_per_step'],2), {n[11:14]:round(x['total_ms']/5,2) for n,x in k.items()})"; done; done

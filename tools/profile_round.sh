@@ -6,13 +6,13 @@ tag=${1:-r05}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-echo "[1] bench c4 (default command)"; timeout -k 10 400 python bench.py > $out/bench_c4.json 2> $out/bench_c4.err; echo rc=$?
+echo "[1] bench c4 (--full)"; timeout -k 10 400 python bench.py --full > $out/bench_c4.json 2> $out/bench_c4.err; echo rc=$?
 echo "[2] bench c3 / c2 / c5 rank share"
-timeout -k 10 200 python bench.py --workload c3 --no-cpu-baseline > $out/bench_c3.json 2> $out/bench_c3.err; echo rc=$?
-timeout -k 10 200 python bench.py --workload c2 --no-cpu-baseline > $out/bench_c2.json 2> $out/bench_c2.err; echo rc=$?
-timeout -k 10 300 python bench.py --workload c5 --nf 64 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_c5_rankshare.json 2> $out/bench_c5_rankshare.err; echo rc=$?
+timeout -k 10 200 python bench.py --full --workload c3 --no-cpu-baseline > $out/bench_c3.json 2> $out/bench_c3.err; echo rc=$?
+timeout -k 10 200 python bench.py --full --workload c2 --no-cpu-baseline > $out/bench_c2.json 2> $out/bench_c2.err; echo rc=$?
+timeout -k 10 300 python bench.py --full --workload c5 --nf 64 --steps 3 --warmup 1 --no-cpu-baseline > $out/bench_c5_rankshare.json 2> $out/bench_c5_rankshare.err; echo rc=$?
 echo "[2b] the N > 1 code path on one rank over RCCL (supervisor, both partitions, self-check)"
-BENCH_FORCE_DIST=1 timeout -k 10 400 python bench.py --no-cpu-baseline > $out/bench_c4_rccl_one_rank.json 2> $out/bench_c4_rccl_one_rank.err; echo rc=$?
+BENCH_FORCE_DIST=1 timeout -k 10 400 python bench.py --full --no-cpu-baseline > $out/bench_c4_rccl_one_rank.json 2> $out/bench_c4_rccl_one_rank.err; echo rc=$?
 cd /tmp && export TMPDIR=/tmp
 echo "[3] rocprofv3 kernel stats, c4 and c3"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c4 -o c4 -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 5 --warmup 2 > $out/prof_c4.log 2>&1; echo rc=$?

@@ -4,7 +4,7 @@ set -u
 out=$GRAFT_REPO_ROOT/gpurun_out/$1; mkdir -p $out; cd $GRAFT_REPO_ROOT
 for r in $(seq 1 ${4:-2}); do for v in $2; do for wl in $3; do
   lib=""; [ $v != base ] && lib=$GRAFT_REPO_ROOT/tools/bin/librime_$v.so
-  RIME_LIB_PATH=$lib timeout -k 10 300 python bench.py --workload $wl --no-cpu-baseline > $out/bench_${wl}_${v}_$r.json 2> $out/bench_${wl}_${v}_$r.err
+  RIME_LIB_PATH=$lib timeout -k 10 300 python bench.py --full --workload $wl --no-cpu-baseline > $out/bench_${wl}_${v}_$r.json 2> $out/bench_${wl}_${v}_$r.err
   python - <<E
 import json
 d=json.load(open("$out/bench_${wl}_${v}_$r.json")); k=d["roofline"]["kernels"]

@@ -6,7 +6,7 @@ out=gpurun_out/r04_c2_splits.txt
 mkdir -p gpurun_out; : > $out
 run() {
     echo "== $*" >> $out
-    env "$@" python bench.py --workload c2 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+    env "$@" python bench.py --full --workload c2 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); k=d['roofline']['kernels']
 print('ms/step %.4f' % d['ms_per_step'], {n.replace('fringe_ant_',''): round(v['total_ms']/v['launches'],4) for n,v in k.items()})" >> $out

@@ -6,7 +6,7 @@ out=$GRAFT_REPO_ROOT/gpurun_out/r04e; mkdir -p $out; cd $GRAFT_REPO_ROOT
 ./tools/bin/simd_map > $out/simd_map.txt 2>&1; head -12 $out/simd_map.txt
 for v in base split16k split24k base; do
   lib=""; [ $v != base ] && lib=$GRAFT_REPO_ROOT/tools/bin/librime_$v.so
-  RIME_LIB_PATH=$lib BENCH_SELFCHECK=1 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 10 --warmup 3 > $out/bench_c4_$v.json 2> $out/bench_c4_$v.err; echo "$v rc=$?"
+  RIME_LIB_PATH=$lib BENCH_SELFCHECK=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $out/bench_c4_$v.json 2> $out/bench_c4_$v.err; echo "$v rc=$?"
   python - <<E
 import json
 d=json.load(open("$out/bench_c4_$v.json")); k=d["roofline"]["kernels"]

@@ -20,7 +20,7 @@ cd $GRAFT_REPO_ROOT
 # plain timing, alternating, same box
 for r in 1 2; do for wl in c3 c2; do for v in base fwdcheap bwdcheap; do
   if [ $v = base ]; then unset RIME_LIB_PATH; else export RIME_LIB_PATH=$GRAFT_REPO_ROOT/tools/bin/librime_$v.so; fi
-  timeout -k 10 200 python bench.py --workload $wl --no-cpu-baseline 2>/dev/null | python -c "
+  timeout -k 10 200 python bench.py --full --workload $wl --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['roofline']['kernels']; print('$wl $v $r', round(d['ms_per_step'],3), {n[11:14]:round(x['total_ms']/d['steps'],3) for n,x in k.items() if 'fringe' in n})"
 done; done; done > $out/timing.txt 2>&1
 unset RIME_LIB_PATH

@@ -6,7 +6,7 @@ mkdir -p $out
 cd $GRAFT_REPO_ROOT
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $out/gputest.txt 2>&1; echo "suite rc=$?"; tail -2 $out/gputest.txt
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1; echo "smoke rc=$?"; tail -3 $out/smoke.txt
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $out/bench_c4.json 2> $out/bench_c4.err; echo "bench rc=$?"
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $out/bench_c4.json 2> $out/bench_c4.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/closing/bench_c4.json').read().strip().splitlines()[-1])

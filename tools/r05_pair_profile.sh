@@ -4,7 +4,7 @@ set -u
 out=$GRAFT_REPO_ROOT/gpurun_out/r05p
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-echo "[1] bench c4"; timeout -k 10 400 python bench.py --no-other-workloads > $out/bench_c4.json 2> $out/bench_c4.err; echo rc=$?
+echo "[1] bench c4"; timeout -k 10 400 python bench.py --full --no-other-workloads > $out/bench_c4.json 2> $out/bench_c4.err; echo rc=$?
 cd /tmp && export TMPDIR=/tmp
 echo "[2] rocprofv3 kernel stats"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_c4 -o c4 -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-other-workloads --steps 5 --warmup 2 > $out/prof_c4.log 2>&1; echo rc=$?

@@ -1,9 +1,10 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/rankshare
-timeout -k 10 300 python bench.py --nf 32 --no-cpu-baseline --no-other-workloads --steps 20 --warmup 5 > gpurun_out/rankshare/bench_nf32.json 2> gpurun_out/rankshare/bench_nf32.err
-python - <<'PY'
-import json
-d = json.loads(open('gpurun_out/rankshare/bench_nf32.json').read().strip().splitlines()[-1])
+res=$(mktemp -d)
+timeout -k 10 300 python bench.py --full --nf 32 --no-cpu-baseline --no-other-workloads --steps 20 --warmup 5 > $res/bench_nf32.json 2> $res/bench_nf32.err
+python - "$res" <<'PY'
+import json, sys
+d = json.loads(open('%s/bench_nf32.json' % sys.argv[1]).read().strip().splitlines()[-1])
 k = d['roofline']['kernels']
 print('nf32 ms/step %.3f' % d['ms_per_step'], {n: round(v['total_ms'] / d['steps'], 3) for n, v in k.items()})
 PY
