@@ -2046,7 +2046,25 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
 // ---------------------------------------------------------------------------------------
 struct PairBwdArgs : AntBwdArgs {
     const int* centre;         // CEN: [2][128] slots of the hub's baselines (as PairArgs::centre)
+    int ap;                    // 0: no octet is searched for progressions (RIME_PAIR_AP=0)
 };
+
+// PROGRESSIONS (round 6).  Antennas of a regular array sit on lattice lines: where rows q .. q + 3 of the block are r, r + d,
+// r + 2d, r + 3d, their phasors are E1 conj(D), E1, E1 D, E1 D D with D = exp(2 pi i nu d.s) -- one evaluation and three complex
+// rotations (4 f32 instructions each) instead of four evaluations (f64 phase, fraction, conversion, sine, cosine).  A lane of
+// the backward generates all rows of its pixel, so D is ONE more evaluation per lane and pixel, shared by every such quad of
+// the block (they have ONE step: the host orders the rows so, ops._pair_ap_order); no row is more than two rotations away
+// from an evaluated one.  The unit is the octet 8m .. 8m + 7 -- the two half-waves of a (tj, ks, jq) step hold its two quads, so
+// the branch on its mask bit is wave-uniform.  Mask 0 is the code of round 5.
+// One rotation, every operation fenced: four independent rotations are what the SLP vectoriser pairs (see keep_scalar)
+__device__ __forceinline__ void rotate_scalar(float c, float s, float dc, float ds, float& oc, float& os)
+{
+    float t = c * dc; keep_scalar(t);
+    oc = fmaf(-s, ds, t); keep_scalar(oc);
+    float w = s * dc; keep_scalar(w);
+    os = fmaf(c, ds, w); keep_scalar(os);
+}
+constexpr double PAIR_AP_TOL = 1e-9;           // [m], on the unscaled positions (ops.MIRROR_TOL)
 
 // TF: row tiles the instantiation is compiled for -- 2: up to 64 rows, tiles (0,0) (0,1) (1,1); 1: up to 32 rows (HERA-37-class
 // arrays), one tile: half the accumulators, a third of the planes
@@ -2076,6 +2094,26 @@ fringe_pair_bwd_kernel(PairBwdArgs A)
     // ---- staging: antenna coordinates (x sign nu / c), the eight planes in A-fragment order, the hub's vectors
     const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
     for (int i = tid; i < 64 * 3; i += PB_THREADS) ant_lds[i] = (i < A.Nant * 3) ? nu_c * A.antpos[i] : 0.0;
+    // progressions: the step of the block is row 1 - row 0; lane m < 8 of every wave tests octet m (both quads, offsets from the
+    // quad's first row against multiples of the step, every coordinate); the ballot is the mask, the scaled step stays in SGPRs
+    uint32_t apmask = 0;
+    double dnx = 0.0, dny = 0.0, dnz = 0.0;
+    if (A.ap && A.Nant >= 8) {                                   // uniform
+        const double dx = A.antpos[3] - A.antpos[0], dy = A.antpos[4] - A.antpos[1], dz = A.antpos[5] - A.antpos[2];
+        bool ok = false;
+        if (lane < 8 && 8 * lane + 8 <= A.Nant) {
+            ok = true;
+            for (int q = 8 * lane; q < 8 * lane + 8; q += 4)
+                for (int k = 1; k < 4; ++k) {
+                    const double* r0 = A.antpos + 3 * q;
+                    const double* rk = r0 + 3 * k;
+                    ok = ok && fabs(rk[0] - r0[0] - k * dx) <= PAIR_AP_TOL && fabs(rk[1] - r0[1] - k * dy) <= PAIR_AP_TOL
+                            && fabs(rk[2] - r0[2] - k * dz) <= PAIR_AP_TOL;
+                }
+        }
+        apmask = __builtin_amdgcn_readfirstlane((uint32_t)__ballot(ok)) & 0xffu;
+        dnx = nu_c * dx; dny = nu_c * dy; dnz = nu_c * dz;
+    }
     const float gs = A.gscale[t * A.Nf + f] * 0.125f;
     const float* gre = A.gvt + ((size_t)t * A.Nf + f) * 2 * A.Nbl;
     const float* gim = gre + A.Nbl;
@@ -2177,6 +2215,11 @@ fringe_pair_bwd_kernel(PairBwdArgs A)
                 } else { accR[q][e] = 0.f; accI[q][e] = 0.f; }
             }
         float part = 0.f;
+        float Dc = 1.f, Ds = 0.f;                                 // D = exp(2 pi i nu d.s): the step of the block's progressions
+        if (apmask) {                                             // uniform
+            const float rr = turn_frac(phase_of<FLAT>(dnx, sx, dny, sy, dnz, sz));
+            Dc = __builtin_amdgcn_cosf(rr); Ds = __builtin_amdgcn_sinf(rr);
+        }
 #pragma unroll
         for (int tjr = 0; tjr < TF; ++tjr) {
             const int tj = TF - 1 - tjr;                          // descending: row tile tj completes here
@@ -2197,6 +2240,20 @@ fringe_pair_bwd_kernel(PairBwdArgs A)
                         if (32 * tj + 16 * ks + 8 * jq >= A.Nant) {  // uniform: 8 padding rows
 #pragma unroll
                             for (int u = 0; u < 4; ++u) { ec[8 * ks + 4 * jq + u] = 0.f; es[8 * ks + 4 * jq + u] = 0.f; }
+                            continue;
+                        }
+                        if ((apmask >> (4 * tj + 2 * ks + jq)) & 1u) {   // uniform: octet of two progressions -- this half-wave's
+                            // quad from its second row: E0 = E1 conj(D), E2 = E1 D, E3 = E2 D
+                            const int an = 32 * tj + 8 * (2 * ks + jq) + 4 * h + 1;
+                            const double ph = phase_of<FLAT>(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
+                            const float rr = turn_frac(ph);
+                            float* c4 = ec + 8 * ks + 4 * jq;
+                            float* s4 = es + 8 * ks + 4 * jq;
+                            c4[1] = __builtin_amdgcn_cosf(rr);
+                            s4[1] = __builtin_amdgcn_sinf(rr);
+                            rotate_scalar(c4[1], s4[1], Dc, -Ds, c4[0], s4[0]);
+                            rotate_scalar(c4[1], s4[1], Dc, Ds, c4[2], s4[2]);
+                            rotate_scalar(c4[2], s4[2], Dc, Ds, c4[3], s4[3]);
                             continue;
                         }
 #pragma unroll
@@ -2449,6 +2506,14 @@ static bool fwd_packed_enabled()
 static bool bwd_small_enabled()
 {
     static const int on = [] { const char* e = getenv("RIME_BWD_SMALL"); return e ? atoi(e) : 1; }();
+    return on != 0;
+}
+
+// RIME_PAIR_AP=0: the pair backward evaluates every phasor (no rotation within progressions; A/B measurements; ops.py reads the
+// same variable and keeps the plain row order)
+static bool pair_ap_enabled()
+{
+    static const int on = [] { const char* e = getenv("RIME_PAIR_AP"); return e ? atoi(e) : 1; }();
     return on != 0;
 }
 
@@ -2745,7 +2810,7 @@ extern "C" int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const
     A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.gpsky = gpsky; A.gvt = (const float*)workspace;
     A.Nant = Nrows; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
     A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign; A.accumulate = accumulate ? 1 : 0;
-    A.rows_i = 0; A.imsign = 1.f; A.mirror = 0; A.centre = centre;
+    A.rows_i = 0; A.imsign = 1.f; A.mirror = 0; A.centre = centre; A.ap = pair_ap_enabled() ? 1 : 0;
     const int ntile = Pstride / 32;
     int per = 256;
     while (per > 8 && (long)Nt * Nf * ((ntile + per - 1) / per) < 1024) per /= 2;

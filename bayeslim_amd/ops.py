@@ -373,14 +373,18 @@ def _mirror_block(blk, P, dev):
 PAIR = _env_int('RIME_PAIR', 1) != 0            # RIME_PAIR=0: such blocks keep the mirror-pair kernels (A/B measurements)
 PAIR_ROWS = 64                                  # rows of the pair kernels (firsts + antennas without a partner)
 PAIR_CPLX = _env_int('RIME_PAIR_CPLX', 1) != 0  # complex psky on pair blocks, one pass per real plane (0: the plain blocks; A/B)
+# round 6: rows ordered so that octets hold two 4-term progressions of one step; the pair backward kernel rotates within them
+# (0: the plain row order here AND no rotation in the library, which reads the same variable -- round 5's result bit for bit)
+PAIR_AP = _env_int('RIME_PAIR_AP', 1) != 0
 
 
-def _pair_layout(P, rows=PAIR_ROWS, hub_ok=True):
+def _pair_layout(P, rows=PAIR_ROWS, hub_ok=True, ap=False):
     """
     Rows of the conjugate-pair form for antenna positions P (n, 3): (firsts, partner, hub, centre) -- firsts[k] the antenna
     of row k, partner[k] its mirror antenna or -1, hub the antenna AT the centre that is served outside the rows (or None)
     -- or None when the set has no point symmetry or does not fit: at most `rows` rows, plus (hub_ok) the hub when the rows
-    are full.
+    are full.  ap: the same rows in the order of the pair BACKWARD (_pair_ap_order); the forward keeps the plain order, and
+    with it every bit of its result.
     """
     found = _mirror_pairs(P)
     if found is None:
@@ -395,7 +399,86 @@ def _pair_layout(P, rows=PAIR_ROWS, hub_ok=True):
         singles = [a for a in singles if a != hub]
     firsts = [a for a, _ in pairs] + list(singles)
     partner = [b for _, b in pairs] + [-1] * len(singles)
+    if ap:
+        order = _pair_ap_order(np.asarray(P, dtype=np.float64)[firsts] - c)
+        firsts, partner = [firsts[k] for k in order], [partner[k] for k in order]
     return firsts, partner, hub, c
+
+
+def _pair_ap_mask(pos):
+    """
+    The octet mask the pair backward kernel derives from its row positions `pos` (nrows, 3) (csrc/fringe_mfma.hip,
+    fringe_pair_bwd_kernel: the same test, restated): with the block's step d = pos[1] - pos[0], bit m is set when rows
+    8m..8m+3 and 8m+4..8m+7 both are r, r + d, r + 2d, r + 3d within MIRROR_TOL in every coordinate.
+    """
+    pos = np.asarray(pos, dtype=np.float64)
+    n = len(pos)
+    if n < 8:
+        return 0
+    d = pos[1] - pos[0]
+    mask = 0
+    for m in range(n // 8):
+        ok = all(np.abs(pos[q + k] - pos[q] - k * d).max() <= MIRROR_TOL for q in (8 * m, 8 * m + 4) for k in (1, 2, 3))
+        mask |= int(ok) << m
+    return mask
+
+
+def _pair_ap_order(pos):
+    """
+    Row order of the conjugate-pair form that exposes arithmetic progressions to the pair backward kernel, which evaluates
+    one phasor of a quad r, r + d, r + 2d, r + 3d and rotates it to the other three: a permutation of
+    range(len(pos)) whose leading octets hold two such quads each, all with ONE step d; every other row follows in its old
+    order.  d is the candidate among the array's shortest separations that yields the most quads (the first such
+    candidate in row order).  The representative of a mirror pair is NOT swapped: the rows are the rows of the plain order,
+    so every phasor keeps its phase and the forward computes what it computed.  The identity when fewer than two quads
+    exist -- arrays without lattice lines keep their order.
+    """
+    pos = np.asarray(pos, dtype=np.float64)
+    n = len(pos)
+    ident = list(range(n))
+    if n < 8:
+        return ident
+    diff = pos[None, :, :] - pos[:, None, :]                       # diff[a, b] = pos[b] - pos[a]
+    length = np.sqrt((diff ** 2).sum(-1))
+    length[np.arange(n), np.arange(n)] = np.inf
+    short = length.min()
+    if not np.isfinite(short) or short <= MIRROR_TOL:
+        return ident
+    cands = []                                                      # steps of the shortest length, one of +d / -d each
+    for a, b in zip(*np.nonzero(length <= short * (1 + 1e-6))):
+        d = diff[a, b]
+        if not any(np.abs(d - e).max() <= MIRROR_TOL or np.abs(d + e).max() <= MIRROR_TOL for e in cands):
+            cands.append(d)
+    best = []
+    for d in cands:
+        succ = -np.ones(n, dtype=np.int64)                          # succ[a]: the row at pos[a] + d
+        for a in range(n):
+            hit = np.nonzero(np.abs(diff[a] - d).max(-1) <= MIRROR_TOL)[0]
+            if len(hit):
+                succ[a] = hit[0]
+        has_pred = set(succ[succ >= 0].tolist())
+        quads = []
+        for a in range(n):
+            if a in has_pred:
+                continue
+            line = [a]
+            while succ[line[-1]] >= 0 and succ[line[-1]] not in line:
+                line.append(int(succ[line[-1]]))
+            quads += [line[4 * q:4 * q + 4] for q in range(len(line) // 4)]
+        if quads:
+            # what the kernel will test: offsets from the quad's first row against multiples of the step of the FIRST quad
+            step = pos[quads[0][1]] - pos[quads[0][0]]
+            quads = [q for q in quads if all(np.abs(pos[q[k]] - pos[q[0]] - k * step).max() <= MIRROR_TOL for k in (1, 2, 3))]
+        if len(quads) > len(best):
+            best = quads
+    noct = len(best) // 2
+    if noct == 0:
+        return ident
+    lead = [a for q in best[:2 * noct] for a in q]
+    taken = set(lead)
+    order = lead + [a for a in ident if a not in taken]
+    assert sorted(order) == ident
+    return order
 
 
 def _pair_block(blk, P, dev):
@@ -412,41 +495,62 @@ def _pair_block(blk, P, dev):
     if lay is None:
         return None
     firsts, partner, hub, c = lay
-    vrow = -np.ones(n, dtype=np.int64)
-    for k, (a, b) in enumerate(zip(firsts, partner)):
-        vrow[a] = k
-        if b >= 0:
-            vrow[b] = 64 + k
-    direct = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
-    conj = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
-    centre = np.full((2, MFMA_GROUP), -1, dtype=np.int32)
     od, oc = blk['direct'].reshape(MFMA_GROUP, MFMA_GROUP).cpu().numpy(), blk['conj'].reshape(MFMA_GROUP, MFMA_GROUP).cpu().numpy()
-    # direct[i, j] = b: baseline b runs from antenna i to antenna j; conj[i, j] = b: from j to i (_antenna_blocks)
-    for tab, swap in ((od, False), (oc, True)):
-        for i, j in zip(*np.nonzero(tab >= 0)):
-            a1, a2 = (j, i) if swap else (i, j)
-            if a1 == hub and a2 == hub:
-                return None                                      # the hub's autocorrelation: not a column sum of the image
-            if a1 == hub:
-                centre[0, vrow[a2]] = tab[i, j]
-            elif a2 == hub:
-                centre[1, vrow[a1]] = tab[i, j]
-            else:
-                r1, r2 = vrow[a1], vrow[a2]
-                if r1 // 32 <= r2 // 32:
-                    direct[r1, r2] = tab[i, j]
+
+    def tables(firsts, partner):
+        vrow = -np.ones(n, dtype=np.int64)
+        for k, (a, b) in enumerate(zip(firsts, partner)):
+            vrow[a] = k
+            if b >= 0:
+                vrow[b] = 64 + k
+        direct = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
+        conj = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
+        centre = np.full((2, MFMA_GROUP), -1, dtype=np.int32)
+        # direct[i, j] = b: baseline b runs from antenna i to antenna j; conj[i, j] = b: from j to i (_antenna_blocks)
+        for tab, swap in ((od, False), (oc, True)):
+            for i, j in zip(*np.nonzero(tab >= 0)):
+                a1, a2 = (j, i) if swap else (i, j)
+                if a1 == hub and a2 == hub:
+                    return None                                  # the hub's autocorrelation: not a column sum of the image
+                if a1 == hub:
+                    centre[0, vrow[a2]] = tab[i, j]
+                elif a2 == hub:
+                    centre[1, vrow[a1]] = tab[i, j]
                 else:
-                    conj[r2, r1] = tab[i, j]
-    nslots = int((direct >= 0).sum()) + int((conj >= 0).sum()) + int((centre >= 0).sum())
-    assert nslots == int((od >= 0).sum()) + int((oc >= 0).sum())
+                    r1, r2 = vrow[a1], vrow[a2]
+                    if r1 // 32 <= r2 // 32:
+                        direct[r1, r2] = tab[i, j]
+                    else:
+                        conj[r2, r1] = tab[i, j]
+        nslots = int((direct >= 0).sum()) + int((conj >= 0).sum()) + int((centre >= 0).sum())
+        assert nslots == int((od >= 0).sum()) + int((oc >= 0).sum())
+        # ... and every baseline slot of the plain block exactly once (a row order must never drop or double one)
+        slots = np.sort(np.concatenate([t[t >= 0] for t in (direct, conj, centre)]))
+        assert np.array_equal(slots, np.sort(np.concatenate([od[od >= 0], oc[oc >= 0]]))) and (np.diff(slots) > 0).all()
+        return direct, conj, centre
+
+    tabs = tables(firsts, partner)
+    if tabs is None:
+        return None
+    direct, conj, centre = tabs
     pos = np.asarray(P)[firsts] - c
     # a coplanar array measured from a centre in its plane: z = 0 within the tolerance of the pairing itself -> exactly 0 and
     # the `flat` licence (the kernels skip that term of the phase)
     flat = int(np.abs(pos[:, 2]).max() <= MIRROR_TOL)
     if flat:
         pos[:, 2] = 0.0
+    dev_t = lambda x: torch.as_tensor(x, device=dev).contiguous()
+    # the backward's own row order (round 6, _pair_ap_order): the same rows permuted, tables rebuilt for them; the forward keeps
+    # the plain order, so no bit of it moves
+    bwd = None
+    order = _pair_ap_order(pos) if PAIR_AP else list(range(len(firsts)))
+    if order != list(range(len(firsts))):
+        bf, bp = [firsts[k] for k in order], [partner[k] for k in order]
+        bd, bc, bcen = tables(bf, bp)
+        bwd = dict(firsts=bf, partner=bp, pos=dev_t(pos[order]), direct=dev_t(bd.reshape(-1)), conj=dev_t(bc.reshape(-1)),
+                   centre=None if hub is None else dev_t(bcen.reshape(-1)))
     return dict(blk, pos=torch.as_tensor(pos, device=dev).contiguous(), nrows=len(firsts), mirror=0, pair=1,
-                firsts=list(firsts), partner=list(partner), hub=hub, flat=flat,
+                firsts=list(firsts), partner=list(partner), hub=hub, flat=flat, bwd=bwd,
                 centre=None if hub is None else torch.as_tensor(centre.reshape(-1), device=dev),
                 cpass=0, fwd_cpass=0, self_pos=None, mf_self=0, mf_fwd=26 if len(firsts) > 32 or hub is not None else 7,
                 mf_bwd_real=30 if len(firsts) > 32 else 9,
@@ -598,8 +702,9 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
                     written.update(planes)
                     dst = ctypes.c_void_p(out.data_ptr() + 4 * (mp * st_mp + pp * st_pp + (0 if single else c)))
                     if blk.get('pair'):
-                        rc = lib.rime_fringe_pair_bwd_block(_ptr(blk['pos']), blk['nrows'], _ptr(blk['centre']), blk['flat'], *geo,
-                                                            _ptr(scale_pp), _ptr(blk['direct']), _ptr(blk['conj']),
+                        rows = blk.get('bwd') or blk             # the backward's own row order, where one exists
+                        rc = lib.rime_fringe_pair_bwd_block(_ptr(rows['pos']), blk['nrows'], _ptr(rows['centre']), blk['flat'], *geo,
+                                                            _ptr(scale_pp), _ptr(rows['direct']), _ptr(rows['conj']),
                                                             *shape, acc, dst, _ptr(ws), ws.numel(), _stream())
                         check(rc, 'rime_fringe_pair_bwd_block')
                         flops += blk['mf_bwd_real']
