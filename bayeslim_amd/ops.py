@@ -83,14 +83,19 @@ class FringeGeometry:
         self.max_blen = float(torch.linalg.norm(self.blvecs, dim=1).max().item())
         # channel grid: 1 = exactly uniform (rotation recurrence), 2 = uniform up to tiny residuals
         # (float32-rounded linspace: recurrence + first-order correction), 0 = arbitrary
+        # nu_phi: the largest phase residual [rad] the near-uniform kernels correct to first order only (they drop
+        # phi^2 / 2: fine for float32 below 2e-3, for float64 only below NU_F64_PHI -- see _fringe_call)
         self.f0 = float(fh[0])
+        self.nu_phi = 0.0
         if len(fh) > 1:
             self.df = float((fh[-1] - fh[0]) / (len(fh) - 1))
             eps = np.abs(fh - (self.f0 + self.df * np.arange(len(fh)))).max()
+            phi = 2 * np.pi * eps * max(self.max_blen, 1.0) / 2.99792458e8
             if eps <= 1e-9 * max(abs(self.df), 1.0):
                 self.uniform = 1
-            elif 2 * np.pi * eps * max(self.max_blen, 1.0) / 2.99792458e8 < 2e-3 and self.df != 0:
+            elif phi < 2e-3 and self.df != 0:
                 self.uniform = 2
+                self.nu_phi = float(phi)
             else:
                 self.uniform = 0
         else:
@@ -131,6 +136,11 @@ def _env_int(name, default):
     m = re.match(r'\s*([+-]?\d+)', v)
     return int(m.group(1)) if m else 0
 
+
+# float64 calls take the near-uniform kernels (MODE_ROT_NU: first-order channel correction, phi^2 / 2 dropped) only while
+# that term stays inside the float64 contract of 1e-11: phi < 1e-6 drops at most 5e-13 per fringe value; beyond it they
+# take the MODE_DIRECT kernels (one sincos per channel).  float32 keeps the 2e-3 bound of FringeGeometry (2e-6 dropped).
+NU_F64_PHI = 1e-6
 
 MFMA_MIN_ANTS = int(os.environ.get('RIME_MFMA_MIN_ANTS', '16'))   # 'auto' threshold (see _setup_antenna_path)
 MFMA_GROUP = 128          # antennas per group of the matrix-core path (4 x 4 tiles of 32)
@@ -860,13 +870,16 @@ def _fringe_call(geom, backward, inp, out, Npp, cplx, strides=None):
     nbytes = lib.rime_fringe_sum_workspace(code, geom.Nbl, geom.Nt, geom.Nf, geom.Pstride,
                                            geom.Nmp, Npp, int(cplx), int(backward))
     ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=inp.device)
+    uniform = int(geom.uniform)
+    if uniform == 2 and code == RIME_F64 and geom.nu_phi >= NU_F64_PHI:
+        uniform = 0
     prof = PROFILE
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     rc = fn(code, _ptr(geom.blvecs), _ptr(geom.sdir), _ptr(geom.freqs), _ptr(inp),
             geom.mp_offsets, _ptr(geom.bl_order), geom.Nbl, geom.Nt, geom.Nf, geom.Pstride,
-            geom.Nmp, Npp, int(cplx), geom.sign, int(geom.uniform), geom.f0, geom.df,
+            geom.Nmp, Npp, int(cplx), geom.sign, uniform, geom.f0, geom.df,
             geom.max_blen, strides, _ptr(out), _ptr(ws), ws.numel(), _stream())
     check(rc, 'rime_fringe_sum_bwd' if backward else 'rime_fringe_sum_fwd')
     if prof is not None:

@@ -105,9 +105,10 @@ def test_fringe_sum_fwd_bwd(ops, Npp, cplx, dtype, uniform):
     x = pad_psky(psky, Ps).to(cdt if cplx else rdt).cuda().requires_grad_(True)
     vis = ops.fringe_sum(x, geom)
     assert vis.shape == ref.shape and vis.dtype == cdt
+    # float64 on the float32-rounded grid (phi ~ 3e-5 > ops.NU_F64_PHI) takes the MODE_DIRECT kernels: no second-order
+    # term of the channel correction is dropped, the bound is the float64 one.  All three grids run the rotation modes
+    # here (1.9 .. 2.4 turns per channel); the shear modes are pinned by tests/test_fringe_valu_gpu.py
     tol_f, tol_g = (1e-11, 1e-11) if dtype == 'f64' else (1e-5, 1e-4)
-    if uniform == 'f32grid' and dtype == 'f64':
-        tol_f = tol_g = 1e-9          # neglected second-order term of the channel correction
     assert relmax(vis, ref) < tol_f
     (vis * gv.to(cdt).cuda().conj()).real.sum().backward()
     g = x.grad[..., :psky.shape[-1]]
