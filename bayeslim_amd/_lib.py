@@ -51,6 +51,10 @@ SIGNATURES = {
                                         _vp, _sz, _vp]),
     'rime_fringe_pair_bwd_block': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i, _i,
                                         _vp, _vp, _sz, _vp]),
+    'rime_fringe_pair_cross_fwd_block': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i,
+                                              _vp, _sz, _vp]),
+    'rime_fringe_pair_cross_bwd_block': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i, _i,
+                                              _vp, _vp, _sz, _vp]),
     'rime_gen_fringe': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'rime_comm_unique_id': (_i, [_vp]),
     'rime_comm_init': (_i, [ctypes.POINTER(ctypes.c_void_p), _i, _i, _vp]),

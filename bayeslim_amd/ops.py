@@ -160,7 +160,7 @@ def _group_capacity(n, group):
     return 64 if (group <= 64 or n <= 64) else 128
 
 
-def _antenna_blocks(bl_ants, Nant, bl_mp=None, ant_model=None, group=MFMA_GROUP):
+def _antenna_blocks(bl_ants, Nant, bl_mp=None, ant_model=None, group=MFMA_GROUP, groups=None):
     """
     Block decomposition of the pair matrix for the matrix-core path (see include/rime_hip.h).
     Antennas are ordered by (beam model, index) and cut into groups of <= `group` antennas that share
@@ -173,16 +173,26 @@ def _antenna_blocks(bl_ants, Nant, bl_mp=None, ant_model=None, group=MFMA_GROUP)
     int32 [128, 128] of baseline slots indexed by LOCAL antenna indices, or None when a pair occurs
     twice (not representable).  cpass: +1 the block holds direct entries only, -1 conj entries only,
     0 both (a complex psky then takes one pass per real plane).
+    groups: the antenna groups themselves (lists of antenna indices, each of <= MFMA_GROUP, together every antenna once)
+    in place of the cut by index -- the symmetric groups of _pair_cross_plan.  Every block carries the indices gi, gj of its groups.
     """
     if ant_model is None:
         ant_model = [0] * Nant
-    order = sorted(range(Nant), key=lambda a: (ant_model[a], a))
-    groups, gid, lid = [], {}, {}
-    for a in order:
-        if not groups or ant_model[groups[-1][0]] != ant_model[a] or len(groups[-1]) >= group:
-            groups.append([])
-        gid[a], lid[a] = len(groups) - 1, len(groups[-1])
-        groups[-1].append(a)
+    gid, lid = {}, {}
+    if groups is None:
+        order = sorted(range(Nant), key=lambda a: (ant_model[a], a))
+        groups = []
+        for a in order:
+            if not groups or ant_model[groups[-1][0]] != ant_model[a] or len(groups[-1]) >= group:
+                groups.append([])
+            gid[a], lid[a] = len(groups) - 1, len(groups[-1])
+            groups[-1].append(a)
+    else:
+        groups = [list(g) for g in groups]
+        for g, ants in enumerate(groups):
+            for k, a in enumerate(ants):
+                gid[a], lid[a] = g, k
+        assert len(gid) == Nant == sum(len(g) for g in groups) and max(len(g) for g in groups) <= MFMA_GROUP
     tabs = {}
 
     def get(key):
@@ -229,12 +239,12 @@ def _antenna_blocks(bl_ants, Nant, bl_mp=None, ant_model=None, group=MFMA_GROUP)
                 ants_i = [groups[gi][k] for k in keep]
             else:
                 ants_i = groups[gi]
-            blk = dict(ants_i=ants_i, ants_j=None, rows_i=len(ants_i), rows_j=0, mp=mp,
+            blk = dict(ants_i=ants_i, ants_j=None, rows_i=len(ants_i), rows_j=0, mp=mp, gi=gi, gj=gj,
                        cpass=(1 if nc == 0 else (-1 if nd == 0 else 0)))
         else:
             ri, cj_ = np.nonzero(used.any(1))[0], np.nonzero(used.any(0))[0]
             direct, conj = compact(direct, ri, cj_), compact(conj, ri, cj_)
-            blk = dict(ants_i=[groups[gi][k] for k in ri], ants_j=None, rows_i=len(ri), rows_j=0, mp=mp,
+            blk = dict(ants_i=[groups[gi][k] for k in ri], ants_j=None, rows_i=len(ri), rows_j=0, mp=mp, gi=gi, gj=gj,
                        cpass=(1 if nc == 0 else (-1 if nd == 0 else 0)))
             gi_ants, gj_ants = blk['ants_i'], [groups[gj][k] for k in cj_]
         if gi != gj:
@@ -567,6 +577,128 @@ def _pair_block(blk, P, dev):
                 direct=torch.as_tensor(direct.reshape(-1), device=dev), conj=torch.as_tensor(conj.reshape(-1), device=dev))
 
 
+# PAIR CROSS BLOCKS (csrc/fringe_xpair.hip): a point-symmetric array of MORE than MFMA_GROUP antennas.  The cut by index makes
+# groups that are not symmetric sets; here the ROWS of the conjugate-pair form (firsts, then antennas without a partner) are cut
+# into groups of <= PAIR_ROWS, a group being its rows together with their mirror antennas -- symmetric about the one centre c.
+# Diagonal blocks: the pair form above, unchanged.  The block between two groups: four real products of their rows' images.
+PAIR_CROSS = _env_int('RIME_PAIR_CROSS', 1) != 0       # RIME_PAIR_CROSS=0: the groups by index and the generic cross blocks
+
+
+def _plain_plan_cost(P, bl_ants, group=MFMA_GROUP):
+    """(MFMAs per 16-pixel K step, generated rows) of the real-psky forward on the groups cut by index, for the baselines
+    asked for: a diagonal block on the conjugate-pair form where its group is a symmetric set that fits (an estimate on the
+    host: the hub's autocorrelation and unused antennas are not looked at), a cross block only between groups that share a
+    baseline"""
+    P = np.asarray(P, dtype=np.float64)
+    Nant = len(P)
+    sizes = [min(group, Nant - k) for k in range(0, Nant, group)]
+    mf = rows = 0
+    for g, n in enumerate(sizes):
+        TA = (n + 31) // 32
+        lay = None
+        if n > 32 and PAIR:
+            lay = _pair_layout(P[g * group:g * group + n]) if n > 64 else _pair_layout(P[g * group:g * group + n], rows=32, hub_ok=False)
+        if lay is not None:
+            mf += 26 if n > 64 else 7
+            rows += len(lay[0])
+        else:
+            mf += 16 if (32 < n <= 48 and FWD_PACKED) else 12 * (TA * (TA - 1) // 2) + 7 * TA
+            rows += n
+    shared = {(min(a // group, b // group), max(a // group, b // group)) for a, b in bl_ants if a // group != b // group}
+    for x, y in shared:
+        ci, cj = _group_capacity(sizes[x], group), _group_capacity(sizes[y], group)
+        if (ci, cj) not in ((32, 32), (32, 64), (64, 32), (64, 64), (128, 128)):
+            ci = cj = 128
+        mf += 12 * (ci // 32) * (cj // 32)
+        rows += sizes[x] + sizes[y]
+    return mf, rows
+
+
+def _pair_cross_plan(antpos, bl_ants, rows=PAIR_ROWS):
+    """
+    Plan of a point-symmetric array with more than MFMA_GROUP antennas, on the host from numpy inputs alone: antpos (Nant, 3),
+    bl_ants the antenna pairs of the baselines in slot order.  Returns None when the array does not qualify (no symmetry of
+    the whole set, a pair listed twice, so many antennas without a partner that the plan contracts or generates no less than
+    the groups by index), else a dict
+      centre  c (3,)
+      groups  [dict(firsts, partner)]: antenna of every row and its mirror antenna (-1: none), <= `rows` rows each, sizes balanced
+              (no tail group too small for the pair form of its diagonal block)
+      ants    [firsts + partners of each group]: the groups for _antenna_blocks
+      cross   {(gi, gj), gi < gj: dict(rows_i, rows_j, pos (rows_i + rows_j, 3) from c, flat, direct, conj)} for the group pairs that
+              share a baseline; direct / conj int32 [128, 128] by virtual row (k: row k of I, 64 + k: its mirror) and virtual
+              column (the same for J): direct[r, c] = slot of the baseline r -> c, conj[r, c] = slot of c -> r.
+    """
+    P = np.asarray(antpos, dtype=np.float64)
+    Nant = len(P)
+    if Nant <= MFMA_GROUP or Nant > MFMA_MAX_ANTS or P.ndim != 2 or P.shape[1] != 3:
+        return None
+    found = _mirror_pairs(P)
+    if found is None:
+        return None
+    c, pairs, singles = found
+    firsts = [a for a, _ in pairs] + list(singles)
+    partner = [b for _, b in pairs] + [-1] * len(singles)
+    R = len(firsts)
+    G = (R + rows - 1) // rows
+    if G < 2:
+        return None                                       # (more than 128 antennas in <= 64 rows cannot be)
+    size = (R + G - 1) // G
+    groups = [dict(firsts=firsts[k:k + size], partner=partner[k:k + size]) for k in range(0, R, size)]
+    assert len(groups) == G and all(len(g['firsts']) <= rows for g in groups)
+    gid, vrow = {}, {}
+    for g, grp in enumerate(groups):
+        for k, (a, b) in enumerate(zip(grp['firsts'], grp['partner'])):
+            gid[a], vrow[a] = g, k
+            if b >= 0:
+                gid[b], vrow[b] = g, 64 + k
+    assert len(gid) == Nant
+    cross = {}
+    seen = set()
+    for slot, (a1, a2) in enumerate(bl_ants):
+        a1, a2 = int(a1), int(a2)
+        if (a1, a2) in seen:
+            return None
+        seen.add((a1, a2))
+        g1, g2 = gid[a1], gid[a2]
+        if g1 == g2:
+            continue
+        key = (min(g1, g2), max(g1, g2))
+        if key not in cross:
+            cross[key] = dict(direct=np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32),
+                              conj=np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32))
+        if g1 < g2:
+            cross[key]['direct'][vrow[a1], vrow[a2]] = slot          # I -> J: V[r, c]
+        else:
+            cross[key]['conj'][vrow[a2], vrow[a1]] = slot            # J -> I: conj(V[r, c])
+    # cost against the groups by index: matrix work and generated rows, both must shrink
+    bl = [(int(a), int(b)) for a, b in bl_ants]
+    mf_new = 26 * G + 48 * len(cross)
+    rows_new = R + sum(len(groups[gi]['firsts']) + len(groups[gj]['firsts']) for gi, gj in cross)
+    mf_old, rows_old = _plain_plan_cost(P, bl)
+    if mf_new >= mf_old or rows_new >= rows_old:
+        return None
+    for (gi, gj), blk in cross.items():
+        fi, fj = groups[gi]['firsts'], groups[gj]['firsts']
+        pos = np.concatenate([P[fi], P[fj]]) - c
+        flat = int(np.abs(pos[:, 2]).max() <= MIRROR_TOL)
+        if flat:
+            pos[:, 2] = 0.0
+        blk.update(rows_i=len(fi), rows_j=len(fj), pos=pos, flat=flat)
+    return dict(centre=c, groups=groups, cross=cross,
+                ants=[g['firsts'] + [b for b in g['partner'] if b >= 0] for g in groups])
+
+
+def _pair_cross_block(blk, plan_blk, dev):
+    """the device form of one block of _pair_cross_plan in place of the built plain cross block `blk` (include/rime_hip.h,
+    rime_fringe_pair_cross_fwd_block).  MFMAs per 16-pixel K step: forward 12 on each of the four tiles, whatever the row counts
+    (48); backward 12 per (row tile of I that holds a row, 16 rows of J that hold a row) and 32 pixels (64 x 64 rows: 48)."""
+    ri, rj = int(plan_blk['rows_i']), int(plan_blk['rows_j'])
+    dev_t = lambda x: torch.as_tensor(x, device=dev).contiguous()
+    return dict(blk, pos=dev_t(plan_blk['pos']), nrows=ri + rj, rows_i=ri, rows_j=rj, xpair=1, mirror=0, flat=int(plan_blk['flat']),
+                cpass=0, fwd_cpass=0, self_pos=None, mf_self=0, mf_fwd=48, mf_bwd_real=6 * ((ri + 31) // 32) * ((rj + 15) // 16),
+                direct=dev_t(plan_blk['direct'].reshape(-1)), conj=dev_t(plan_blk['conj'].reshape(-1)))
+
+
 def _dense_strides(t):
     """element strides (time, model pair, pol product, channel) of a (Nt,Nmp,Npp,Nf,P) tensor whose
     pixel axis is contiguous, or None when the tensor cannot be passed as is"""
@@ -653,6 +785,13 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
                                                    *shape, cflag, _ptr(ws), ws.numel(), _stream())
                 check(rc, 'rime_fringe_ant_fwd_block')
                 return blk['mf_self']
+            if blk.get('xpair'):                             # pair cross block: one real plane per call
+                rc = lib.rime_fringe_pair_cross_fwd_block(_ptr(blk['pos']), blk['rows_i'], blk['rows_j'], blk['flat'], *geo, src,
+                                                          _ptr(scale[mp, pp]), _ptr(rowmin[c][mp, pp]),
+                                                          _ptr(blk['direct']), _ptr(blk['conj']),
+                                                          *shape, _ptr(ws), ws.numel(), _stream())
+                check(rc, 'rime_fringe_pair_cross_fwd_block')
+                return blk['mf_fwd']
             if blk.get('pair'):                              # conjugate-pair form: one real plane per call (c picks it)
                 rc = lib.rime_fringe_pair_fwd_block(_ptr(blk['pos']), blk['nrows'], _ptr(blk['centre']), blk['flat'], *geo, src,
                                                     _ptr(scale[mp, pp]), _ptr(rowmin[c][mp, pp]),
@@ -711,6 +850,13 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
                     assert all((pl in written) == bool(acc) for pl in planes)
                     written.update(planes)
                     dst = ctypes.c_void_p(out.data_ptr() + 4 * (mp * st_mp + pp * st_pp + (0 if single else c)))
+                    if blk.get('xpair'):
+                        rc = lib.rime_fringe_pair_cross_bwd_block(_ptr(blk['pos']), blk['rows_i'], blk['rows_j'], blk['flat'], *geo,
+                                                                  _ptr(scale_pp), _ptr(blk['direct']), _ptr(blk['conj']),
+                                                                  *shape, acc, dst, _ptr(ws), ws.numel(), _stream())
+                        check(rc, 'rime_fringe_pair_cross_bwd_block')
+                        flops += blk['mf_bwd_real']
+                        continue
                     if blk.get('pair'):
                         rows = blk.get('bwd') or blk             # the backward's own row order, where one exists
                         rc = lib.rime_fringe_pair_bwd_block(_ptr(rows['pos']), blk['nrows'], _ptr(rows['centre']), blk['flat'], *geo,
@@ -756,7 +902,12 @@ def _setup_antenna_path(self, antpos, bl_ants, force=False, bl_mp=None, mp_pairs
         # without a model table the blocks read psky plane 0: several planes, or one plane that is not plane 0,
         # stay on the baseline-formulation kernels
         return
-    raw = _antenna_blocks(bl_ants, Nant, bl_mp if ant_model is not None else None, ant_model, group)
+    # a point-symmetric array of more than 128 antennas with one beam model: symmetric groups (_pair_cross_plan)
+    plan = None
+    if PAIR_CROSS and MIRROR and PAIR and ant_model is None and group == MFMA_GROUP and Nant > MFMA_GROUP:
+        plan = _pair_cross_plan(antpos.detach().to(torch.float64).cpu().numpy(), bl_ants)
+    raw = _antenna_blocks(bl_ants, Nant, bl_mp if ant_model is not None else None, ant_model, group,
+                          groups=None if plan is None else plan['ants'])
     if raw is None:
         return
     # the factorisation must reproduce the baseline vectors it replaces
@@ -822,13 +973,21 @@ def _setup_antenna_path(self, antpos, bl_ants, force=False, bl_mp=None, mp_pairs
         # which does not contract the mirror rows either
         pb = [(_pair_block(b, posh[np.asarray(r['ants_i'])], dev) if (PAIR and r['ants_j'] is None) else None)
               for b, r in zip(blocks, raw)]
+        # ... and the blocks between the symmetric groups of a larger array on the pair cross form
+        xb = [None] * len(blocks)
+        if plan is not None:
+            xb = [(_pair_cross_block(b, plan['cross'][(min(r['gi'], r['gj']), max(r['gi'], r['gj']))], dev)
+                   if r['ants_j'] is not None else None) for b, r in zip(blocks, raw)]
+            pb = [x if x is not None else q for x, q in zip(xb, pb)]
         if any(m is not None for m in mb) or any(q is not None for q in pb):
             self.ant['blocks_mirror'] = [m if m is not None else b for m, b in zip(mb, blocks)]
             self.ant['blocks_real'] = [q if q is not None else m for q, m in zip(pb, self.ant['blocks_mirror'])]
             self.ant['mirror_groups'] = [(bin(m['mirror']).count('1'), (m['nrows'] + 15) // 16)
                                          for m, q in zip(mb, pb) if m is not None and q is None]
             self.ant['pair_blocks'] = [(sum(1 for x in q['partner'] if x >= 0), q['nrows'], int(q['hub'] is not None))
-                                       for q in pb if q is not None]
+                                       for q in pb if q is not None and not q.get('xpair')]
+            if plan is not None:
+                self.ant['pair_cross_blocks'] = [(x['rows_i'], x['rows_j']) for x in xb if x is not None]
             if PAIR_CPLX and any(q is not None for q in pb):
                 # complex psky: pair blocks (two real passes: fwd_cpass = cpass = 0) in place of their plain blocks
                 self.ant['blocks_cplx'] = [q if q is not None else b for q, b in zip(pb, blocks)]

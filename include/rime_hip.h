@@ -223,6 +223,31 @@ int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const int* centr
                                long long st_t, long long st_f, long long st_p, int sign, int accumulate,
                                float* gpsky, const void* workspace, size_t workspace_bytes, void* stream);
 
+/* Conjugate-pair CROSS block, real psky (csrc/fringe_xpair.hip): the block between two groups I and J of ONE point-symmetric
+ * array with more than 128 antennas.  Both groups are closed under the mirror (a group is a set of rows together with their
+ * mirror antennas) and are measured from the SAME centre c, so the four quadrants V[x, y], V[x', y'], V[x', y], V[x, y'] follow
+ * from four real products of the rows' images: 48 MFMAs per 16 pixels instead of the 192 of a generic (128, 128) cross block,
+ * from rows_i + rows_j generated rows instead of twice as many.
+ *   antpos [rows_i + rows_j, 3]: positions measured from c of the rows of group I, then of group J (1 <= rows <= 64 each); a
+ *       row is one antenna of a mirror pair, an antenna without a partner, or the antenna at c itself (position 0).
+ *   pair_direct / pair_conj [128 * 128]: r = k for the antenna of row k of I, 64 + k for its mirror; c = l for the antenna of
+ *       row l of J, 64 + l for its mirror.  pair_direct[r*128 + c] = slot of the baseline r -> c (receives V[r, c]),
+ *       pair_conj[r*128 + c] = slot of the baseline c -> r (receives its conjugate), or -1.  A row without a mirror has no
+ *       entries in its mirror quadrants.
+ *   flat: as for the pair blocks.  psky / gpsky is ONE real plane (st_p = 1, or 2: a plane of an interleaved complex buffer).
+ * The other arguments, the workspace and _finish / _prepare are those of rime_fringe_pair_fwd_block / rime_fringe_pair_bwd_block;
+ * the blocks mix with every other block kind in one launch sequence.  -1 on a bad argument, -2 on a short workspace. */
+int rime_fringe_pair_cross_fwd_block(const double* antpos, int rows_i, int rows_j, int flat, const double* sdir,
+                                     const double* freqs, const float* psky, const float* scale, const float* rowmin,
+                                     const int* pair_direct, const int* pair_conj, int Nbl, int Nt, int Nf, int Pstride,
+                                     long long st_t, long long st_f, long long st_p, int sign,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+int rime_fringe_pair_cross_bwd_block(const double* antpos, int rows_i, int rows_j, int flat, const double* sdir,
+                                     const double* freqs, const float* gscale, const int* pair_direct,
+                                     const int* pair_conj, int Nbl, int Nt, int Nf, int Pstride,
+                                     long long st_t, long long st_f, long long st_p, int sign, int accumulate,
+                                     float* gpsky, const void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * ICRS (ra, dec) -> topocentric (zenith angle, azimuth East of North), degrees, float64.
  * Replaces the per-direction part of telescope_model.eq2top (telescope_model.py:469-502,
