@@ -85,6 +85,8 @@ SIGNATURES = {
     'rime_alm2pix_pack': (_i, [_vp, _d, _i, _i, _i, _vp, _vp]),
     'rime_alm2pix_fwd_packed': (_i, [_vp, _vp, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'rime_alm2pix_bwd_packed': (_i, [_vp, _vp, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'rime_sfb_fwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'rime_sfb_bwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 

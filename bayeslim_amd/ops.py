@@ -1756,3 +1756,108 @@ class _Alm2Pix(torch.autograd.Function):
 def alm2pix(alm, Ylm):
     """Re(alm @ Ylm): alm (..., Ncoeff) complex, Ylm (Ncoeff, Npix) complex -> (..., Npix) real."""
     return _Alm2Pix.apply(alm, Ylm)
+
+
+# ---------------------------------------------------------------------------------------
+# spherical Fourier-Bessel radial transform (csrc/sfb.hip)
+SFB_TILE_ROWS, SFB_TILE_COLS = 64, 32        # rime::SFB_TI, rime::SFB_TC
+
+
+class SFBPlan:
+    """
+    Device-side tables of one SFB radial transform (rime_sfb_fwd / _bwd): the real (Nk, Nr) matrices of all degrees packed
+    into ONE buffer `g` (degree after degree in the order given, each row-major), int32 `blocks` [Nblk, 5] = (g_off, Nk,
+    p_off, col_off, Nl), `cols` (the output columns of every degree), the forward tile list [(block, r0, c0)] over the
+    (Nr x Nl) outputs and the backward one [(block, n0, c0)] over the (Nk x Nl) parameter blocks, and `covered`: whether
+    every one of the Nlm output columns belongs to a degree (if not, the forward zero-fills its output first).
+    mats: sequence of real 2-D (Nk, Nr) tensors / arrays (Nk may be 0); col_lists: their output columns.
+    """
+    def __init__(self, mats, col_lists, Nr, Nlm, dtype, device):
+        assert dtype in (torch.float32, torch.float64), dtype
+        # the device as tensors report it ('cuda' -> 'cuda:0'), so that it compares equal to params.device
+        self.Nr, self.Nlm, self.dtype, self.device = int(Nr), int(Nlm), dtype, torch.empty(0, device=device).device
+        blocks, cols, tf, tb, flat = [], [], [], [], []
+        g_off = p_off = 0
+        for bi, (G, cl) in enumerate(zip(mats, col_lists)):
+            G = torch.as_tensor(G)
+            if G.is_complex():
+                raise ValueError('SFBPlan packs real matrices')
+            if G.ndim != 2 or G.shape[1] != self.Nr:
+                raise ValueError('degree %d: matrix of shape %s, expected (Nk, %d)' % (bi, tuple(G.shape), self.Nr))
+            cl = np.asarray(cl, dtype=np.int64).ravel()
+            if len(cl) and (cl.min() < 0 or cl.max() >= self.Nlm):
+                raise ValueError('degree %d: output column outside [0, %d)' % (bi, self.Nlm))
+            Nk, Nl = int(G.shape[0]), len(cl)
+            blocks.append((g_off, Nk, p_off, len(cols), Nl))
+            cols.extend(cl.tolist())
+            flat.append(G.detach().to(device=self.device, dtype=dtype).reshape(-1))
+            for c0 in range(0, Nl, SFB_TILE_COLS):
+                tf.extend((bi, r0, c0) for r0 in range(0, self.Nr, SFB_TILE_ROWS))
+                tb.extend((bi, n0, c0) for n0 in range(0, Nk, SFB_TILE_ROWS))
+            g_off += Nk * self.Nr
+            p_off += Nk * Nl
+        if len(set(cols)) != len(cols):
+            raise ValueError('two degrees claim the same output column')
+        if max(g_off, p_off, self.Nr * self.Nlm) >= 2 ** 31:
+            raise ValueError('SFB tables index with int32')
+        self.Nlmn, self.Nblk = p_off, len(blocks)
+        self.shapes = [(b[1], b[4]) for b in blocks]
+        self.covered = len(cols) == self.Nlm
+        i32 = lambda a, w: torch.as_tensor(np.asarray(a, dtype=np.int32).reshape(-1, w), device=self.device).contiguous()
+        self.blocks, self.cols = i32(blocks, 5), i32(cols or [0], 1)      # never a null table
+        self.tiles_fwd, self.tiles_bwd = i32(tf, 3), i32(tb, 3)
+        self.g = torch.cat(flat) if flat else torch.zeros(0, dtype=dtype, device=self.device)
+        if self.g.numel() == 0:
+            self.g = torch.zeros(1, dtype=dtype, device=self.device)       # a valid pointer for the all-empty case
+
+
+def _sfb_call(fn, name, inp, plan, tiles, cplx, B, res):
+    code = RIME_F32 if plan.dtype == torch.float32 else RIME_F64
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = fn(code, int(cplx), _ptr(inp), _ptr(plan.g), _ptr(plan.blocks), _ptr(plan.cols), _ptr(tiles), plan.Nblk,
+            tiles.shape[0], B, plan.Nlmn, plan.Nr, plan.Nlm, _ptr(res), _stream())
+    check(rc, name)
+    if prof is not None:
+        e1.record()
+        prof.append((name.replace('rime_', '') + '_kernel', e0, e1, 2 * int(cplx + 1) * B * plan.Nr * plan.Nlmn))
+
+
+class _SFBRadial(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, params, plan):
+        _require_cuda(params)
+        p = params.detach().contiguous()
+        _, rdt = _real_dtype(p)
+        if rdt != plan.dtype or p.device != plan.device:
+            raise TypeError('SFB plan built for %s on %s, parameters are %s on %s' % (plan.dtype, plan.device, p.dtype, p.device))
+        if p.ndim < 1 or p.shape[-1] != plan.Nlmn:
+            raise ValueError('parameters of shape %s, expected (..., %d)' % (tuple(p.shape), plan.Nlmn))
+        batch = p.shape[:-1]
+        B = int(np.prod(batch, dtype=np.int64))
+        alloc = torch.empty if plan.covered else torch.zeros
+        out = alloc(batch + (plan.Nr, plan.Nlm), dtype=p.dtype, device=p.device)
+        _sfb_call(lib.rime_sfb_fwd, 'rime_sfb_fwd', p, plan, plan.tiles_fwd, p.is_complex(), B, out)
+        ctx.plan, ctx.cplx, ctx.batch = plan, p.is_complex(), batch
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        plan = ctx.plan
+        go = gout.detach().contiguous()
+        B = int(np.prod(ctx.batch, dtype=np.int64))
+        gp = torch.empty(ctx.batch + (plan.Nlmn,), dtype=go.dtype, device=go.device)
+        _sfb_call(lib.rime_sfb_bwd, 'rime_sfb_bwd', go, plan, plan.tiles_bwd, ctx.cplx, B, gp)
+        return gp, None
+
+
+def sfb_radial(params, plan):
+    """
+    out[..., r, cols_l[c]] = sum_n g_l[n, r] params[..., p_off_l + n Nl + c] for every degree l of `plan` (an SFBPlan) in
+    one launch; params (..., Nlmn) real or complex in the plan's precision -> (..., Nr, Nlm) of the same dtype, columns
+    without a degree 0.  Differentiable w.r.t. params (one launch); the basis is fixed.
+    """
+    return _SFBRadial.apply(params, plan)

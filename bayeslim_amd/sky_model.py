@@ -161,15 +161,19 @@ class PixelSkyResponse:
     """
     params (Nstokes, 1, Nfreq_coeff, Npix_coeff) -> sky (Nstokes, 1, Nfreqs, Npix)
     (sky_model.py:503-720).  spatial_mode 'pixel' | 'linear' | 'alm' (spat_LM = LinearModel /
-    AlmModel); freq_mode 'channel' | 'linear' | 'powerlaw'.  ('bessel' needs the cosmology
-    module -- out of scope.)
+    AlmModel); freq_mode 'channel' | 'linear' | 'powerlaw'.  freq_mode='bessel' (which builds its radial basis from the
+    cosmology module) raises; a spherical Fourier-Bessel sky is composed instead from the pieces that are built, with the
+    comoving distance r of every channel as an input:
+        sfb = sph_harm.SFBModel(); sfb.setup_gln(l, r=r, m=m, r_min=..., r_max=..., kmax=..., r_crit=...)
+        R = PixelSkyResponse(freqs, spatial_mode='alm', spat_LM=alm_model, LM=sfb)      # params: complex (Nstokes, 1, Nlmn)
     """
     def __init__(self, freqs, comp_params=False, spatial_mode='pixel', freq_mode='channel',
                  device=None, transform_order=0, cosmo=None, spat_LM=None, freq_LM=None, f0=None,
                  gln=None, kbins=None, log=False, real_output=True, abs_output=False, LM=None,
                  sky0=None):
         if freq_mode == 'bessel':
-            raise NotImplementedError("freq_mode='bessel' is outside the RIME hot path")
+            raise NotImplementedError("freq_mode='bessel' is not built (it needs the cosmology module); use spatial_mode='alm' "
+                                      "with spat_LM=AlmModel and LM=sph_harm.SFBModel set up on the channels' comoving distances")
         self.freqs = freqs
         self.comp_params = comp_params
         self.Nfreqs = len(freqs)

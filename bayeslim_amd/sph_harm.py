@@ -1,12 +1,17 @@
 """
 Spherical-harmonic forward model with the reference's API (sph_harm.py): `gen_lm` (:14-40),
-`gen_sph2pix` for integer degree on the full sphere (:255-475) and `AlmModel`
-(:1244-1581) whose a_lm -> pixel product runs in the HIP kernel `rime_alm2pix_fwd/bwd`.
+`gen_sph2pix` for integer degree on the full sphere (:255-475), `AlmModel`
+(:1244-1581) whose a_lm -> pixel product runs in the HIP kernel `rime_alm2pix_fwd/bwd`, and the
+spherical Fourier-Bessel layer `gen_bessel2freq`, `sph_bessel_func`, `sph_bessel_kln` (:955-1241),
+`SFBModel` and `sfb_binning` (:1851-2145) whose radial transform t_lmn -> a_lm(r) runs in the HIP
+kernel `rime_sfb_fwd/bwd` (one launch for all degrees).
 
 Out of scope (one-off host setup in the reference): cut-sky (cap / stripe)
-non-integer-degree bases built from hypergeometric functions, spherical Fourier-Bessel models,
-HDF5 Ylm files.
+non-integer-degree bases built from hypergeometric functions, HDF5 Ylm files; of the SFB layer
+`SFBModel.least_squares` (needs the reference's linalg module), boundary condition 3 and the cosmology
+(frequency -> comoving distance: r is an input).
 """
+import copy
 import math
 
 import numpy as np
@@ -267,3 +272,291 @@ class AlmModel:
         self.__dict__.pop('_Ylm_cast_cache', None)
         if self.LM is not None:
             self.LM.push(device)
+
+
+# ---------------------------------------------------------------------------------------
+# spherical Fourier-Bessel radial basis (sph_harm.py:955-1241) -- host set-up, float64 numpy
+# ---------------------------------------------------------------------------------------
+def _int_degree(l):
+    li = int(round(float(l)))
+    if not np.isclose(float(l), li, atol=1e-9, rtol=0) or li < 0:
+        raise ValueError('integer degree l >= 0 only (got %r): the non-integer-degree bases are out of scope' % (l,))
+    return li
+
+
+def _sph_jn(l, z, deriv=False):
+    from scipy import special
+    return special.spherical_jn(l, np.asarray(z, dtype=np.float64), derivative=bool(deriv))
+
+
+def _sph_yn(l, z, deriv=False):
+    """y_l clipped from below at -1e50, as the reference clips it wherever it divides or adds"""
+    from scipy import special
+    with np.errstate(all='ignore'):
+        return np.clip(special.spherical_yn(l, np.asarray(z, dtype=np.float64), derivative=bool(deriv)), -1e50, np.inf)
+
+
+def sph_bessel_kln(l, r_min, r_max, kmax=0.5, dk_factor=0.5, decimate=False, bc_type=2, add_kzero=False):
+    """
+    Radial wavenumbers k_ln [1/Mpc] of degree l that meet the boundary condition on a ball (r_min ~ 0) or a shell
+    [r_min, r_max] (sph_harm.py:1171-1241): bc_type 1 (Dirichlet, the function vanishes at the edges) or 2 (Neumann, its
+    derivative does); bc_type 3 (potential) is not built.  The condition is sampled on the reference's grid (from
+    kmin = 1e-4 in steps of kmin * dk_factor up to kmax) and each sign change refined with utils.get_zeros.
+    decimate keeps every other root; add_kzero prepends k = 0 for l = 0.
+    """
+    if bc_type == 3:
+        raise NotImplementedError('bc_type=3 (potential boundary condition) is not built')
+    if bc_type not in (1, 2):
+        raise ValueError('bc_type must be 1 or 2')
+    li = _int_degree(l)
+    kmin = 1e-4
+    dk = kmin * dk_factor
+    ks = np.linspace(kmin, kmax, int((kmax - kmin) // dk) + 1)
+    d = bc_type == 2
+    if np.isclose(r_min, 0):
+        y = _sph_jn(li, ks * r_max, d)
+    else:
+        y = _sph_jn(li, ks * r_min, d) * _sph_yn(li, ks * r_max, d) - _sph_jn(li, ks * r_max, d) * _sph_yn(li, ks * r_min, d)
+    k = utils.get_zeros(ks, y)
+    if decimate:
+        k = k[::2]
+    if add_kzero and li == 0:
+        k = [0.0] + list(k)
+    return np.asarray(k, dtype=np.float64)
+
+
+def sph_bessel_func(l, k, r, method='shell', bc_type=2, r_crit=None, renorm=False, device=None, dtype=None):
+    """
+    Radial basis g_l(k_n r) = j_l(k_n r) + A_ln y_l(k_n r), (Nk, Nr) (sph_harm.py:1087-1168).  method 'ball': A = 0;
+    'shell': A_ln = -j_l(k r_crit) / y_l(k r_crit) (bc_type 1) or the same ratio of derivatives (bc_type 2) at the edge
+    r_crit, for k > 0.  y_l is clipped at -1e50.  Integer l only (scipy.special.spherical_jn / spherical_yn).
+    renorm scales each row so that sum_r r^2 |g|^2 = pi / 2 / max(k, 1e-4)^2.  Evaluated in float64, returned as `dtype`.
+    """
+    if bc_type == 3:
+        raise NotImplementedError('bc_type=3 (potential boundary condition) is not built')
+    if method not in ('ball', 'shell'):
+        raise ValueError("didn't recognize method {}".format(method))
+    if method == 'shell' and r_crit is None:
+        raise ValueError("method='shell' needs r_crit")
+    li = _int_degree(l)
+    k = np.atleast_1d(np.asarray(utils.tensor2numpy(k), dtype=np.float64))
+    r = np.atleast_1d(np.asarray(utils.tensor2numpy(r), dtype=np.float64))
+    kr = k[:, None] * r[None, :]
+    g = _sph_jn(li, kr).reshape(len(k), len(r))
+    if method == 'shell':
+        pos = k > 0
+        if pos.any():
+            d = bc_type == 2
+            A = -_sph_jn(li, k[pos] * r_crit, d) / _sph_yn(li, k[pos] * r_crit, d)
+            g[pos] += A[:, None] * _sph_yn(li, kr[pos])
+    if renorm:
+        g *= np.sqrt(np.pi / 2 * k.clip(1e-4) ** -2.0 / np.sum(r ** 2 * np.abs(g) ** 2, axis=1))[:, None]
+    return torch.as_tensor(g, device=device).to(dtype if dtype is not None else _float())
+
+
+def gen_bessel2freq(l, r, kbins=None, Nproc=None, Ntask=10, device=None, dtype=None, method='shell', bc_type=2,
+                    renorm=True, r_crit=None, use_pathos=False, **kln_kwargs):
+    """
+    Transform matrices sqrt(2/pi) r^2 max(k, 1e-4) g_l(k r) from radial wavenumber to line-of-sight distance, one per
+    unique degree of l (sph_harm.py:955-1084).  Returns (gln, kln): dicts keyed by degree (in ascending order) of
+    (Nk, Nr) tensors and of the k_ln arrays.  kbins: precomputed k_ln per degree; otherwise kln_kwargs (r_min, r_max and
+    the keywords of sph_bessel_kln) give them.  renorm divides every row by its 2-norm (clipped at 1e-20).
+    Nproc, Ntask and use_pathos (the reference's multiprocessing over degrees) are accepted and IGNORED: the scipy
+    evaluation takes a fraction of a second per degree.  Evaluated in float64 whatever the default dtype, then cast.
+    """
+    r = np.atleast_1d(np.asarray(utils.tensor2numpy(r), dtype=np.float64))
+    dtype = dtype if dtype is not None else _float()
+    kw = copy.deepcopy(kln_kwargs)
+    if kbins is None:
+        r_min, r_max = kw.pop('r_min'), kw.pop('r_max')
+    gln, kln = {}, {}
+    for ll in np.unique(utils.tensor2numpy(l)):
+        k = sph_bessel_kln(ll, r_min, r_max, bc_type=bc_type, **kw) if kbins is None else kbins[ll]
+        k64 = np.atleast_1d(np.asarray(utils.tensor2numpy(k), dtype=np.float64))
+        gl = sph_bessel_func(ll, k64, r, method=method, bc_type=bc_type, r_crit=r_crit, dtype=torch.float64).numpy()
+        G = np.sqrt(2 / np.pi) * r ** 2 * k64[:, None].clip(1e-4) * gl
+        if renorm:
+            G = G / np.sqrt(np.sum(np.abs(G) ** 2, axis=1, keepdims=True).clip(1e-40))
+        gln[ll] = torch.as_tensor(G, device=device).to(dtype)
+        kln[ll] = k
+    return gln, kln
+
+
+class SFBModel:
+    """
+    Radial step of the spherical Fourier-Bessel transform, a_lm(r) = sum_n g_l(k_ln r) t_lmn (sph_harm.py:1851-2066):
+    params (..., Nlmn) -> (..., Nr, Nlm).  The Nlmn axis is the concatenation, in the key order of `gln`, of per-degree
+    blocks laid out [Nk][Nl] (k slow, column fast); the output columns of a degree are where `l` equals its key; columns
+    whose degree has no key are 0.  All degrees run in ONE HIP launch (ops.sfb_radial) and one more backwards, instead
+    of the reference's Python loop of per-degree matmuls.  Complex params give a complex output, real params a real one.
+    The matrices are real: a complex-typed gln (which the reference needs, real @ complex raises in torch) is accepted
+    when its imaginary part is 0 and stored once on the device as one packed real buffer in the parameters' precision.
+    There is no CPU path.
+    """
+    def __init__(self, LM=None):
+        self.LM = LM
+
+    def setup_gln(self, l, gln=None, kln=None, out_dtype=None, r=None, m=None, **gln_kwargs):
+        """
+        l (Nlm,): degree of every output column; gln / kln: dicts from gen_bessel2freq (generated from r and gln_kwargs
+        if gln is None; kln then serves as kbins); m (Nlm,), optional, fills m_arr.  Sets params_idx / alm_idx /
+        alm_shape (per key), k_arr / l_arr / m_arr (per element of the Nlmn axis, in the reference's order), Nlmn, Nr,
+        Nlm, out_dtype, device.
+        """
+        if gln is None:
+            gln, kln = gen_bessel2freq(l, r, kbins=kln, dtype=out_dtype, **gln_kwargs)
+        for key, G in gln.items():
+            G = torch.as_tensor(G)
+            if G.is_complex() and bool((G.imag != 0).any()):
+                raise ValueError('gln[%r] has a non-zero imaginary part: the radial basis is real' % (key,))
+        self.gln, self.kln, self.l, self.m = gln, kln, l, m
+        l_np = np.asarray(utils.tensor2numpy(l))
+        self.params_idx, self.alm_idx, self.alm_shape = {}, {}, {}
+        k_arr, l_arr, m_arr = [], [], []
+        n0 = 0
+        for key, G in gln.items():
+            Nk = len(G)
+            idx = np.where(np.isclose(l_np, key, atol=1e-6, rtol=1e-10))[0]
+            Nl = len(idx)
+            self.params_idx[key] = slice(n0, n0 + Nk * Nl)
+            self.alm_idx[key] = utils._list2slice(list(idx))
+            self.alm_shape[key] = (G.shape[1], Nl)
+            k_arr.extend(list(kln[key]) * Nl)
+            l_arr.extend([key] * (Nk * Nl))
+            if m is not None:
+                m_arr.extend(mm for mm in np.asarray(m)[idx] for _ in range(Nk))
+            n0 += Nk * Nl
+        self.Nlmn = n0
+        self.k_arr, self.l_arr, self.m_arr = np.asarray(k_arr), np.asarray(l_arr), np.asarray(m_arr)
+        first = torch.as_tensor(next(iter(gln.values())))
+        self.Nr = first.shape[1]
+        self.Nlm = len(l_np)
+        self.out_dtype = out_dtype if out_dtype is not None else _cfloat()
+        self.device = first.device
+        self._drop_plans()
+
+    def _drop_plans(self):
+        self.__dict__.pop('_plans', None)
+
+    def __getstate__(self):
+        # pickle / deepcopy: the packed device buffer and the int32 tables are derived from gln; the copy packs again on
+        # first use (as AlmModel drops its conversion caches)
+        state = dict(self.__dict__)
+        state.pop('_plans', None)
+        return state
+
+    def _col_lists(self):
+        return [np.arange(self.Nlm)[self.alm_idx[key]] if isinstance(self.alm_idx[key], slice)
+                else np.asarray(self.alm_idx[key], dtype=np.int64) for key in self.gln]
+
+    def _make_plan(self, gln, dtype, device):
+        mats = []
+        for key, G in gln.items():
+            G = torch.as_tensor(G)
+            if G.is_complex():
+                if bool((G.imag != 0).any()):
+                    raise ValueError('gln[%r] has a non-zero imaginary part: the radial basis is real' % (key,))
+                G = G.real
+            mats.append(G)
+        return ops.SFBPlan(mats, self._col_lists(), self.Nr, self.Nlm, dtype, device)
+
+    def _plan(self, dtype, device):
+        plans = self.__dict__.setdefault('_plans', {})
+        key = (dtype, str(device))
+        if key not in plans:
+            plans[key] = self._make_plan(self.gln, dtype, device)
+        return plans[key]
+
+    def __call__(self, params, **kwargs):
+        return self.forward_gln(params, **kwargs)
+
+    def forward_gln(self, params, gln=None):
+        """
+        params (..., Nlmn) -> (..., Nr, Nlm).  gln: use these matrices instead of self.gln (same keys in the same order,
+        same shapes; packed for this call only).
+        """
+        if self.LM is not None:
+            params = self.LM(params)
+        if not params.is_cuda:
+            raise RuntimeError('SFBModel.forward_gln needs GPU tensors (no CPU path)')
+        rdt = params.real.dtype if params.is_complex() else params.dtype
+        if gln is None:
+            plan = self._plan(rdt, params.device)
+        else:
+            if list(gln.keys()) != list(self.gln.keys()):
+                raise ValueError('gln keys differ from those of setup_gln')
+            plan = self._make_plan(gln, rdt, params.device)
+            want = [(len(self.gln[key]), self.alm_shape[key][1]) for key in self.gln]
+            if plan.shapes != want:
+                raise ValueError('gln shapes differ from those of setup_gln')
+        return ops.sfb_radial(params, plan)
+
+    def push(self, device):
+        """move gln to a device, or re-type it (a dtype): the packed tables are rebuilt on the next call"""
+        for key in self.gln:
+            self.gln[key] = utils.push(torch.as_tensor(self.gln[key]), device)
+        if self.LM is not None:
+            self.LM.push(device)
+        if isinstance(device, torch.dtype):
+            self.out_dtype = device
+        else:
+            self.device = device
+        self._drop_plans()
+
+    def make_closure(self, params, loss_fn, target, real=False):
+        """closure for an optimiser: zero the gradient, loss_fn(forward_gln(params), target) [real parts if `real`],
+        backward, return the loss (sph_harm.py:2032-2066)"""
+        def closure(params=params, loss_fn=loss_fn, target=target, real=real):
+            if params.grad is not None:
+                params.grad.zero_()
+            out = self.forward_gln(params)
+            tgt = target
+            if real:
+                out, tgt = out.real, target.real
+            loss = loss_fn(out, tgt)
+            loss.backward()
+            return loss
+        return closure
+
+
+def sfb_binning(params, k_arr, kbins, var=None, wgts=None, l_arr=None, lbins=None):
+    """
+    Weighted average of a t_lmn tensor (..., Nlmn) into k bins (1-D) or (k, l) bins (2-D, when lbins is given), bins
+    given by their centres (sph_harm.py:2069-2145).  Returns (binned params, binned variance).  As in the reference, an
+    element belongs to bin i when np.digitize against the upper edges (centre + half the spacing to the next) gives i,
+    the 1-D branch normalises the weights of a bin by their total before summing, the 2-D branch divides the sums by
+    the total (variance: by its square) afterwards; empty bins give 0.
+    """
+    def edges(centres):
+        centres = np.asarray(centres, dtype=np.float64)
+        step = np.diff(centres)
+        return centres + np.concatenate([step, step[-1:]]) / 2
+
+    kind = np.digitize(k_arr, edges(kbins))
+    Nk = len(kbins)
+    if var is None:
+        var = torch.ones_like(params)
+    if wgts is None:
+        wgts = torch.ones_like(params, dtype=_float())
+    if lbins is None:
+        out = torch.zeros(params.shape[:-1] + (Nk,), dtype=params.dtype, device=params.device)
+        vout = torch.zeros_like(out)
+        for i in range(Nk):
+            sel = np.where(kind == i)[0]
+            w = wgts[..., sel]
+            w /= torch.sum(w).clip(1e-40)          # `w` is a copy (index-array selection): wgts itself is untouched
+            out[..., i] = torch.sum(params[..., sel] * w, dim=-1)
+            vout[..., i] = torch.sum(var[..., sel] * w ** 2, dim=-1)
+        return out, vout
+    lind = np.digitize(l_arr, edges(lbins))
+    Nl = len(lbins)
+    out = torch.zeros(params.shape[:-1] + (Nk, Nl), dtype=params.dtype, device=params.device)
+    vout = torch.zeros_like(out)
+    for i in range(Nk):
+        for j in range(Nl):
+            sel = np.where((kind == i) & (lind == j))[0]
+            w = wgts[..., sel]
+            tot = torch.sum(w).clip(1e-40)
+            out[..., i, j] = torch.sum(params[..., sel] * w, dim=-1) / tot
+            vout[..., i, j] = torch.sum(var[..., sel] * w ** 2, dim=-1) / tot ** 2
+    return out, vout

@@ -163,6 +163,36 @@ def _list2slice(inds):
     return inds
 
 
+def fit_zero(x, y):
+    """root of the parabola through three samples (x, y) that lies nearest x[0] (utils.py:1906-1913)"""
+    a, b, c = np.polyfit(x, y, 2)
+    disc = np.sqrt(b * b - 4 * a * c)
+    roots = ((-b + disc) / (2 * a), (-b - disc) / (2 * a))
+    return roots[0] if abs(roots[0] - x[0]) < abs(roots[1] - x[0]) else roots[1]
+
+
+def get_zeros(x, y):
+    """
+    Zero crossings of sampled y(x): at every sign change between consecutive samples (ignoring |y| <= 1e-40 jitter and a
+    first departure from exactly 0, which is no root) the three samples of smallest |y| among y[i-3 : i+3] carry a
+    parabola whose root is taken (utils.py:1916-1940).  Returns a list.
+    """
+    roots = []
+    sgn = np.sign(y)
+    mag = np.abs(y)
+    last = sgn[0]
+    for i in range(1, len(y)):
+        s = sgn[i]
+        if s == last or s == 0.0 or not mag[i] > 1e-40 or not np.isfinite(last):
+            continue
+        if last != 0.0:
+            lo = max(i - 3, 0)
+            near = np.argsort(mag[lo:i + 3])[:3] + lo
+            roots.append(fit_zero(x[near], y[near]))
+        last = s
+    return roots
+
+
 def _slice2tensor(obj, device=None):
     """a slice as the integer tensor it selects (utils.py:2136-2144)"""
     if isinstance(obj, slice):

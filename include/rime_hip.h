@@ -388,6 +388,28 @@ int rime_alm2pix_bwd_packed(const void* gout, const void* packed, double y_scale
                             void* galm, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Spherical Fourier-Bessel radial transform  a_lm(r) = sum_n g_l(k_ln r) t_lmn  for every degree l in ONE launch
+ * (SFBModel.forward_gln, sph_harm.py:1979-1982: a Python loop of one small matmul per degree) and its adjoint.
+ *   forward   out[b, r, cols[col_off + c]] = sum_n g[g_off + n Nr + r] * params[b, p_off + n Nl + c]
+ *   backward  gparams[b, p_off + n Nl + c] = sum_r g[g_off + n Nr + r] * gout[b, r, cols[col_off + c]]
+ *   params / gparams T [B, Nlmn] (x2 interleaved re, im when cplx = 1); out / gout T [B, Nr, Nlm] (x2 when cplx);
+ *   g T: the real (Nk, Nr) matrices of all degrees packed one after another, row n of a degree contiguous in r;
+ *   blocks int32 [Nblk][5] = (g_off, Nk, p_off, col_off, Nl) per degree; cols int32: the a_lm columns of every degree,
+ *   a degree's Nl entries starting at col_off; tiles int32 [Ntile][3] = (block, i0, c0): a 64 x 32 tile of the
+ *   (Nr x Nl) output of a degree forwards (i0 a multiple of 64 in r), of its (Nk x Nl) parameter block backwards
+ *   (i0 a multiple of 64 in n), c0 a multiple of 32.  One work-group per tile and batch row; the forward list holds
+ *   tiles for degrees with Nk = 0 too (their columns are stored as zeros), the backward list needs none for them.
+ * Every element covered by a tile is written exactly once (no atomics, no zero-fill, sums in ascending order:
+ * bit-reproducible); out columns that belong to no degree are NOT written -- the caller zero-fills when its tables
+ * do not cover all Nlm columns.  The parameter blocks partition [0, Nlmn), so gparams is fully defined.
+ * No gradient with respect to g.  Accumulation in T.  Ntile = 0 or B = 0 returns RIME_OK without a launch.
+ * ------------------------------------------------------------------------------------- */
+int rime_sfb_fwd(int dtype, int cplx, const void* params, const void* g, const int* blocks, const int* cols,
+                 const int* tiles, int Nblk, int Ntile, int B, int Nlmn, int Nr, int Nlm, void* out, void* stream);
+int rime_sfb_bwd(int dtype, int cplx, const void* gout, const void* g, const int* blocks, const int* cols,
+                 const int* tiles, int Nblk, int Ntile, int B, int Nlmn, int Nr, int Nlm, void* gparams, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Likelihood epilogue:  chi^2 = sum_i icov[i] * |pred[i] - data[i]|^2  over a complex visibility tensor
  * (N complex elements, interleaved), and its backward gpred[i] = 2 g icov[i] (pred[i] - data[i]).
  * Replaces `res = prediction - data; apply_icov(res, icov, cov_axis=None); torch.sum(...)` of
