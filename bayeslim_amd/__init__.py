@@ -5,5 +5,6 @@ gfx950 behind the C ABI of include/rime_hip.h; importing this package loads that
 fails loudly if it has not been built.
 """
 from . import _lib, ops            # noqa: F401  (loads librime_hip.so)
+from . import filt                 # noqa: F401,E402
 
 __version__ = '0.1.0'

@@ -1861,3 +1861,224 @@ def sfb_radial(params, plan):
     without a degree 0.  Differentiable w.r.t. params (one launch); the basis is fixed.
     """
     return _SFBRadial.apply(params, plan)
+
+
+# ---------------------------------------------------------------------------------------
+# grouped matrix filter along the last axis (csrc/filt.hip)
+FILT_TILE_LINES, FILT_TILE_ROWS = 64, 128    # rime::FILT_TL, rime::FILT_TC
+
+
+def filt_pack(W):
+    """
+    Filters [Nfilt, R, C] (real or complex) as the real, contraction-major buffer rime_filt_apply reads: [Nfilt, C, R] for a
+    real W; [Nfilt, 2C, R] for a complex one, rows 2c / 2c + 1 holding Re W[:, :, c] / -Im W[:, :, c].
+    """
+    W = torch.as_tensor(W)
+    if W.ndim != 3:
+        raise ValueError('filters of shape %s, expected (Nfilt, rows, columns)' % (tuple(W.shape),))
+    if W.is_complex():
+        Nf, R, C = W.shape
+        return torch.view_as_real(W.conj().resolve_conj()).reshape(Nf, R, 2 * C).transpose(1, 2).contiguous()
+    return W.transpose(1, 2).contiguous()
+
+
+def filt_tables(M, K, residual=False, input_idx=None):
+    """
+    The index tables of both directions of y = filter(x) with a (M, K) matrix G (numpy; see rime_filt_apply):
+    a dict with 'fwd' and 'bwd', each (ic int32, oc int32, base float64, s), and 'Ny', the length of an output line.
+    input_idx: None, or the M columns of the input (integers or a boolean mask of length K) the filtered samples replace.
+    """
+    M, K = int(M), int(K)
+    idx = None
+    if input_idx is not None:
+        idx = np.asarray(input_idx.detach().cpu() if isinstance(input_idx, torch.Tensor) else input_idx)
+        if idx.dtype == bool:
+            if idx.shape != (K,):
+                raise ValueError('boolean input_idx of shape %s, the filtered axis has %d samples' % (idx.shape, K))
+            idx = np.nonzero(idx)[0]
+        idx = idx.astype(np.int64).ravel()
+        idx = np.where(idx < 0, idx + K, idx)
+        if len(idx) != M:
+            raise ValueError('input_idx selects %d samples, G has %d rows' % (len(idx), M))
+        if len(idx) and (idx.min() < 0 or idx.max() >= K):
+            raise ValueError('input_idx outside [0, %d)' % K)
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError('input_idx repeats a sample')
+    elif residual and M != K:
+        raise ValueError('residual of a (%d, %d) filter: the output has another length than the input' % (M, K))
+    s = -1.0 if residual else 1.0
+    eyeK, eyeM = np.arange(K, dtype=np.int32), np.arange(M, dtype=np.int32)
+    sel = eyeM if idx is None else idx.astype(np.int32)
+    fwd = (eyeK, sel, np.full(M, 1.0 if residual else 0.0), s)
+    if residual:
+        bbase = np.ones(K)
+    elif idx is None:
+        bbase = np.zeros(K)
+    else:
+        bbase = np.ones(K)
+        bbase[idx] = 0.0
+    bwd = (sel, eyeK, bbase, s)
+    return {'fwd': fwd, 'bwd': bwd, 'Ny': M if idx is None else K, 'idx': idx}
+
+
+def filt_tiles(outer, Nbl, inner, bl2filt, with_pass=True):
+    """
+    Tile list of a tensor of outer x Nbl x inner lines (line = (o Nbl + b) inner + t) whose baseline b uses filter
+    bl2filt[b] (-1: none): int32 [Ntile, 65] = (filter, 64 line indices).  Lines are grouped by filter, filters ascending,
+    lines ascending inside a filter, -1 padding only at the end of a filter's last tile; the tiles of the unfiltered lines
+    (filter -1) come last and are left out when with_pass is False.  Returns (tiles, number of pass-through tiles).
+    """
+    b2f = np.asarray(bl2filt, dtype=np.int64).ravel()
+    if len(b2f) != Nbl:
+        raise ValueError('%d filter indices for %d baselines' % (len(b2f), Nbl))
+    if outer * Nbl * inner >= 2 ** 31:
+        raise ValueError('filter tables index lines with int32')
+    fl = np.broadcast_to(b2f[None, :, None], (outer, Nbl, inner)).reshape(-1)
+    out, npass = [], 0
+    order = sorted(f for f in np.unique(b2f) if f >= 0) + ([-1] if (with_pass and (b2f < 0).any()) else [])
+    for f in order:
+        lines = np.nonzero(fl == f)[0] if f >= 0 else np.nonzero(fl < 0)[0]
+        nt = -(-len(lines) // FILT_TILE_LINES)
+        padded = np.full(nt * FILT_TILE_LINES, -1, dtype=np.int32)
+        padded[:len(lines)] = lines
+        t = np.empty((nt, 1 + FILT_TILE_LINES), dtype=np.int32)
+        t[:, 0] = f
+        t[:, 1:] = padded.reshape(nt, FILT_TILE_LINES)
+        out.append(t)
+        if f < 0:
+            npass = nt
+    tiles = np.concatenate(out) if out else np.zeros((0, 1 + FILT_TILE_LINES), dtype=np.int32)
+    return tiles, npass
+
+
+class FiltPlan:
+    """
+    Device-side state of one grouped filter (rime_filt_apply) in one precision on one device: the filters G [Nfilt, M, K]
+    (or [M, K]) packed for the forward (W = G) and the adjoint (W = G^H), the tables ic / oc / base of both directions
+    (filt_tables) and the tile lists, cached per (outer, Nbl, inner, baseline -> filter, with_pass) layout.
+    """
+    def __init__(self, G, residual=False, input_idx=None, dtype=torch.float32, device='cuda'):
+        assert dtype in (torch.float32, torch.float64), dtype
+        G = torch.as_tensor(G)
+        if G.requires_grad:
+            raise ValueError('the filter matrix G requires grad: filt_apply differentiates with respect to the data only')
+        if G.ndim == 2:
+            G = G[None]
+        if G.ndim != 3 or 0 in G.shape:
+            raise ValueError('G of shape %s, expected (Nfilt, M, K) or (M, K)' % (tuple(G.shape),))
+        self.dtype, self.device = dtype, torch.empty(0, device=device).device
+        _require_cuda(torch.empty(0, device=self.device))
+        self.Nfilt, self.M, self.K = (int(n) for n in G.shape)
+        self.cplx, self.residual = G.is_complex(), bool(residual)
+        tab = filt_tables(self.M, self.K, residual, input_idx)
+        self.Ny, self.has_idx = tab['Ny'], tab['idx'] is not None
+        G = G.detach().to(device=self.device, dtype=(_lib_cdtype(dtype) if self.cplx else dtype))
+        dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), device=self.device).to(dt).contiguous()
+        self.W = {'fwd': filt_pack(G), 'bwd': filt_pack(G.transpose(1, 2).conj() if self.cplx else G.transpose(1, 2))}
+        self.tab = {d: (dev(tab[d][0], torch.int32), dev(tab[d][1], torch.int32), dev(tab[d][2], dtype), tab[d][3])
+                    for d in ('fwd', 'bwd')}
+        self._tiles = {}
+
+    def tiles(self, outer, Nbl, inner, bl2filt, with_pass):
+        key = (int(outer), int(Nbl), int(inner), tuple(int(f) for f in bl2filt), bool(with_pass))
+        if key not in self._tiles:
+            t, npass = filt_tiles(key[0], key[1], key[2], key[3], key[4])
+            if len(t) and t[:, 0].max() >= self.Nfilt:
+                raise ValueError('a baseline names filter %d, the plan holds %d' % (t[:, 0].max(), self.Nfilt))
+            self._tiles[key] = (torch.as_tensor(t, device=self.device).contiguous(), npass)
+        return self._tiles[key]
+
+
+def _lib_cdtype(dtype):
+    return torch.complex64 if dtype == torch.float32 else torch.complex128
+
+
+def _filt_call(plan, direction, x, y, tiles, npass):
+    ic, oc, base, s = plan.tab[direction]
+    M, K = (plan.M, plan.K) if direction == 'fwd' else (plan.K, plan.M)
+    Nx, Ny = x.shape[-1], y.shape[-1]
+    nlines = x.numel() // Nx
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = lib.rime_filt_apply(RIME_F32 if plan.dtype == torch.float32 else RIME_F64, int(plan.cplx), _ptr(x), _ptr(plan.W[direction]),
+                             _ptr(ic), _ptr(oc), _ptr(base), _ptr(tiles), tiles.shape[0], npass, plan.Nfilt, M, K, Nx, Ny,
+                             nlines, s, _ptr(y), _stream())
+    check(rc, 'rime_filt_apply')
+    if prof is not None:
+        e1.record()
+        prof.append(('filt_kernel', e0, e1, 2 * (4 if plan.cplx else 2) * nlines * M * K))
+
+
+class _FiltApply(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, plan, layout):
+        _require_cuda(x)
+        xc = x.detach().contiguous()
+        if not xc.is_complex():
+            raise TypeError('filt_apply runs on complex lines, got %s' % xc.dtype)
+        _, rdt = _real_dtype(xc)
+        if rdt != plan.dtype or xc.device != plan.device:
+            raise TypeError('filter plan built for %s on %s, data are %s on %s' % (plan.dtype, plan.device, xc.dtype, xc.device))
+        if xc.ndim < 1 or xc.shape[-1] != plan.K:
+            raise ValueError('data of shape %s, the filter takes %d samples along the last axis' % (tuple(xc.shape), plan.K))
+        batch = xc.shape[:-1]
+        nlines = int(np.prod(batch, dtype=np.int64))
+        if layout is None:
+            layout = (1, 1, (0,))
+        Nbl, inner, b2f = layout
+        if Nbl * inner == 0 or nlines % (Nbl * inner):
+            raise ValueError('%d lines do not divide into %d baselines x %d' % (nlines, Nbl, inner))
+        outer = nlines // (Nbl * inner)
+        if min(b2f) < 0 and plan.Ny != plan.K:
+            raise ValueError('unfiltered baselines pass through unchanged, but the filter maps %d samples to %d' % (plan.K, plan.Ny))
+        if plan.has_idx:
+            y = xc.clone()                              # the kernel writes the input_idx columns of the filtered lines only
+        else:
+            y = torch.empty(batch + (plan.Ny,), dtype=xc.dtype, device=xc.device)
+        if nlines:
+            tiles, npass = plan.tiles(outer, Nbl, inner, b2f, not plan.has_idx)
+            _filt_call(plan, 'fwd', xc, y, tiles, npass)
+        ctx.plan, ctx.geom = plan, (outer, Nbl, inner, b2f)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        plan = ctx.plan
+        g = gy.detach().contiguous()
+        gx = torch.empty(g.shape[:-1] + (plan.K,), dtype=g.dtype, device=g.device)
+        if gx.numel():
+            tiles, npass = plan.tiles(*ctx.geom, True)
+            _filt_call(plan, 'bwd', g, gx, tiles, npass)
+        return gx, None, None
+
+
+def filt_apply(x, plan, dim=-1, layout=None):
+    """
+    y[l, oc[i]] = s sum_k G[f(l)][i, k] x[l, k] + base[i] x[l, oc[i]] along axis `dim` of a complex x, in one launch
+    (rime_filt_apply) and one more backwards; `plan` is a FiltPlan.  layout = (Nbl, inner, bl2filt): the lines of x (all axes
+    but `dim`, flattened) are outer x Nbl x inner and baseline b uses filter bl2filt[b], -1 leaving its lines as they are;
+    None: every line uses filter 0.  Only the last, contiguous axis runs in the kernel: any other `dim` costs one extra
+    transposition pass each way (movedim(dim, -1).contiguous(), kernel, movedim back), and `layout` then describes the lines
+    of the transposed tensor.  A real x is filtered as a complex one with a zero imaginary part (one more pass) and comes
+    back real when G is real.  Differentiable with respect to x only.
+    """
+    _require_cuda(x)
+    if x.ndim < 1:
+        raise ValueError('filt_apply needs at least one axis')
+    if layout is not None:
+        layout = (int(layout[0]), int(layout[1]), tuple(int(f) for f in layout[2]))
+    was_real = not x.is_complex()
+    if was_real:
+        x = torch.complex(x, torch.zeros_like(x))
+    d = dim % x.ndim
+    if d != x.ndim - 1:
+        x = x.movedim(d, -1)
+    y = _FiltApply.apply(x, plan, layout)
+    if d != y.ndim - 1:
+        y = y.movedim(-1, d)
+    if was_real and not plan.cplx:
+        y = y.real
+    return y

@@ -410,6 +410,28 @@ int rime_sfb_bwd(int dtype, int cplx, const void* gout, const void* g, const int
                  const int* tiles, int Nblk, int Ntile, int B, int Nlmn, int Nr, int Nlm, void* gparams, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Grouped matrix filter along the last axis of a complex tensor: the reference's MatFilter / GPFilter / WedgeFilter
+ * (filt.py:89-160, 382-397: per baseline group a gather, a complex einsum and a scatter) in ONE launch, forward and adjoint.
+ * For every line l (Nx contiguous complex samples of x, Ny of y) with filter index f(l):
+ *     acc_i       = sum_k W[f(l)][i, k] * x[l, ic[k]]                  i < M, k < K
+ *     y[l, oc[i]] = s * acc_i + base[i] * x[l, oc[i]]
+ *   x T [Nlines][Nx][2], y T [Nlines][Ny][2] (interleaved re, im); ic int32 [K] (columns of x), oc int32 [M] (columns of y,
+ *   and of x where base[i] != 0), base T [M]; s = +1 or -1.
+ *   Wt T [Nfilt][KR][M], the filters TRANSPOSED (contraction index major): wcplx = 0: KR = K, Wt[f][k][i] = W[f][i][k];
+ *   wcplx = 1: KR = 2K, Wt[f][2k][i] = Re W[f][i][k], Wt[f][2k+1][i] = -Im W[f][i][k].
+ *   tiles int32 [Ntile][65] = (filter, 64 line indices, -1 = padding): the host groups the lines by filter.  A tile of
+ *   filter -1 copies its lines from x to y; Npass is the number of such tiles and Nx == Ny is required when Npass > 0.
+ *   One work-group per tile and per 128 output rows.  Every (line, oc[i]) of a listed line is written exactly once; no other
+ *   element of y is touched (the caller provides them); no atomics, sums in ascending k: bit-reproducible.
+ * float32 runs on v_mfma_f32_32x32x2_f32 (an exact fmaf chain), float64 on the vector ALU.  Forward: W = G, ic the identity,
+ * oc = input_idx or the identity, base = residual, s = residual ? -1 : +1.  Adjoint: W = G^H, ic = input_idx, oc the identity.
+ * No gradient with respect to W.  Ntile = 0 or Nlines = 0 returns RIME_OK without a launch.
+ * ------------------------------------------------------------------------------------- */
+int rime_filt_apply(int dtype, int wcplx, const void* x, const void* Wt, const int* ic, const int* oc, const void* base,
+                    const int* tiles, int Ntile, int Npass, int Nfilt, int M, int K, int Nx, int Ny, long long Nlines,
+                    double s, void* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Likelihood epilogue:  chi^2 = sum_i icov[i] * |pred[i] - data[i]|^2  over a complex visibility tensor
  * (N complex elements, interleaved), and its backward gpred[i] = 2 g icov[i] (pred[i] - data[i]).
  * Replaces `res = prediction - data; apply_icov(res, icov, cov_axis=None); torch.sum(...)` of
