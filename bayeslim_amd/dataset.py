@@ -258,6 +258,58 @@ class VisData(TensorData):
     def get_icov(self, bl=None, icov=None, try_view=False, **kwargs):
         return self.get_cov(bl=bl, cov=self.icov if icov is None else icov, try_view=try_view, **kwargs)
 
+    def bl_average(self, reds=None, wgts=None, redtol=1.0, inplace=False):
+        """
+        Average baselines together (dataset.py:1257-1361); baselines in no group of `reds` are dropped.  reds: list of
+        baseline groups as antenna pairs or baseline numbers, e.g. [[(0, 1), (1, 2)], [(2, 5), (3, 6)]]; default: the
+        redundant groups of self.antpos within redtol metres.  wgts: weights shaped like the data; default: self.icov
+        when it holds inverse variances (cov_axis None), else uniform.  Flags, cov and icov are averaged along.
+        inplace: edit this object, else return a new one.
+        """
+        if reds is None:
+            from . import telescope_model
+            red_info = telescope_model.build_reds(self.antpos, bls=self.bls, redtol=redtol)
+            reds, bl2red = red_info[0], red_info[2]
+        else:
+            bl2red = {}
+            for i, red in enumerate(reds):
+                for bl in red:
+                    bl2red[bl] = i
+        bls = self.bls if isinstance(list(bl2red.keys())[0], tuple) else self.blnums
+        Nmax = len(reds)
+        index = torch.as_tensor([bl2red.get(bl, Nmax) for bl in bls], device=self.data.device)
+        Nout_bls = index.unique().numel()
+        truncate = bool((index == Nmax).any())
+        if wgts is None and self.icov is not None and self.cov_axis is None:
+            wgts = self.icov
+        cov = None
+        if self.cov_axis is None:
+            if self.cov is not None:
+                cov = self.cov
+            elif self.icov is not None:
+                cov = 1 / self.icov.clip(1e-60)
+        avg_data, sum_wgts, avg_cov = average_data(self.data, -3, index, Nout_bls, wgts=wgts, cov=cov, truncate=truncate)
+        avg_flags = None
+        if self.flags is not None:
+            shape = list(avg_data.shape[-self.flags.ndim:])
+            if truncate:
+                shape[-3] += 1
+            # a group is flagged where all of its members are: count the unflagged members
+            count = torch.zeros(shape, dtype=torch.int64, device=avg_data.device)
+            count.index_add_(-3, index, (~self.flags).to(torch.int64))
+            avg_flags = count == 0
+            if truncate:
+                avg_flags = avg_flags[..., :-1, :, :]
+        avg_icov = None
+        if self.icov is not None:
+            avg_icov = 1 / avg_cov.clip(1e-60)
+        if self.cov is None:
+            avg_cov = None
+        vout = self if inplace else self.copy(copydata=False, copymeta=False)
+        vout.setup_data([red[0] for red in reds], vout.times, vout.freqs, pol=self.pol, data=avg_data, flags=avg_flags,
+                        cov=avg_cov, icov=avg_icov, cov_axis=None, history=self.history)
+        return vout
+
     def _inflate_by_redundancy(self, new_bls, red_bl_inds, try_view=False):
         """
         new VisData whose baseline axis is self's indexed by red_bl_inds (one redundant-group index per
@@ -285,6 +337,52 @@ class VisData(TensorData):
         mine = {bl2red[b]: i for i, b in enumerate(self.bls)}
         keep = [b for b in bls if bl2red[b] in mine]
         return self._inflate_by_redundancy(keep, [mine[bl2red[b]] for b in keep])
+
+
+
+def average_data(data, dim, index, N, wgts=None, cov=None, truncate=False):
+    """
+    Weighted average of a tensor along `dim` with torch.index_add_ (dataset.py:3940-4052): index[i] is the output slot
+    of element i along dim, N the number of slots, e.g. [0, 1, 0, 1] -> [mean(data[[0, 2]]), mean(data[[1, 3]])].
+    wgts: weights that broadcast against data (uniform when None); cov: variances of the data (its trailing axes),
+    propagated through the weighted sum; truncate: drop the last slot, the one that collects the elements no output needs.
+    Returns (avg_data, sum_wgts, avg_cov); avg_cov = sum w^2 cov / (sum w)^2, which is 1 / sum w for w = 1 / cov.
+    """
+    dim = int(np.arange(-data.ndim, 0, 1)[dim])
+    if wgts is None:
+        shape = [1] * data.ndim
+        shape[dim] = data.shape[dim]
+        wgts = torch.ones(shape, device=data.device, dtype=data.real.dtype if data.is_complex() else data.dtype)   # the reference: default dtype
+    if wgts.shape[dim] != data.shape[dim]:
+        shape = list(wgts.shape)
+        shape[dim] = data.shape[dim]
+        wgts = wgts.expand(shape)
+    shape = list(data.shape)
+    shape[dim] = N
+    avg_data = torch.zeros(shape, dtype=data.dtype, device=data.device)
+    shape = list(wgts.shape)
+    shape[dim] = N
+    sum_wgts = torch.zeros(shape, dtype=wgts.dtype, device=wgts.device)
+    sum_wgts.index_add_(dim, index, wgts)
+    avg_data.index_add_(dim, index, data * wgts)
+    avg_data = avg_data / sum_wgts.clip(1e-40)
+    if cov is not None:
+        assert cov.shape == data.shape[-cov.ndim:]
+        shape = list(cov.shape)
+        shape[dim] = N
+        avg_cov = torch.zeros(shape, dtype=cov.dtype, device=cov.device)
+        avg_cov.index_add_(dim, index, cov * wgts.pow(2))
+        avg_cov = avg_cov / sum_wgts.clip(1e-40).pow(2)
+    else:
+        avg_cov = None
+    if truncate:
+        slices = [slice(None)] * data.ndim
+        slices[dim] = slice(0, N - 1)
+        avg_data = avg_data[tuple(slices)]
+        sum_wgts = sum_wgts[tuple(slices[-wgts.ndim:])]
+        if cov is not None:
+            avg_cov = avg_cov[tuple(slices[-cov.ndim:])]
+    return avg_data, sum_wgts, avg_cov
 
 
 class RedVisInflate(utils.Module):

@@ -2082,3 +2082,217 @@ def filt_apply(x, plan, dim=-1, layout=None):
     if was_real and not plan.cplx:
         y = y.real
     return y
+
+
+# ---------------------------------------------------------------------------------------
+# batched 1-D DFT along the last axis with window, shifts, norm and epilogue fused (csrc/fft.hip)
+# ---------------------------------------------------------------------------------------
+FFT_MAX_N = 4096
+FFT_ABS, FFT_PEAKNORM, FFT_SQUARE, FFT_PEAK = 1, 2, 4, 8
+_FFT_EPILOGUES = {'none': 0, 'abs': FFT_ABS, 'peaknorm': FFT_PEAKNORM, 'square': FFT_SQUARE, 'peak': FFT_PEAK}
+
+
+def fft_radices(N):
+    """
+    Radix list of the Stockham passes of an N-point transform (product N): 4 while two factors of 2 are left, then a lone 2,
+    then 3s, 5s and every other prime factor ascending (those run as generic p-term butterflies).  N = 1: no pass.
+    """
+    N = int(N)
+    if N < 1:
+        raise ValueError('transform length %d' % N)
+    out, n = [], N
+    while n % 4 == 0:
+        out.append(4)
+        n //= 4
+    p = 2
+    while n > 1:
+        if p * p > n:
+            p = n
+        while n % p == 0:
+            out.append(p)
+            n //= p
+        p += 1 if p == 2 else 2
+    return out
+
+
+def fft_twiddles(N, inverse=False):
+    """exp(-+2 pi i j / N), j < N (plus for inverse), numpy complex128: the table of rime_fft_apply before its one rounding"""
+    return np.exp((2j if inverse else -2j) * np.pi * np.arange(int(N)) / int(N))
+
+
+def fft_epilogue_mask(epilogue):
+    """'none', 'abs', 'peaknorm', 'square', 'peak' or several joined by '+' -> the bit mask of rime_fft_apply; the kernel
+    applies them in the reference's order abs -> peaknorm -> square (-> peak) whatever the order of the names"""
+    if isinstance(epilogue, (int, np.integer)):
+        mask = int(epilogue)
+        if not 0 <= mask <= 15:
+            raise ValueError('unknown fft epilogue %r' % (epilogue,))
+        return mask
+    mask = 0
+    for name in str(epilogue).split('+'):
+        if name not in _FFT_EPILOGUES:
+            raise ValueError('unknown fft epilogue %r' % (epilogue,))
+        mask |= _FFT_EPILOGUES[name]
+    return mask
+
+
+def fft_scale(N, inverse, norm):
+    """the factor torch.fft applies: 'backward' (None) scales the inverse by 1/N, 'forward' the forward, 'ortho' both by 1/sqrt(N)"""
+    if norm in (None, 'backward'):
+        return 1.0 / N if inverse else 1.0
+    if norm == 'forward':
+        return 1.0 if inverse else 1.0 / N
+    if norm == 'ortho':
+        return 1.0 / np.sqrt(N)
+    raise ValueError("norm %r, expected None, 'backward', 'forward' or 'ortho'" % (norm,))
+
+
+class FFTPlan:
+    """
+    Host plan of an N-point transform in one precision on one device: the radix list and both twiddle tables
+    exp(-+2 pi i j / N), computed in float64, rounded once to the precision of the run and kept on the device.  The tables
+    are built on first use and dropped on pickling.
+    """
+    def __init__(self, N, dtype=torch.float32, device='cuda'):
+        dtype = {torch.complex64: torch.float32, torch.complex128: torch.float64}.get(dtype, dtype)
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError('fft plan in %s: float32 or float64' % dtype)
+        N = int(N)
+        if N < 1 or N > FFT_MAX_N:
+            raise ValueError('transform length %d: the kernel serves 1 ... %d' % (N, FFT_MAX_N))
+        self.N, self.dtype, self.device = N, dtype, torch.device(device)
+        self.radix = fft_radices(N)
+        self._radix_c = (ctypes.c_int * max(1, len(self.radix)))(*self.radix)
+
+    def table(self, inverse, device=None):
+        device = self.device if device is None else torch.device(device)
+        if device.type != 'cuda':
+            raise RuntimeError("bayeslim_amd ops need tensors on the GPU (got device '%s'); there is no CPU implementation" % device)
+        tw = self.__dict__.setdefault('_tw', {})
+        key = (bool(inverse), str(device))
+        if key not in tw:
+            tw[key] = torch.as_tensor(fft_twiddles(self.N, key[0])).to(_lib_cdtype(self.dtype)).to(device).contiguous()
+        return tw[key]
+
+    def serves(self, device):
+        """whether the plan's device names `device` ('cuda' without an index names every GPU)"""
+        return device.type == self.device.type and self.device.index in (None, device.index)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tw', None)
+        state.pop('_radix_c', None)
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._radix_c = (ctypes.c_int * max(1, len(self.radix)))(*self.radix)
+
+
+def _fft_call(plan, x, inverse, sh_in, sh_out, window, win_store, scale, mask, start, df):
+    """one launch of rime_fft_apply on the lines of a contiguous complex x [..., N]"""
+    N = plan.N
+    batch = tuple(x.shape[:-1])
+    nlines = int(np.prod(batch, dtype=np.int64))
+    rdt = plan.dtype
+    if mask & FFT_PEAK:
+        y = torch.empty(batch + (1,), dtype=rdt, device=x.device)
+    elif mask & (FFT_ABS | FFT_SQUARE):
+        y = torch.empty(batch + (N,), dtype=rdt, device=x.device)
+    else:
+        y = torch.empty(batch + (N,), dtype=x.dtype, device=x.device)
+    if nlines == 0:
+        return y
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = lib.rime_fft_apply(RIME_F32 if rdt == torch.float32 else RIME_F64, _ptr(x), _ptr(plan.table(inverse, x.device)), _ptr(window),
+                            int(win_store), plan._radix_c, len(plan.radix), N, nlines, int(bool(inverse)), int(sh_in), int(sh_out),
+                            float(scale), int(mask), float(start), float(df), _ptr(y), _stream())
+    check(rc, 'rime_fft_apply')
+    if prof is not None:
+        e1.record()
+        prof.append(('fft_kernel', e0, e1, nlines * N))
+    return y
+
+
+class _FFTApply(torch.autograd.Function):
+    """the linear part y = P_out s F P_in W x and its adjoint W P_in^H s F^H P_out^H through the same kernel"""
+    @staticmethod
+    def forward(ctx, x, plan, inverse, sh_in, sh_out, window, scale, mask, start, df):
+        xc = x.detach().contiguous()
+        y = _fft_call(plan, xc, inverse, sh_in, sh_out, window, False, scale, mask, start, df)
+        ctx.plan, ctx.args, ctx.window = plan, (inverse, sh_in, sh_out, scale), window
+        if mask:
+            ctx.mark_non_differentiable(y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        plan, N = ctx.plan, ctx.plan.N
+        inverse, sh_in, sh_out, scale = ctx.args
+        g = gy.detach().contiguous()
+        gx = _fft_call(plan, g, not inverse, (N - sh_out) % N, (N - sh_in) % N, ctx.window, True, scale, 0, 0.0, 1.0)
+        return (gx,) + (None,) * 9
+
+
+def fft_apply(x, plan, dim=-1, inverse=False, window=None, shift=False, norm=None, epilogue='none', start=0.0, df=1.0):
+    """
+    The reference's FFT block along axis `dim` of x in one launch of rime_fft_apply (`plan` an FFTPlan of that length):
+    multiply by the real `window` (a vector of N samples, or None), ifftshift (inverse and shift), transform (`inverse`:
+    the ifft), scale as torch.fft does for `norm`, fftshift (forward and shift), then the epilogue: 'none' (complex out),
+    'abs', 'square' (|.|^2), 'peaknorm' (divide the line by its max |.|), or several joined by '+', applied in the
+    reference's order abs -> peaknorm -> square.  With 'peak' (alone or after the others) the result is one real per line,
+    length 1 along `dim`: start + (n + delta) df with n the first index of the line's maximum and delta Quinn's second
+    estimator from the neighbours of n (wrapping round); not differentiable.
+
+    Differentiable with respect to x through the linear part (one more launch: conjugate twiddles, window on the store,
+    shifts swapped, the same scale); no gradient flows to the window.  The non-linear epilogues are fused only when no
+    gradient is asked for (torch.no_grad(), or x does not require grad); otherwise the kernel returns the complex
+    spectrum and abs / peak normalisation / square are the reference's torch expressions.  Only the last, contiguous axis
+    runs in the kernel: any other `dim` costs movedim(dim, -1).contiguous() and a movedim back.  A real x is promoted to
+    complex first.
+    """
+    _require_cuda(x)
+    if x.ndim < 1:
+        raise ValueError('fft_apply needs at least one axis')
+    if not x.is_complex():
+        if not x.is_floating_point():
+            x = x.to(plan.dtype)
+        x = torch.complex(x, torch.zeros_like(x))
+    _, rdt = _real_dtype(x)
+    if rdt != plan.dtype or not plan.serves(x.device):
+        raise TypeError('fft plan built for %s on %s, data are %s on %s' % (plan.dtype, plan.device, x.dtype, x.device))
+    d = dim % x.ndim
+    if d != x.ndim - 1:
+        x = x.movedim(d, -1)
+    N = plan.N
+    if x.shape[-1] != N:
+        raise ValueError('data of shape %s along the transformed axis last, the plan transforms %d samples' % (tuple(x.shape), N))
+    if window is not None:
+        window = torch.as_tensor(window).detach()
+        if window.is_complex() or window.numel() != N:
+            raise ValueError('the window is a real vector of %d samples' % N)
+        window = window.reshape(N).to(device=x.device, dtype=rdt).contiguous()
+    mask = fft_epilogue_mask(epilogue)
+    scale = fft_scale(N, inverse, norm)
+    sh_in = N // 2 if (shift and inverse) else 0
+    sh_out = (N - N // 2) % N if (shift and not inverse) else 0
+    needs_grad = torch.is_grad_enabled() and x.requires_grad
+    if mask & FFT_PEAK:
+        x, needs_grad = x.detach(), False
+    if mask == 0 or not needs_grad:
+        y = _FFTApply.apply(x, plan, bool(inverse), sh_in, sh_out, window, scale, mask, start, df)
+    else:
+        y = _FFTApply.apply(x, plan, bool(inverse), sh_in, sh_out, window, scale, 0, 0.0, 1.0)
+        if mask & FFT_ABS:
+            y = torch.abs(y)
+        if mask & FFT_PEAKNORM:
+            y = y / torch.max(torch.abs(y), dim=-1, keepdim=True).values
+        if mask & FFT_SQUARE:
+            y = torch.abs(y) ** 2
+    if d != y.ndim - 1:
+        y = y.movedim(-1, d)
+    return y

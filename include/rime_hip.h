@@ -432,6 +432,35 @@ int rime_filt_apply(int dtype, int wcplx, const void* x, const void* Wt, const i
                     double s, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Batched 1-D complex DFT along the last axis with the reference's FFT block fused around it (fft.py:99-202: window,
+ * ifftshift, fft, fftshift, abs, peak normalisation, |.|^2, and PeakDelay's per-line Quinn estimate) in ONE launch.
+ * For every line l of N interleaved complex samples, 1 <= N <= 4096:
+ *     X[k]   = wl[src] x[l, src],  src = (k + shift_in) mod N             (wl = win when win_on_store = 0, else 1)
+ *     Y      = sum_k X[k] tw[(j k) mod N]                                 tw T [N][2] = exp(-+2 pi i j / N), caller-built
+ *     z[k]   = ws[k] scale Y[(k + shift_out) mod N]                       (ws = win when win_on_store = 1, else 1)
+ *     y[l,k] = epilogue(z[k])
+ *   radix int32 [nradix], HOST memory: the Stockham pass radices, product N (2, 3, 4, 5 are written out, any other radix
+ *   runs as r-term sums); inverse (0 / 1) names the sign of tw's exponent (0: minus); win T [N] real or NULL.
+ *   epilogue: a sum of RIME_FFT_ABS (1), RIME_FFT_PEAKNORM (2, divide by the line's max |z|), RIME_FFT_SQUARE (4), applied in
+ *   that order as the reference does; y is T [nlines][N][2] for 0 and 2, T [nlines][N] real when 1 or 4 is set.  With
+ *   RIME_FFT_PEAK (8) added y is T [nlines]: start + (n + delta) df with n the first index of the maximum of |z| and delta
+ *   Quinn's second estimator from the epilogue's values at n - 1, n, n + 1 (indices wrap round).
+ * The adjoint of a call (epilogue 0) is the call with inverse flipped and the other table, shift_in' = (N - shift_out) mod N,
+ * shift_out' = (N - shift_in) mod N, win_on_store flipped and the same scale.
+ * One work-group per 1024 / N lines (one above 512 samples); every output is written exactly once, no atomics, sums in a
+ * fixed order: bit-reproducible.  All arguments are checked before any HIP call: RIME_EINVAL for N < 1, N > 4096, an
+ * unknown dtype or epilogue, a null x / y / tw, a radix list whose product is not N, a shift outside [0, N).
+ * nlines = 0 returns RIME_OK without a launch.
+ * ------------------------------------------------------------------------------------- */
+#define RIME_FFT_ABS 1
+#define RIME_FFT_PEAKNORM 2
+#define RIME_FFT_SQUARE 4
+#define RIME_FFT_PEAK 8
+int rime_fft_apply(int dtype, const void* x, const void* tw, const void* win, int win_on_store, const int* radix,
+                   int nradix, int N, long long nlines, int inverse, int shift_in, int shift_out, double scale,
+                   int epilogue, double start, double df, void* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Likelihood epilogue:  chi^2 = sum_i icov[i] * |pred[i] - data[i]|^2  over a complex visibility tensor
  * (N complex elements, interleaved), and its backward gpred[i] = 2 g icov[i] (pred[i] - data[i]).
  * Replaces `res = prediction - data; apply_icov(res, icov, cov_axis=None); torch.sum(...)` of
