@@ -89,6 +89,7 @@ SIGNATURES = {
     'rime_sfb_bwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rime_filt_apply': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _d, _vp, _vp]),
     'rime_fft_apply': (_i, [_i, _vp, _vp, _vp, _i, _ip, _i, _i, _ll, _i, _i, _i, _d, _i, _d, _d, _vp, _vp]),
+    'rime_lm_apply': (_i, [_i, _i, _i, _i, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _ll, _vp, _vp]),
 }
 
 

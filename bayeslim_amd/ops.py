@@ -2296,3 +2296,225 @@ def fft_apply(x, plan, dim=-1, inverse=False, window=None, shift=False, norm=Non
     if d != y.ndim - 1:
         y = y.movedim(-1, d)
     return y
+
+
+# ---------------------------------------------------------------------------------------
+# linear model y = A x along any axis with gather, coeff and real part fused (csrc/lm.hip)
+# ---------------------------------------------------------------------------------------
+LM_REG = 32          # rime::LM_REG: the register limit between the few-in and the few-out form of the strided kernels
+
+
+def lm_layout(R, K, I):
+    """
+    The storage order of M [R, K] for one launch: 'rk' (row-major, k contiguous) for the few-in strided kernels (I > 1,
+    K <= 32), which read a row of M per output row; 'kr' (r contiguous) for the few-out strided kernels and for the last-axis
+    kernel (I == 1), which read a column of M per input.
+    """
+    return 'rk' if (I > 1 and K <= LM_REG) else 'kr'
+
+
+class LMPlan:
+    """
+    Device-side state of one linear model y = A x (rime_lm_apply): the design matrix A (Nsamples, Nfeatures), real or complex,
+    the gather table idx along the contracted axis and the vector coeff of the un-gathered axis (or None).  The tables the
+    kernel reads -- A for the forward, A^H for the adjoint, each also as its real part and in either storage order
+    (lm_layout) -- are built on first use per precision and device from the master copy, which is kept as given, and dropped
+    on pickling and deep copies; a rebuilt table holds the same bits.  pre = coeff[idx] scales the gathered inputs.
+    """
+    def __init__(self, A, idx=None, coeff=None):
+        A = torch.as_tensor(A)
+        if A.requires_grad:
+            raise ValueError('the design matrix A requires grad: lm_apply differentiates with respect to the input only')
+        if A.ndim == 1:
+            A = A[:, None]                                 # one feature
+        if A.ndim != 2 or 0 in A.shape:
+            raise ValueError('A of shape %s, expected (Nsamples, Nfeatures)' % (tuple(A.shape),))
+        if not (A.is_floating_point() or A.is_complex()):
+            A = A.to(torch.get_default_dtype())
+        self.A = A.detach()
+        self.R, self.K = (int(n) for n in A.shape)
+        self.cplx = A.is_complex()
+        self.idx = self.coeff = None
+        self.K_in = None
+        if coeff is not None:
+            coeff = torch.as_tensor(coeff).detach().reshape(-1)
+            if coeff.is_complex():
+                raise TypeError('the fused coeff is a real vector; multiply a complex one into the input first')
+            self.coeff, self.K_in = coeff, int(coeff.numel())
+        if idx is not None:
+            idx = torch.as_tensor(idx).detach().reshape(-1).to(torch.int64)
+            if idx.numel() != self.K:
+                raise ValueError('idx names %d entries, A takes %d features' % (idx.numel(), self.K))
+            self.idx = idx
+            self.idx_min, self.idx_max = int(idx.min()), int(idx.max())
+            if self.idx_min < 0 or (self.K_in is not None and self.idx_max >= self.K_in):
+                raise IndexError('idx outside the indexed axis')
+        elif self.K_in is not None and self.K_in != self.K:
+            raise ValueError('coeff of %d entries, A takes %d features' % (self.K_in, self.K))
+
+    def _cache(self):
+        return self.__dict__.setdefault('_tabs', {})
+
+    def table(self, direction, real_part, layout, dtype, device):
+        """(buffer, m_rs, m_ks, R, K, complex) of M = A ('fwd') or A^H ('bwd'), or of Re(M), stored in `layout`"""
+        device = torch.device(device)
+        key = ('M', direction, bool(real_part), layout, dtype, str(device))
+        tabs = self._cache()
+        if key not in tabs:
+            M = self.A.to(device=device, dtype=(_lib_cdtype(dtype) if self.cplx else dtype))
+            if direction == 'bwd':
+                M = M.conj().T if self.cplx else M.T
+            if real_part and self.cplx:
+                M = M.real
+            R, K = (int(n) for n in M.shape)
+            if layout == 'rk':
+                buf, rs, ks = M.resolve_conj().contiguous(), K, 1
+            else:
+                buf, rs, ks = M.T.resolve_conj().contiguous(), 1, R
+            tabs[key] = (buf, rs, ks, R, K, buf.is_complex())
+        return tabs[key]
+
+    def matrix(self, direction, real_part, layout, dtype, device):
+        """the table as the matrix the kernel multiplies with, [R, K] (a view of the buffer)"""
+        buf, rs, ks, R, K, _ = self.table(direction, real_part, layout, dtype, device)
+        return buf if layout == 'rk' else buf.T
+
+    def gather(self, device, dtype=torch.int32):
+        """idx on the device, cached: int32 is the kernel's table, int64 what index_add_ / indexing take; None without idx"""
+        if self.idx is None:
+            return None
+        key = ('idx', dtype, str(torch.device(device)))
+        tabs = self._cache()
+        if key not in tabs:
+            tabs[key] = self.idx.to(device=device, dtype=dtype).contiguous()
+        return tabs[key]
+
+    def scale(self, dtype, device):
+        """pre = coeff[idx] (coeff without idx) in the run's precision, or None"""
+        if self.coeff is None:
+            return None
+        key = ('pre', dtype, str(torch.device(device)))
+        tabs = self._cache()
+        if key not in tabs:
+            c = self.coeff.to(device=device, dtype=dtype)
+            if self.idx is not None:
+                c = c[self.gather(device, torch.int64)]
+            tabs[key] = c.contiguous()
+        return tabs[key]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tabs', None)
+        return state
+
+    def __deepcopy__(self, memo):
+        new = type(self).__new__(type(self))
+        import copy
+        new.__dict__.update({k: copy.deepcopy(v, memo) for k, v in self.__getstate__().items()})
+        return new
+
+
+def _lm_call(plan, direction, x3, real_out, with_idx=True):
+    """
+    one launch of rime_lm_apply on a contiguous x3 [O, K_in, I]: 'fwd' gathers through plan.idx, scales by pre and applies A;
+    'bwd' applies A^H and scales the compact result [O, K, I] by pre.  real_out: Re(.) only.
+    """
+    O, K_in, I = (int(n) for n in x3.shape)
+    _, rdt = _real_dtype(x3)
+    xc = x3.is_complex()
+    real_part = bool(real_out and not xc)                     # Re(M x) of a real x: Re(M) x
+    R, K = (plan.R, plan.K) if direction == 'fwd' else (plan.K, plan.R)
+    buf, rs, ks, R, K, mc = plan.table(direction, real_part, lm_layout(R, K, I), rdt, x3.device)
+    idx = pre = post = None
+    if direction == 'fwd':
+        pre = plan.scale(rdt, x3.device)
+        if with_idx:
+            idx = plan.gather(x3.device)
+        if idx is not None:
+            if plan.idx_max >= K_in:
+                raise IndexError('idx reaches entry %d, the indexed axis holds %d' % (plan.idx_max, K_in))
+        elif K_in != K:
+            raise ValueError('the contracted axis holds %d entries, A takes %d' % (K_in, K))
+    else:
+        post = plan.scale(rdt, x3.device)
+        if K_in != K:
+            raise ValueError('the contracted axis holds %d entries, A gives %d' % (K_in, K))
+    out_real = bool(real_out and xc)
+    ycplx = (xc or mc) and not out_real
+    y = torch.empty((O, R, I), dtype=_lib_cdtype(rdt) if ycplx else rdt, device=x3.device)
+    if y.numel() == 0:
+        return y
+    prof = PROFILE
+    if prof is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    rc = lib.rime_lm_apply(RIME_F32 if rdt == torch.float32 else RIME_F64, int(xc), int(mc), int(out_real), _ptr(x3), _ptr(buf),
+                           rs, ks, _ptr(idx), _ptr(pre), _ptr(post), O, K, K_in, R, I, _ptr(y), _stream())
+    check(rc, 'rime_lm_apply')
+    if prof is not None:
+        e1.record()
+        prof.append(('lm_kernel', e0, e1, O * R * I * K))
+    return y
+
+
+def _lm_adjoint(plan, g3, K_in, want_real):
+    """A^H g with the scaling, scattered through idx to [O, K_in, I]; real when want_real"""
+    gx = _lm_call(plan, 'bwd', g3, want_real)
+    if plan.idx is not None:
+        full = torch.zeros((gx.shape[0], K_in, gx.shape[2]), dtype=gx.dtype, device=gx.device)
+        gx = full.index_add_(1, plan.gather(gx.device, torch.int64), gx)
+    return gx
+
+
+class _LMApply(torch.autograd.Function):
+    """y = A (coeff x)[idx] ('fwd') or its adjoint ('bwd') on x3 [O, K_in, I]; the backward pass is the other direction"""
+    @staticmethod
+    def forward(ctx, x3, plan, direction, out_real, K_in):
+        xc = x3.detach().contiguous()
+        ctx.plan, ctx.direction, ctx.xcplx, ctx.K_in, ctx.xdtype = plan, direction, xc.is_complex(), int(xc.shape[1]), xc.dtype
+        if direction == 'fwd':
+            return _lm_call(plan, 'fwd', xc, out_real)
+        return _lm_adjoint(plan, xc, K_in, out_real)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        g = gy.detach().contiguous()
+        if ctx.direction == 'fwd':
+            gx = _lm_adjoint(ctx.plan, g, ctx.K_in, not ctx.xcplx)
+        else:
+            gx = _lm_call(ctx.plan, 'fwd', g, not ctx.xcplx)
+        if gx.dtype != ctx.xdtype:
+            gx = gx.to(ctx.xdtype)                            # a real product for a complex input: zero imaginary part
+        return gx, None, None, None, None
+
+
+def lm_apply(x, plan, dim=0, out_real=False, adjoint=False, K_in=None):
+    """
+    y = A (coeff * x)[idx] along axis `dim` of x in one launch of rime_lm_apply (`plan` an LMPlan): x of up to 8 axes maps onto
+    [O, K_in, I] (the axes before `dim`, `dim`, the axes after it; the last axis, or a 1-D x, gives I = 1 and the last-axis
+    kernel), and y has A's Nsamples entries along `dim`.  x and A are real or complex, y is complex when either is; with
+    out_real only Re(A x) is computed and returned.  The run's precision is the wider of x's and A's.
+    adjoint=True applies coeff[idx] * (A^H x) instead and scatters it through idx with index_add_ onto K_in entries (default:
+    what the plan's coeff fixes, else A's Nfeatures).
+    Differentiable once with respect to x only (the other direction through the same kernel; the scatter through idx is a torch
+    index_add_); A, idx and coeff carry no gradient.  A non-contiguous x is made contiguous.  No CPU path.
+    """
+    _require_cuda(x)
+    if x.ndim < 1 or x.ndim > 8:
+        raise ValueError('lm_apply takes 1 to 8 axes, got %d' % x.ndim)
+    if not (x.is_floating_point() or x.is_complex()):
+        x = x.to(plan.A.real.dtype if plan.cplx else plan.A.dtype)
+    rx, ra = _real_dtype(x)[1], _real_dtype(plan.A)[1]
+    if rx != ra and ra == torch.float64:
+        x = x.to(torch.complex128 if x.is_complex() else torch.float64)
+    d = dim % x.ndim
+    shape = tuple(x.shape)
+    O, I = int(np.prod(shape[:d], dtype=np.int64)), int(np.prod(shape[d + 1:], dtype=np.int64))
+    if adjoint:
+        if K_in is None:
+            K_in = plan.K_in if plan.K_in is not None else plan.K
+        if plan.idx is not None and plan.idx_max >= K_in:
+            raise IndexError('idx reaches entry %d, the indexed axis holds %d' % (plan.idx_max, K_in))
+    y = _LMApply.apply(x.reshape(O, shape[d], I), plan, 'bwd' if adjoint else 'fwd', bool(out_real), K_in)
+    return y.reshape(shape[:d] + (y.shape[1],) + shape[d + 1:])

@@ -160,8 +160,9 @@ class PixelSky(SkyBase):
 class PixelSkyResponse:
     """
     params (Nstokes, 1, Nfreq_coeff, Npix_coeff) -> sky (Nstokes, 1, Nfreqs, Npix)
-    (sky_model.py:503-720).  spatial_mode 'pixel' | 'linear' | 'alm' (spat_LM = LinearModel /
-    AlmModel); freq_mode 'channel' | 'linear' | 'powerlaw'.  freq_mode='bessel' (which builds its radial basis from the
+    (sky_model.py:503-720).  spatial_mode 'pixel' | 'linear' | 'alm' (spat_LM = linear_model.LinearModel /
+    AlmModel); freq_mode 'channel' | 'linear' (freq_LM = linear_model.LinearModel along dim=-2, e.g.
+    LinearModel('poly', dim=-2, x=freqs, Ndeg=6, basis='legendre')) | 'powerlaw'.  freq_mode='bessel' (which builds its radial basis from the
     cosmology module) raises; a spherical Fourier-Bessel sky is composed instead from the pieces that are built, with the
     comoving distance r of every channel as an input:
         sfb = sph_harm.SFBModel(); sfb.setup_gln(l, r=r, m=m, r_min=..., r_max=..., kmax=..., r_crit=...)

@@ -39,6 +39,29 @@ def colat2lat(theta, deg=True):
     return (90.0 - theta) if deg else (math.pi / 2 - theta)
 
 
+def prep_xarr(x, d0=None, logx=False, whiten=False, x0=None, dx=None):
+    """
+    Prepare the sample axis of a polynomial basis (utils.py:200-241): divide by d0 if given, take the logarithm if logx,
+    then centre and scale (whiten_xarr) if whiten.  Returns (x, x0, dx); x0 and dx are passed through when not whitening.
+    """
+    x = x / d0 if d0 else x
+    x = torch.log(x) if logx else x
+    return whiten_xarr(x, x0, dx) if whiten else (x, x0, dx)
+
+
+def whiten_xarr(x, x0=None, dx=None):
+    """
+    Centre a monotonically increasing x by x0 (default: its mean) and scale it by 1 / dx (default: the largest centred value
+    plus half the mean spacing, so that uniform samples span [-1 + d/2, 1 - d/2]) (utils.py:244-279).  Returns (x, x0, dx).
+    """
+    x0 = x.mean() if x0 is None else x0
+    centred = x - x0
+    if dx is None:
+        half_step = (x[-1] - x[0]) / (2 * (len(x) - 1))
+        dx = centred.max() + half_step
+    return centred / dx, x0, dx
+
+
 # ---------------------------------------------------------------------------------------
 # hashing / device helpers
 # ---------------------------------------------------------------------------------------

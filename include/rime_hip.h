@@ -461,6 +461,29 @@ int rime_fft_apply(int dtype, const void* x, const void* tw, const void* win, in
                    int epilogue, double start, double df, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Linear model along a middle axis: the reference's LinearModel.forward (linear_model.py:121-169: params * coeff,
+ * index_select, matmul or einsum, .real) in ONE launch, and the same launch with M = A^H for its backward pass and for the
+ * A^H y product of least squares.  For a contiguous x [O][K_in][I] and a matrix M [R][K]:
+ *     y[o, r, i] = post[r] * sum_{k < K} M[r, k] * pre[k] * x[o, idx[k], i]              y [O][R][I] contiguous
+ *   x: T (xcplx = 0) or interleaved complex T (xcplx = 1); M likewise (mcplx), element (r, k) at element offset
+ *   r * m_rs + k * m_ks (both > 0; the kernels walk k fastest when I > 1 and K <= 32, r fastest otherwise: store M so that
+ *   this index is contiguous); y is complex when x or M is, unless out_real = 1: then only Re(M x) = Mr xr - Mi xi is
+ *   computed and y is real.  out_real needs a complex x: for a real x the caller passes Re(M).
+ *   idx int32 [K] (device): rows of x along the contracted axis, each in [0, K_in), repeats allowed; NULL: the identity, and
+ *   K_in must equal K.  The kernel does not check the entries of idx.  pre T [K], post T [R]: real scalings, or NULL.
+ * Forward: M = A, pre = coeff[idx], idx.  Adjoint: M = A^H, post = coeff[idx], no idx; the caller scatters the compact
+ * [O][K][I] result through idx.  I > 1 runs one lane per column (o, i): with K <= 32 the K inputs of a column stay in
+ * registers and the rows are looped over, with K > 32 up to 32 rows are accumulated in registers (R > 32 is tiled by 32 over the
+ * grid and x re-read per tile); I == 1 runs lanes along r with M and the lines
+ * staged in LDS.  Every output is written exactly once, sums in ascending k, no atomics: bit-reproducible.  No workspace.
+ * All arguments are checked before any HIP call: RIME_EINVAL for an unknown dtype or flag, K, R, O or I <= 0, a null x, M
+ * or y, out_real with a real x, idx with K_in <= 0, no idx with K_in != K, a stride <= 0, O * max(K_in, R) * I >= 2^62.
+ * ------------------------------------------------------------------------------------- */
+int rime_lm_apply(int dtype, int xcplx, int mcplx, int out_real, const void* x, const void* M, long long m_rs,
+                  long long m_ks, const int* idx, const void* pre, const void* post, long long O, int K, int K_in,
+                  int R, long long I, void* y, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Likelihood epilogue:  chi^2 = sum_i icov[i] * |pred[i] - data[i]|^2  over a complex visibility tensor
  * (N complex elements, interleaved), and its backward gpred[i] = 2 g icov[i] (pred[i] - data[i]).
  * Replaces `res = prediction - data; apply_icov(res, icov, cov_axis=None); torch.sum(...)` of
