@@ -13,15 +13,23 @@ the reference's `torch.pinv` call at :2441 does not exist in torch, so that bran
 `JonesResponse` (calibration.py:745-875: complex / amplitude / phase / delay / slope gain types, optional linear
 bases over time and frequency) -> complex gains -> `_apply_cal` on the fused kernels, with the reference-antenna
 phase convention (`rephase_to_refant`, :2490-2608) and the time index cache for minibatches (`IndexCache`, :291-413).
-The redundant-calibration degeneracy projections of BaseResponse.setup_projection (abs_amp / phs_slope) and the
-CalData export are outside the hot path and not built.
+
+Redundant calibration: `RedVisModel` (one visibility per redundant group, calibration.py:877-1053) and `VisModel` (one per
+baseline, :1056-1209) add their model to the input VisData through ops.redvis -- the group gather, the time selection of a
+minibatch and the add in one pass, and in the backward pass a segmented, fixed-order reduction in place of the atomic
+scatter-add that autograd gives the reference's index_select, so the gradient of the model is bit-identical from run to run.
+The degeneracy tools (`compute_redcal_degen`, `redcal_degen_gains`, `remove_redcal_degen`, `compute_redcal_degen_vis`,
+`redcal_degen_vis`, :2611-2915) are small dense torch arithmetic on whatever device their input is on (CPU included), and
+BaseResponse.setup_projection(abs_amp_gain=, phs_slope_gain=, wgts_gain=) projects them out of the gains through
+remove_redcal_degen.  `vis2JonesModel` / `vis2RedVisModel` (:2918-2983) build vanilla models from a VisData.
+The CalData export is outside the hot path and not built.
 """
 import copy
 
 import numpy as np
 import torch
 
-from . import ops, utils
+from . import dataset, ops, telescope_model, utils
 
 
 def _index_tensor(idx, device):
@@ -182,13 +190,25 @@ class BaseResponse:
         self._args = dict(freq_mode=freq_mode, time_mode=time_mode, param_type=param_type)
 
     def setup_projection(self, abs_amp_gain=False, phs_slope_gain=False, wgts_gain=None, refant_idx=None):
-        if abs_amp_gain or phs_slope_gain:
-            raise NotImplementedError('redundant-calibration degeneracy projections are not built')
+        """projection of the complex parameters after the response (calibration.py:150-212): abs_amp_gain / phs_slope_gain
+        divide the redundant-calibration degeneracies (antenna-averaged amplitude, phase gradient over the array; the latter
+        needs self.antpos) out of complex gains, computed with the 1-D antenna weights wgts_gain (default uniform);
+        refant_idx rephases to that antenna.  Call it after construction where the subclass sets antpos there."""
+        self._proj_abs_amp_gain, self._proj_phs_slope_gain, self._proj_wgts_gain = abs_amp_gain, phs_slope_gain, wgts_gain
+        if phs_slope_gain:
+            assert getattr(self, 'antpos', None) is not None, 'phs_slope requires antpos'
         self._proj_refant_idx = refant_idx
-        self._projection = refant_idx is not None
+        self._projection = bool(abs_amp_gain or phs_slope_gain or refant_idx is not None)
 
     def projection(self, params):
-        if self._projection:
+        if not self._projection:
+            return params
+        if self._proj_abs_amp_gain or self._proj_phs_slope_gain:
+            antpos = getattr(self, 'antpos', None)
+            ants = None if antpos is None else antpos.ants
+            params = remove_redcal_degen(params, ants, antpos, abs_amp=self._proj_abs_amp_gain,
+                                         phs_slope=self._proj_phs_slope_gain, wgts=self._proj_wgts_gain)[0]
+        if self._proj_refant_idx is not None:
             i = self._proj_refant_idx
             params = params / torch.exp(1j * torch.angle(params[:, :, i:i + 1].detach()))
         return params
@@ -406,3 +426,345 @@ class JonesModel(utils.Module, IndexCache):
             for pr in (prs or []):
                 if pr is not None:
                     pr.push(device)
+
+
+# ---------------------------------------------------------------------------------------
+# redundant calibration: visibility models (calibration.py:877-1255)
+# ---------------------------------------------------------------------------------------
+class VisModelResponse(BaseResponse):
+    """response of VisModel / RedVisModel: params -> complex (Npol, Npol, Nbls | Nred, Ntimes, Nfreqs); param_type 'com'
+    (real view, last axis [real, imag]), 'real', 'amp' or 'amp_phs' (calibration.py:1212-1255)"""
+    def __init__(self, freq_mode='channel', time_mode='channel', param_type='real', device=None, freqs=None, times=None,
+                 freq_LM=None, time_LM=None, LM=None, base0=None):
+        super().__init__(freq_mode=freq_mode, time_mode=time_mode, param_type=param_type, device=device, freq_LM=freq_LM,
+                         time_LM=time_LM, LM=LM, base0=base0, freqs=freqs, times=times)
+
+    def forward(self, params, bls=None, times=None, **kwargs):
+        return super().forward(params)
+
+    __call__ = forward
+
+
+def _sel2index(sel, N):
+    """an IndexCache selection (None, slice, list, array or tensor) along an axis of N entries as an int64 numpy array"""
+    if sel is None:
+        return np.arange(N)
+    if isinstance(sel, slice):
+        return np.arange(N)[sel]
+    if torch.is_tensor(sel):
+        sel = sel.cpu().numpy()
+    return np.asarray(sel, dtype=np.int64).reshape(-1)
+
+
+class _VisTerm(utils.Module, IndexCache):
+    """what RedVisModel and VisModel share: parameters -> response -> hooks / priors -> ops.redvis with a cached plan"""
+    def _setup(self, params, R, parameter, p0, bls, atol):
+        self.params = torch.nn.Parameter(params) if parameter else params
+        self.device = params.device
+        self.R = R if R is not None else VisModelResponse()
+        self.p0 = p0
+        IndexCache.__init__(self, times=getattr(self.R, 'times', None), bls=bls, atol=atol)
+        self.clear_cache()
+
+    def clear_cache(self):
+        """clear all caches, some come from IndexCache"""
+        self.clear_time_cache()
+        self.clear_bl_cache()
+        self.clear_vd_cache()
+
+    def clear_time_cache(self):
+        self.cache_tidx, self.cache_plan = {}, {}
+
+    def clear_bl_cache(self):
+        self.cache_bidx, self.cache_plan = {}, {}
+
+    def clear_vd_cache(self):
+        self._vd = None
+
+    def _model(self, prior_cache):
+        params = self.params if self.p0 is None else self.params + self.p0
+        vis = self.R(params)
+        if getattr(self, '_hook_registry', None) is not None and vis.requires_grad:
+            for r in self._hook_registry:
+                vis.register_hook(r)
+        self.eval_prior(prior_cache, inp_params=self.params, out_params=vis)
+        return vis
+
+    def _time_index(self, vd, Ntm):
+        """(tmap or None for the identity, cache key): the model time of every time of vd"""
+        Nt = vd.data.shape[-2]
+        sel = self.get_time_idx(vd.times) if (Ntm != Nt or self._select_equal_times) else None
+        if sel is None or (isinstance(sel, slice) and len(range(*sel.indices(Ntm))) == Ntm):
+            assert Ntm == Nt, 'model of %d times, input of %d and no time index to select with' % (Ntm, Nt)
+            return None, None
+        return _sel2index(sel, Ntm), utils.arr_hash(vd.times)
+
+    def _apply(self, vd, model, red, Nred, bkey, undo):
+        if not vd.data.is_cuda:
+            raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
+        if getattr(self, '_vd', None) is None:
+            self._vd = vd.copy(copydata=False)
+        vout = self._vd
+        if model.shape[-2] == 1 and vd.data.shape[-2] > 1:
+            model = model.expand(model.shape[:3] + (vd.data.shape[-2],) + model.shape[4:])     # one model time for all: read in place
+        Ntm = model.shape[-2]
+        tmap, tkey = self._time_index(vd, Ntm)
+        key = (bkey, tkey, Nred, Ntm, vd.data.shape[-3], vd.data.shape[-2])
+        if key not in self.cache_plan:
+            self.cache_plan[key] = ops.RedVisPlan(red(), Nred, tmap=tmap, Ntm=Ntm)
+        if model.shape[-1] == 1 and vd.data.shape[-1] > 1:
+            model = model.expand(model.shape[:4] + (vd.data.shape[-1],))
+        vout.data = ops.redvis(vd.data, model, self.cache_plan[key], undo=undo)
+        return vout
+
+    def push(self, device):
+        """push to a new device or dtype"""
+        if not isinstance(device, torch.dtype):
+            self.clear_cache()
+            self.device = device
+            if isinstance(self._times, torch.Tensor):
+                self._times = utils.push(self._times, device)
+            if isinstance(self._bls, torch.Tensor):
+                self._bls = utils.push(self._bls, device)
+        self.params = utils.push(self.params, device)
+        self.R.push(device)
+        if self.p0 is not None:
+            self.p0 = utils.push(self.p0, device)
+        for prs in (self.priors_inp_params, self.priors_out_params):
+            for pr in (prs or []):
+                if pr is not None:
+                    pr.push(device)
+
+
+class RedVisModel(_VisTerm):
+    """
+    Redundant visibility model V^d_jk = V^r + V^m_jk (calibration.py:877-1053): params (Npol, Npol, Nredvis, Ntimes | Ncoeff,
+    Nfreqs | Ncoeff[, 2]) hold one visibility per redundant group; bl2red maps a baseline -- an antenna-pair tuple, as
+    telescope_model.build_reds returns it, or a baseline number -- to its index along Nredvis.  forward(vd, undo=False,
+    prior_cache=None) adds (undo: subtracts) the model of every baseline's group to vd.data on the fused kernel of ops.redvis,
+    selecting the times of a minibatch through the time index cache; a model whose baseline axis already equals the input's is
+    added baseline by baseline.  Returns the cached output VisData with new data, as the reference does.
+    """
+    _select_equal_times = True       # the reference indexes the model's time axis whenever the response knows the times
+
+    def __init__(self, params, bl2red, R=None, parameter=True, p0=None, name=None, atol=1e-5):
+        utils.Module.__init__(self, name=name)
+        self.bl2red = bl2red
+        self._setup(params, R, parameter, p0, None, atol)
+
+    def get_bl_idx(self, bls):
+        """index tensor that expands the Nredvis axis to the baselines `bls` (baseline numbers); overloads IndexCache.get_bl_idx"""
+        h = utils.arr_hash(bls)
+        if h not in self.cache_bidx:
+            def look(bl):
+                return self.bl2red[bl] if bl in self.bl2red else self.bl2red[utils.blnum2ants(int(bl))]
+            nums = bls.cpu().numpy() if isinstance(bls, torch.Tensor) else bls
+            self.cache_bidx[h] = torch.as_tensor([look(bl) for bl in nums], device=self.device)
+        return self.cache_bidx[h]
+
+    def forward(self, vd, undo=False, prior_cache=None):
+        redvis = self._model(prior_cache)
+        Nbl, Nred = vd.data.shape[-3], redvis.shape[-3]
+        if Nred != Nbl:
+            return self._apply(vd, redvis, lambda: self.get_bl_idx(vd._blnums), Nred, utils.arr_hash(vd._blnums), undo)
+        return self._apply(vd, redvis, lambda: np.arange(Nbl), Nred, None, undo)
+
+
+class VisModel(_VisTerm):
+    """
+    Visibility model V^d_jk = V^v_jk + V^m_jk (calibration.py:1056-1209): params (Npol, Npol, Nbl, Ntimes | Ncoeff,
+    Nfreqs | Ncoeff[, 2]) ordered like the input of forward; `blnums` (the baseline numbers along Nbl) is only needed for
+    baseline minibatches.  Runs the kernel of RedVisModel with the baseline selection in place of the group map.
+    """
+    _select_equal_times = False      # ... and here only when the input holds fewer times than the model
+
+    def __init__(self, params, R=None, parameter=True, p0=None, blnums=None, name=None, atol=1e-5):
+        utils.Module.__init__(self, name=name)
+        self._setup(params, R, parameter, p0, blnums, atol)
+
+    def forward(self, vd, undo=False, prior_cache=None, **kwargs):
+        vis = self._model(prior_cache)
+        Nbl, Nmod = vd.data.shape[-3], vis.shape[-3]
+        if Nmod != Nbl:
+            assert self._bls is not None, 'a baseline minibatch needs blnums'
+            return self._apply(vd, vis, lambda: _sel2index(self.get_bl_idx(vd._blnums), Nmod), Nmod,
+                               utils.arr_hash(vd._blnums), undo)
+        return self._apply(vd, vis, lambda: np.arange(Nbl), Nmod, None, undo)
+
+
+# ---------------------------------------------------------------------------------------
+# redundant calibration: degeneracies (calibration.py:2611-2915); dense torch arithmetic on the input's device
+# ---------------------------------------------------------------------------------------
+def _lstsq_proj(A, wgts):
+    """(A^T W A)^+ A^T W with W = diag(w / sum w), W = 1 without weights; A (N, 2)"""
+    if wgts is None:
+        return torch.pinverse(A.T @ A) @ A.T
+    w = (wgts / torch.sum(wgts)).to(dtype=A.dtype, device=A.device)
+    AtW = A.T * w
+    return torch.pinverse(AtW @ A) @ AtW
+
+
+def remove_redcal_degen(gains, ants, antpos, degen=None, wgts=None, redvis=None, bls=None, abs_amp=True, phs_slope=True):
+    """
+    Remove the redundant-calibration degeneracies from gains (Npol, Npol, Nants, Ntimes, Nfreqs; 1-pol or 2-pol) and, with
+    redvis (Npol, Npol, Nbls, Ntimes, Nfreqs) and its baseline tuples bls, multiply them into the model visibilities
+    (calibration.py:2611-2662): the degenerate gains are computed from the detached gains (wgts: 1-D antenna weights), divided
+    by `degen` (a new degeneracy to insert) if given, and divided out of gains.  Returns (new_gains, new_vis | None,
+    degen_gains).  The redvis branch runs through apply_cal and therefore needs GPU tensors; the rest works on any device.
+    """
+    rd = compute_redcal_degen(gains.detach(), ants, antpos, wgts=wgts, abs_amp=abs_amp, phs_slope=phs_slope)
+    degen_gains = redcal_degen_gains(ants=ants, antpos=antpos, abs_amp=rd[0], phs_slope=rd[1])
+    if degen is not None:
+        degen_gains = degen_gains / degen
+    new_gains = gains / degen_gains
+    new_vis = None
+    if redvis is not None:
+        dg = degen_gains.to(redvis.device)
+        if dg.shape[2] == 1 and len(ants) > 1:
+            dg = dg.expand(dg.shape[:2] + (len(ants),) + dg.shape[3:])           # amplitude only: one gain for every antenna
+        new_vis = apply_cal(redvis, bls, dg, ants, undo=False)[0]
+    return new_gains, new_vis, degen_gains
+
+
+def compute_redcal_degen(gains, ants, antpos, wgts=None, abs_amp=True, phs_slope=True):
+    """
+    The degeneracy parameters of redundant calibration of antenna gains (Npol, Npol, Nant, Ntimes, Nfreqs)
+    (calibration.py:2665-2740): the overall amplitude eta = log sqrt(<|g|^2>), g_abs = exp(eta), of shape (Npol, Npol, 1,
+    Ntimes, Nfreqs), and the phase gradient Phi [rad / m] over the array, g_phs = exp(i r . Phi), of shape (Npol, Npol, 2,
+    Ntimes, Nfreqs) with (East, North) along axis 2, the (weighted) least-squares fit of the gain phases to the antenna
+    positions.  wgts: 1-D antenna weights (default uniform).  Returns (abs_amp | None, phs_slope | None).
+    """
+    abs_amp_param = phs_slope_param = None
+    if abs_amp:
+        if wgts is None:
+            abs_amp_param = torch.sum(torch.abs(gains) ** 2, dim=2, keepdim=True)
+        else:
+            w = wgts.to(gains.device)[:, None, None]
+            abs_amp_param = torch.sum(torch.abs(gains) ** 2 * w, dim=2, keepdim=True) / torch.sum(w)
+        abs_amp_param = torch.log(torch.sqrt(abs_amp_param))
+    if phs_slope:
+        gain_phs = torch.angle(gains)
+        A = antpos[[a for a in ants]][:, :2].to(dtype=gain_phs.dtype, device=gains.device)
+        phs_slope_param = torch.einsum("ab,ijblm->ijalm", _lstsq_proj(A, wgts), gain_phs)
+    return abs_amp_param, phs_slope_param
+
+
+def redcal_degen_gains(abs_amp=None, phs_slope=None, ants=None, antpos=None):
+    """
+    Degeneracy parameters (compute_redcal_degen) -> complex gains (Npol, Npol, Nant | 1, Ntimes, Nfreqs)
+    (calibration.py:2743-2785).  The antenna axis follows `ants` (default: every antenna of antpos, which is what the reference
+    always uses); antpos is needed for phs_slope.
+    """
+    device = abs_amp.device if abs_amp is not None else (phs_slope.device if phs_slope is not None else None)
+    gains = torch.ones(1, 1, 1, 1, 1, dtype=utils._cfloat(), device=device)
+    if abs_amp is not None:
+        gains = gains * torch.exp(abs_amp)
+    if phs_slope is not None:
+        A = antpos[[a for a in (ants if ants is not None else antpos)]][:, :2].to(dtype=phs_slope.dtype, device=device)
+        phs = (phs_slope.moveaxis(2, -1) @ A.T).moveaxis(-1, 2)
+        gains = gains * torch.exp(1j * phs)
+    return gains
+
+
+def _bl_design(vd, bls, antpos):
+    if isinstance(vd, dataset.VisData):
+        bls, antpos = vd.bls, vd.antpos
+    ant1, ant2 = zip(*bls)
+    return (antpos[list(ant1)] - antpos[list(ant2)])[:, :2]
+
+
+def compute_redcal_degen_vis(vd, wgts=None, abs_amp=True, phs_slope=True, bls=None, antpos=None):
+    """
+    The degeneracy parameters of a set of visibilities, a VisData or a tensor (Npol, Npol, Nbls, Ntimes, Nfreqs) with its
+    baseline tuples bls and antpos (calibration.py:2788-2850): the log of the baseline-averaged amplitude, (Npol, Npol, 1,
+    Ntimes, Nfreqs), and the phase gradient [rad / m] of the visibility phases over the baseline vectors r_1 - r_2,
+    (Npol, Npol, 2, Ntimes, Nfreqs).  wgts: 1-D baseline weights.  The weighted branch of the reference names variables that
+    do not exist and cannot run; this is the weighted least squares it plainly intends, W = diag(w / sum w).
+    """
+    data = vd.data if isinstance(vd, dataset.VisData) else vd
+    abs_amp_param = phs_slope_param = None
+    if abs_amp:
+        if wgts is None:
+            abs_amp_param = torch.sum(torch.abs(data), dim=2, keepdim=True)
+        else:
+            w = wgts.to(data.device)[:, None, None]
+            abs_amp_param = torch.sum(torch.abs(data) * w, dim=2, keepdim=True) / torch.sum(w)
+        abs_amp_param = torch.log(abs_amp_param)
+    if phs_slope:
+        vis_phs = torch.angle(data)
+        A = _bl_design(vd, bls, antpos).to(dtype=vis_phs.dtype, device=data.device)
+        phs_slope_param = torch.einsum("ab,ijblm->ijalm", _lstsq_proj(A, wgts), vis_phs)
+    return abs_amp_param, phs_slope_param
+
+
+def redcal_degen_vis(abs_amp=None, phs_slope=None, vd=None, bls=None, antpos=None):
+    """
+    Degeneracy parameters of visibilities (compute_redcal_degen_vis) -> the degenerate visibilities exp(abs_amp) *
+    exp(i (r_1 - r_2) . Phi) (calibration.py:2853-2915): a tensor, or with vd a new VisData with vd's metadata (zeros when no
+    parameter is given).  The reference decides which parameters are present by the truth value of the tensors, which only
+    single-element tensors have; here a parameter is present when it is not None.
+    """
+    data = None
+    if abs_amp is not None:
+        data = torch.exp(abs_amp)
+    if phs_slope is not None:
+        A = _bl_design(vd, bls, antpos).to(dtype=phs_slope.dtype, device=phs_slope.device)
+        phs_data = torch.exp(1j * (phs_slope.moveaxis(2, -1) @ A.T).moveaxis(-1, 2))
+        data = phs_data if data is None else data * phs_data
+    if vd is None:
+        return data
+    out = dataset.VisData()
+    out.setup_meta(telescope=vd.telescope, antpos=vd.antpos)
+    if data is None:
+        data = torch.zeros_like(vd.data)
+    out.setup_data(vd.bls, vd.times, vd.freqs, pol=vd.pol, data=data, flags=vd.flags, cov=vd.cov, cov_axis=vd.cov_axis,
+                   icov=vd.icov, history=vd.history)
+    return out
+
+
+# ---------------------------------------------------------------------------------------
+# vanilla models from a VisData (calibration.py:2918-2983)
+# ---------------------------------------------------------------------------------------
+def _param_sizes(vis, freq_mode, time_mode, freq_LM, time_LM):
+    """(Ntime_params, Nfreq_params): the VisData's axes in channel mode, the LinearModel's feature count in linear mode"""
+    Nt = vis.Ntimes if time_mode == 'channel' else int(time_LM.A.shape[1])
+    Nf = vis.Nfreqs if freq_mode == 'channel' else int(freq_LM.A.shape[1])
+    return Nt, Nf
+
+
+def vis2JonesModel(vis, param_type='com', freq_mode='channel', time_mode='channel', freqs=None, freq_LM=None, time_LM=None,
+                   refant=None, single_ant=False):
+    """
+    A vanilla JonesModel for a VisData (calibration.py:2918-2954): unit gains ('com', stored as a real view) or zero parameters,
+    one per antenna of vis.bls (2 for the slope types, 1 with single_ant).  The reference sizes the time and channel axes from
+    R.Ntime_params / R.Nfreq_params, which its response classes do not define in channel mode; here they are the VisData's
+    Ntimes / Nfreqs in channel mode and the LinearModel's number of features (A.shape[1]) in linear mode.
+    """
+    R = JonesResponse(param_type=param_type, antpos=vis.antpos, freq_mode=freq_mode, freq_LM=freq_LM, freqs=freqs,
+                      time_mode=time_mode, time_LM=time_LM)
+    ants = sorted(int(a) for a in np.unique(np.asarray(vis.bls).ravel()))
+    polmode = '1pol' if vis.Npol == 1 else '4pol'
+    Nants = 2 if 'slope' in param_type else (1 if single_ant else len(ants))
+    Nt, Nf = _param_sizes(vis, freq_mode, time_mode, freq_LM, time_LM)
+    if param_type == 'com':
+        params = utils.viewreal(torch.ones(vis.Npol, vis.Npol, Nants, Nt, Nf, dtype=utils._cfloat()))
+    else:
+        params = torch.zeros(vis.Npol, vis.Npol, Nants, Nt, Nf, dtype=utils._float())
+    return JonesModel(params, ants=ants, R=R, refant=refant, polmode=polmode, single_ant=single_ant)
+
+
+def vis2RedVisModel(vis, param_type='com', freq_mode='channel', time_mode='channel', freqs=None, freq_LM=None, time_LM=None,
+                    redtol=1.0):
+    """
+    A vanilla RedVisModel for a VisData (calibration.py:2957-2983): zero parameters, one row per redundant group of vis.bls
+    (telescope_model.build_reds with redtol).  Axis sizes as in vis2JonesModel: the VisData's in channel mode, the
+    LinearModel's number of features in linear mode (the reference reads attributes its responses do not define).
+    """
+    reds, _, bl2red = telescope_model.build_reds(vis.antpos, bls=vis.bls, redtol=redtol)[:3]
+    R = VisModelResponse(param_type=param_type, freq_mode=freq_mode, freqs=freqs, freq_LM=freq_LM, time_mode=time_mode,
+                         time_LM=time_LM)
+    Nt, Nf = _param_sizes(vis, freq_mode, time_mode, freq_LM, time_LM)
+    params = torch.zeros(vis.Npol, vis.Npol, len(reds), Nt, Nf, dtype=utils._cfloat())
+    if param_type == 'com':
+        params = utils.viewreal(params)
+    return RedVisModel(params, bl2red, R=R)

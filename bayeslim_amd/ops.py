@@ -2518,3 +2518,129 @@ def lm_apply(x, plan, dim=0, out_real=False, adjoint=False, K_in=None):
             raise IndexError('idx reaches entry %d, the indexed axis holds %d' % (plan.idx_max, K_in))
     y = _LMApply.apply(x.reshape(O, shape[d], I), plan, 'bwd' if adjoint else 'fwd', bool(out_real), K_in)
     return y.reshape(shape[:d] + (y.shape[1],) + shape[d + 1:])
+
+
+# ---------------------------------------------------------------------------------------
+# redundant / per-baseline visibility model term: out = vis +- model[red[b], tmap[t]] (csrc/redvis.hip)
+# ---------------------------------------------------------------------------------------
+def _csr(index, N):
+    """(offsets [N + 1], members) of a map index [n] -> [0, N): the members of every target in ascending position"""
+    off = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(np.bincount(index, minlength=N), out=off[1:])
+    return off.astype(np.int32), np.argsort(index, kind='stable').astype(np.int32)
+
+
+class RedVisPlan:
+    """
+    Index tables of one (baseline set, time set) of rime_redvis_fwd / rime_redvis_bwd, built with numpy on the host (no GPU
+    needed) and cached per device as int32 tensors: `red` [Nbl], the group (model row) of every baseline; `tmap` [Nt], the
+    model time of every time (None with Ntm: the identity over Ntm times); and the two CSR tables of the backward reduction,
+    goff [Nred + 1] / gmem [Nbl] (baselines of every group, ascending) and toff [Ntm + 1] / tmem [Nt] (times of every model
+    time, ascending).  A `red` entry outside [0, Nred) or a `tmap` entry outside [0, Ntm) is a ValueError.
+    """
+    def __init__(self, red, Nred, tmap=None, Ntm=None):
+        red = np.asarray(red.cpu() if torch.is_tensor(red) else red).reshape(-1)
+        if tmap is None:
+            if Ntm is None:
+                raise ValueError('RedVisPlan needs tmap or, for the identity, Ntm')
+            tmap, self.identity_t = np.arange(int(Ntm)), True
+        else:
+            tmap, self.identity_t = np.asarray(tmap.cpu() if torch.is_tensor(tmap) else tmap).reshape(-1), False
+            if Ntm is None:
+                raise ValueError('RedVisPlan needs Ntm with tmap')
+        for name, a in (('red', red), ('tmap', tmap)):
+            if a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError('%s must be a non-empty integer array' % name)
+        self.Nred, self.Ntm, self.Nbl, self.Nt = int(Nred), int(Ntm), int(red.size), int(tmap.size)
+        if self.Nred <= 0 or red.min() < 0 or red.max() >= self.Nred:
+            raise ValueError('red entry outside [0, %d)' % self.Nred)
+        if self.Ntm <= 0 or tmap.min() < 0 or tmap.max() >= self.Ntm:
+            raise ValueError('tmap entry outside [0, %d)' % self.Ntm)
+        self.red, self.tmap = red.astype(np.int32), tmap.astype(np.int32)
+        self.goff, self.gmem = _csr(red, self.Nred)
+        self.toff, self.tmem = _csr(tmap, self.Ntm)
+        self.max_members = int(np.diff(self.goff).max())
+
+    def tables(self, device):
+        """dict of the six int32 tables on `device`, cached"""
+        key = str(torch.device(device))
+        tabs = self.__dict__.setdefault('_tabs', {})
+        if key not in tabs:
+            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous()
+                         for k in ('red', 'tmap', 'goff', 'gmem', 'toff', 'tmem')}
+        return tabs[key]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tabs', None)
+        return state
+
+
+def _redvis_bwd_call(plan, gout, sign):
+    """gmodel [NP, NP, Nred, Ntm, Nf] of a contiguous gout [NP, NP, Nbl, Nt, Nf]: every element written by the kernel"""
+    NP, _, Nbl, Nt, Nf = gout.shape
+    code, _ = _real_dtype(gout)
+    T = plan.tables(gout.device)
+    gm = torch.empty((NP, NP, plan.Nred, plan.Ntm, Nf), dtype=gout.dtype, device=gout.device)
+    rc = lib.rime_redvis_bwd(code, NP, _ptr(torch.view_as_real(gout)), _ptr(T['goff']), _ptr(T['gmem']), _ptr(T['toff']),
+                             _ptr(T['tmem']), Nbl, Nt, Nf, plan.Nred, plan.Ntm, sign, _ptr(torch.view_as_real(gm)), _stream())
+    check(rc, 'rime_redvis_bwd')
+    return gm
+
+
+class _RedVis(torch.autograd.Function):
+    """out = vis + sign * model[:, :, red][:, :, :, tmap] in one pass; backward: gvis = gout itself, gmodel by the segmented
+    fixed-order reduction"""
+    @staticmethod
+    def forward(ctx, vis, model, plan, sign):
+        _require_cuda(vis, model)
+        assert model.is_complex() and model.ndim == 5, 'complex model of shape (Npol, Npol, Nred, Ntimes, Nfreqs)'
+        NP, Nf = model.shape[0], model.shape[4]
+        assert NP in (1, 2) and model.shape[1] == NP, 'Npol must be 1 or 2'
+        if tuple(model.shape[2:4]) != (plan.Nred, plan.Ntm):
+            raise ValueError('model of %d rows and %d times, the plan has %d and %d' % (tuple(model.shape[2:4]) + (plan.Nred, plan.Ntm)))
+        shape = (NP, NP, plan.Nbl, plan.Nt, Nf)
+        v = None
+        if vis is not None:
+            assert vis.is_complex(), 'complex visibilities'
+            if tuple(vis.shape) != shape:
+                raise ValueError('vis of shape %s, the plan and the model give %s' % (tuple(vis.shape), shape))
+            v = vis.detach().contiguous()
+        dtype = v.dtype if v is not None else model.dtype
+        m = model.detach().resolve_conj()
+        if m.dtype != dtype:
+            m = m.to(dtype)
+        st = m.stride()
+        if min(st) < 0 or (NP == 2 and st[0] != 2 * st[1]):
+            m = m.contiguous()
+            st = m.stride()
+        code, _ = _real_dtype(m)
+        T = plan.tables(m.device)
+        out = torch.empty(shape, dtype=dtype, device=m.device)
+        rc = lib.rime_redvis_fwd(code, NP, _ptr(torch.view_as_real(v) if v is not None else None), _ptr(torch.view_as_real(m)),
+                                 _ptr(T['red']), _ptr(None if plan.identity_t else T['tmap']), plan.Nbl, plan.Nt, Nf,
+                                 plan.Nred, plan.Ntm, st[1], st[2], st[3], st[4], sign, _ptr(torch.view_as_real(out)), _stream())
+        check(rc, 'rime_redvis_fwd')
+        ctx.plan, ctx.sign, ctx.mdtype = plan, sign, model.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        gm = None
+        if ctx.needs_input_grad[1]:
+            gm = _redvis_bwd_call(ctx.plan, gout.detach().resolve_conj().contiguous(), ctx.sign)
+            if gm.dtype != ctx.mdtype:
+                gm = gm.to(ctx.mdtype)
+        return (gout if ctx.needs_input_grad[0] else None), gm, None, None
+
+
+def redvis(vis, model, plan, undo=False):
+    """
+    out[p, q, b, t, f] = vis[p, q, b, t, f] +- model[p, q, red[b], tmap[t], f] (minus with undo) in one launch of
+    rime_redvis_fwd: vis (Npol, Npol, Nbl, Nt, Nf) complex or None (the inflated model alone), model (Npol, Npol, Nred, Ntm, Nf)
+    complex, any view with non-negative strides (an expanded axis is read in place), plan a RedVisPlan.  Differentiable once
+    with respect to both: the gradient of vis is the incoming gradient itself, that of the model the segmented reduction of
+    rime_redvis_bwd, whose summation order is fixed by the plan (bit-identical from run to run).  No CPU path.
+    """
+    return _RedVis.apply(vis, model, plan, -1 if undo else 1)

@@ -519,6 +519,34 @@ int rime_apply_cal_bwd(int dtype, int NP, int diag, const void* vis, const void*
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Redundant-visibility / per-baseline visibility model term (calibration.RedVisModel, VisModel: calibration.py:877-1209):
+ *     out[p, b, t, f] = vis[p, b, t, f] + sign * model[p, red[b], tmap[t], f]        sign = +1 | -1 (undo)
+ *   vis, out, gout   T [NP*NP][Nbl][Nt][Nf][2]   contiguous, interleaved complex; vis NULL: the inflated model alone
+ *   model            complex T, element (p, r, t', f) at complex offset p*mst_p + r*mst_r + t'*mst_t + f*mst_f
+ *                    (strides >= 0, 0 broadcasts), r < Nred, t' < Ntm
+ *   red              int32 [Nbl] (device): group of every baseline;  tmap int32 [Nt] (device): model time of every time, or
+ *                    NULL for the identity (then Ntm must be Nt)
+ *   gmodel           T [NP*NP][Nred][Ntm][Nf][2]  contiguous
+ * Forward: one pass, gather + time selection + add fused.  Backward:
+ *     gmodel[p, r, t', f] = sign * sum_{t: tmap[t] = t'} sum_{b: red[b] = r} gout[p, b, t, f]
+ * as a segmented reduction over two CSR tables (device, int32) that the caller builds on the host: goff [Nred + 1] / gmem [Nbl]
+ * (the baselines of every group) and toff [Ntm + 1] / tmem [Nt] (the times of every model time).  Lanes run along
+ * (model time, channel); the 4 waves of a block take the members w, w + 4, ... of a group in ascending list position and the
+ * partial sums are added through LDS in wave order: the summation order is a function of the tables alone (bit-reproducible).
+ * Every element of gmodel is written exactly once, 0 for a group or model time without members; no atomics, no workspace.
+ * Checked before any HIP call (RIME_EINVAL): null pointers (vis and tmap may be null), NP outside {1, 2}, an extent <= 0, an
+ * unknown dtype, sign outside {+1, -1}, a negative stride, tmap NULL with Ntm != Nt.  The tables live on the device: the
+ * caller checks them where it builds them (entries in range, offsets non-decreasing, last offset Nbl / Nt); the kernels
+ * never read outside gout / model for a table that breaks this, but the result is then undefined.
+ * ------------------------------------------------------------------------------------- */
+int rime_redvis_fwd(int dtype, int NP, const void* vis, const void* model, const int* red, const int* tmap,
+                    int Nbl, int Nt, int Nf, int Nred, int Ntm, long long mst_p, long long mst_r,
+                    long long mst_t, long long mst_f, int sign, void* out, void* stream);
+int rime_redvis_bwd(int dtype, int NP, const void* gout, const int* goff, const int* gmem, const int* toff,
+                    const int* tmem, int Nbl, int Nt, int Nf, int Nred, int Ntm, int sign, void* gmodel,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
