@@ -19,19 +19,11 @@
 // block generates the operand images once into LDS and every wave runs its MFMAs from LDS
 // fragments (details at the kernels).  Larger arrays: groups of 128 antennas, diagonal blocks (this
 // kernel) + cross blocks (8 waves, 16 tiles); multi-pol / complex psky: one launch per real plane.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <type_traits>
-#include "rime_common.h"
+#include "fringe_mfma_common.h"
 
 namespace rime {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int MF_NA = 128;                   // antennas per block (4 x 4 tiles)
-constexpr int MF_SPLIT_PIX = 16384;           // pixels per block (bounds the f32 MFMA accumulation chain)
 
 struct AntArgs {
     const double* antpos;      // [Nant, 3]
@@ -54,47 +46,6 @@ struct AntArgs {
                                // phasors are the complex conjugates and are not evaluated again (round 5, see MIRROR PAIRS below)
 };
 
-__device__ __forceinline__ uint32_t pack_rtz(float a, float b)
-{
-    auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    return __builtin_bit_cast(uint32_t, h);
-}
-
-// split (a, b) into f16 hi and lo pairs: x = hi + lo + O(2^-21 |x|)
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo)
-{
-    auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    hi = __builtin_bit_cast(uint32_t, h);
-    const float ra = a - (float)h[0];
-    const float rb = b - (float)h[1];
-    lo = pack_rtz(ra, rb);
-}
-
-// the same split for values that are not products: the residual a - hi is one mixed-precision FMA
-// (a * 1.0 - hi, the f16 half read in place) instead of v_cvt_f32_f16 + v_sub_f32 -- the compiler
-// only forms v_fma_mix when there is a multiply to fuse
-__device__ __forceinline__ void split2_plain(float a, float b, uint32_t& hi, uint32_t& lo)
-{
-    auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    hi = __builtin_bit_cast(uint32_t, h);
-    float ra, rb;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "v"(hi));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "v"(hi));
-    lo = pack_rtz(ra, rb);
-}
-
-// Keeps a float a scalar computation of its own: the compiler's SLP pass pairs independent f32 adds / multiplies / FMAs into
-// v_pk_*_f32.  Round 5: in the conjugate-pair backward -- the first kernel here whose blocks SHARE a CU, so that one block stages its
-// G planes while another block's waves stream MFMAs on the same SIMDs -- the build whose staging arithmetic the compiler had
-// vectorised (65 v_pk_add_f32: sums of two freshly loaded gradients) produced wrong planes in a fraction of the blocks that
-// were dispatched late, different from run to run; alone on the CU, or with scalar adds, the same code is exact
-// (tools/debug_pair_bwd.py, profiles/r05/pair_form.txt 3 and 8).  A hand-written v_pk_add_f32 in the same place, and the
-// compiler's add / subtract / select sequence verbatim in inline asm, are exact too: the mechanism is open.  With round 2's
-// stale packed reads of matrix-core results (rime_common.h) it is the second sighting of compiler-packed f32 arithmetic going
-// wrong beside a busy matrix pipe, so the pair kernels contain NO packed f32 instruction (the build scans for them): a fence
-// around an observed failure, not an explanation of it.
-__device__ __forceinline__ void keep_scalar(float& x) { asm("" : "+v"(x)); }
-
 // the split of two PRODUCTS (a0 b0, a1 b1) that are also read as f32 (p0, p1): the residuals a b - hi as one mixed-precision FMA
 // each on the exact product -- what the compiler makes of split2(a0 * b0, a1 * b1, ..) when the products have no other reader
 // (with one, it subtracts the rounded product: v_cvt_f32_f16 + v_sub_f32, two instructions per value)
@@ -109,27 +60,6 @@ __device__ __forceinline__ void split2_prod(float a0, float b0, float a1, float 
     asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(a1), "v"(b1), "v"(hi));
     lo = pack_rtz(ra, rb);
 }
-
-// Phase of a phasor in turns: a.s = ax sx + ay sy + az sz in float64 (antenna coordinates pre-multiplied by sign nu / c), reduced to
-// its fraction as a float32 for v_sin_f32 / v_cos_f32 (a fixed-point reduction in the low mantissa bits saves two instructions
-// per phasor for 2.2 x the phase noise: measured, not adopted -- profiles/r04/phase_magic_ab.txt, tools/lab/).
-__device__ __forceinline__ double phase3(double ax, double sx, double ay, double sy, double az, double sz)
-{
-    return ax * sx + ay * sy + az * sz;
-}
-__device__ __forceinline__ float turn_frac(double ph) { return (float)__builtin_amdgcn_fract(ph); }
-
-// FLAT (round 5, the conjugate-pair kernels): every row's z coordinate is zero (a coplanar array measured from a centre in its
-// plane -- the layouts simulations run on), so the third term of the phase is exactly zero and is not evaluated: one f64 FMA
-// less per phasor (3 % of a headline step; a licence stated by the caller, like `mirror`)
-template <bool FLAT>
-__device__ __forceinline__ double phase_of(double ax, double sx, double ay, double sy, double az, double sz)
-{
-    if constexpr (FLAT) return ax * sx + ay * sy;
-    else return phase3(ax, sx, ay, sy, az, sz);
-}
-
-__device__ __forceinline__ f16x8 as_frag(const uint4& v) { return __builtin_bit_cast(f16x8, v); }
 
 // ---------------------------------------------------------------------------------------
 // forward kernel
@@ -197,7 +127,6 @@ __device__ __forceinline__ f16x8 as_frag(const uint4& v) { return __builtin_bit_
 // C4 (127-antenna hexagon + outrigger: 7 of 8 groups) 85.4 -> 79.4 ms/step, C3 20.3 -> 18.1, C2 0.861 -> 0.825
 // (profiles/r05/mirror_pairs.txt; a timing-only build had promised twice as much for the forward -- an artefact: its
 // duplicated image rows lowered the matrix pipe's switching power, and the chip is power-limited under these kernels).
-constexpr int MF_KP = 32;                       // pixels per panel (one barrier per panel); 16 per MFMA
 constexpr int MF_NH = MF_KP / 16;               // 16-pixel K steps per panel
 constexpr int MF_ROWB = 4 * MF_KP + 16;         // [re KP x f16][im KP x f16][pad]: odd number of 16-B granules
 
@@ -287,8 +216,6 @@ __device__ __forceinline__ void static_for(F&& f)
 {
     if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
 }
-
-#define RIME_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag(a), as_frag(b), c, 0, 0, 0)
 
 // CPLX (cross blocks only): psky is complex and the block contracts it in ONE pass with asymmetric
 // weighting -- group I rows hold L = 2^7 E, group J rows hold B = (psky scale / 2^7) E (a complex product,
@@ -2464,57 +2391,13 @@ transpose_gvis_kernel(const float* __restrict__ gvis, float* __restrict__ gvt, i
     }
 }
 
-static int ant_splits(int Nt, int Nf, int Pstride)
-{
-    // at most MF_SPLIT_PIX pixels per block; more splits while the grid is below ~4 blocks per CU
-    long S = (Pstride + MF_SPLIT_PIX - 1) / MF_SPLIT_PIX;
-    const long blocks = (long)Nt * Nf;
-    const long maxS = std::max(1, Pstride / 1024);
-    while (blocks * S < 1024 && S < maxS) ++S;
-    return (int)std::max<long>(1, S);
-}
-
 } // namespace rime
 
 using namespace rime;
 
-static void ant_split_plan(int Nt, int Nf, int Pstride, int& S, int& panels_per_split)
-{
-    S = ant_splits(Nt, Nf, Pstride);
-    const int npanel = Pstride / MF_KP;
-    panels_per_split = (npanel + S - 1) / S;
-    panels_per_split = ((panels_per_split + 3) / 4) * 4;            // splits start on 64-pixel boundaries
-    S = (npanel + panels_per_split - 1) / panels_per_split;
-}
-
 extern "C" size_t rime_fringe_ant_workspace(int Nbl, int Nt, int Nf, int Pstride)
 {
-    int S, pps;
-    ant_split_plan(Nt, Nf, Pstride, S, pps);
-    return (size_t)S * Nbl * Nt * Nf * 2 * sizeof(float);
-}
-
-// RIME_FWD_PACKED=0: arrays of 33..48 antennas keep the generic two-tile forward kernel (A/B measurements; ops.py reads
-// the same variable for its count of executed MFMAs)
-static bool fwd_packed_enabled()
-{
-    static const int on = [] { const char* e = getenv("RIME_FWD_PACKED"); return e ? atoi(e) : 1; }();
-    return on != 0;
-}
-
-// RIME_BWD_SMALL=0: arrays of up to 64 antennas keep the four-tile instantiation of the backward kernel (A/B measurements)
-static bool bwd_small_enabled()
-{
-    static const int on = [] { const char* e = getenv("RIME_BWD_SMALL"); return e ? atoi(e) : 1; }();
-    return on != 0;
-}
-
-// RIME_PAIR_AP=0: the pair backward evaluates every phasor (no rotation within progressions; A/B measurements; ops.py reads the
-// same variable and keeps the plain row order)
-static bool pair_ap_enabled()
-{
-    static const int on = [] { const char* e = getenv("RIME_PAIR_AP"); return e ? atoi(e) : 1; }();
-    return on != 0;
+    return fwd_workspace_bytes(Nbl, Nt, Nf, Pstride);
 }
 
 static bool cross_shape_ok(int rows_i, int rows_j)
@@ -2535,16 +2418,36 @@ static bool ant_common_ok(int Nrows, int cross, int Nbl, int Nt, int Nf, int Pst
     return sign == 1 || sign == -1;
 }
 
+// the mirror mask names 16-row groups of the block: no negative mask, no bit at or beyond ceil(Nrows / 16)
+static bool mirror_ok(int mirror, int Nrows)
+{
+    return mirror >= 0 && !(Nrows > 0 && Nrows <= MF_NA && (mirror >> ((Nrows + 15) / 16)) != 0);
+}
+
+template <int TA>
+static void launch_fwd_diag(const AntArgs& A, dim3 grid, hipStream_t st)
+{
+    using SH = FwdShape<TA, TA, false>;
+    with_bool(A.mirror != 0, [&](auto MIR) {
+        launch_real_plane(fringe_ant_fwd_kernel<TA, true, MIR()>, fringe_ant_fwd_kernel<TA, false, MIR()>, grid, SH::NW * 64,
+                          SH::LDS, st, A);
+    });
+}
+
 template <int TI, int TJ>
-static void launch_fwd_cross(const AntArgs& A, dim3 grid, hipStream_t st, bool has_rowmin, int cplx)
+static void launch_fwd_cross(const AntArgs& A, dim3 grid, hipStream_t st, int cplx)
 {
     using SH = FwdShape<TI, TJ, true>;
-    if (cplx) {
-        hipLaunchKernelGGL((fringe_ant_fwd_cross_kernel<TI, TJ, false, true>), grid, dim3(SH::NW * 64), SH::LDS, st, A);
-        return;
-    }
-    hipLaunchKernelGGL((fringe_ant_fwd_cross_kernel<TI, TJ, true, false>), grid, dim3(SH::NW * 64), SH::LDS, st, A);
-    if (has_rowmin) hipLaunchKernelGGL((fringe_ant_fwd_cross_kernel<TI, TJ, false, false>), grid, dim3(SH::NW * 64), SH::LDS, st, A);
+    if (cplx) hipLaunchKernelGGL((fringe_ant_fwd_cross_kernel<TI, TJ, false, true>), grid, dim3(SH::NW * 64), SH::LDS, st, A);
+    else launch_real_plane(fringe_ant_fwd_cross_kernel<TI, TJ, true, false>, fringe_ant_fwd_cross_kernel<TI, TJ, false, false>, grid,
+                           SH::NW * 64, SH::LDS, st, A);
+}
+
+template <int TI>
+static void launch_fwd_self(const AntArgs& A, dim3 grid, hipStream_t st)
+{
+    using SH = FwdShape<TI, TI, true, true>;
+    hipLaunchKernelGGL((fringe_ant_fwd_self_kernel<TI>), grid, dim3(SH::NW * 64), SH::LDS, st, A);
 }
 
 extern "C" int rime_fringe_ant_fwd_block(const double* antpos, int Nrows, int cross, int mirror, const double* sdir,
@@ -2556,73 +2459,54 @@ extern "C" int rime_fringe_ant_fwd_block(const double* antpos, int Nrows, int cr
     if (!antpos || !sdir || !freqs || !psky || !scale || !pair_direct || !pair_conj) return RIME_EINVAL;
     if (!ant_common_ok(Nrows, cross, Nbl, Nt, Nf, Pstride, st_p, sign, psky_complex)) return RIME_EINVAL;
     if (psky_complex && !cross) return RIME_EUNSUPPORTED;          // diagonal blocks: one real plane per call
+    if (!mirror_ok(mirror, Nrows)) return RIME_EINVAL;
+    if (!workspace || workspace_bytes < fwd_workspace_bytes(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
     AntArgs A{};
-    A.antpos = antpos; A.sdir = sdir; A.freqs = freqs; A.psky = psky; A.scale = scale; A.rowmin = psky_complex ? nullptr : rowmin;
-    A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.vis = nullptr; A.ws = (float*)workspace;
-    A.Nant = Nrows; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
-    A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign; A.imsign = psky_complex < 0 ? -1.f : 1.f;
+    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
+    const dim3 grid = fill_forward(A, psky, scale, psky_complex ? nullptr : rowmin, workspace);
+    A.Nant = Nrows; A.imsign = psky_complex < 0 ? -1.f : 1.f;
     // mirror groups: diagonal blocks on a real plane (the packed 33..48 shape: first row tile only); anything else evaluates
     // every row (the mask is a licence, not an obligation)
-    if (mirror < 0 || (Nrows > 0 && Nrows <= MF_NA && (mirror >> ((Nrows + 15) / 16)) != 0)) return RIME_EINVAL;
     A.mirror = (!cross && !psky_complex) ? mirror : 0;
-    ant_split_plan(Nt, Nf, Pstride, A.S, A.panels_per_split);
-    if (!workspace || workspace_bytes < rime_fringe_ant_workspace(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)Nt * A.S * Nf, 1, 1);
     if (cross && cross == Nrows) {
-#define RIME_FWD_SELF(TI)                                                                                      \
-    do {                                                                                                       \
-        using SH = FwdShape<TI, TI, true, true>;                                                               \
-        hipLaunchKernelGGL((fringe_ant_fwd_self_kernel<TI>), grid, dim3(SH::NW * 64), SH::LDS, st, A);         \
-    } while (0)
-        if (Nrows == 32) RIME_FWD_SELF(1);
-        else if (Nrows == 64) RIME_FWD_SELF(2);
-        else if (Nrows == 96) RIME_FWD_SELF(3);
-        else RIME_FWD_SELF(4);
-#undef RIME_FWD_SELF
+        switch (Nrows / 32) {
+            case 1: launch_fwd_self<1>(A, grid, st); break;
+            case 2: launch_fwd_self<2>(A, grid, st); break;
+            case 3: launch_fwd_self<3>(A, grid, st); break;
+            default: launch_fwd_self<4>(A, grid, st); break;
+        }
         return check_launch();
     }
     if (cross) {
         const int ti = cross / 32, tj = (Nrows - cross) / 32;
-        if (ti == 1 && tj == 1) launch_fwd_cross<1, 1>(A, grid, st, rowmin != nullptr, psky_complex);
-        else if (ti == 1 && tj == 2) launch_fwd_cross<1, 2>(A, grid, st, rowmin != nullptr, psky_complex);
-        else if (ti == 2 && tj == 2) launch_fwd_cross<2, 2>(A, grid, st, rowmin != nullptr, psky_complex);
-        else launch_fwd_cross<4, 4>(A, grid, st, rowmin != nullptr, psky_complex);
+        if (ti == 1 && tj == 1) launch_fwd_cross<1, 1>(A, grid, st, psky_complex);
+        else if (ti == 1 && tj == 2) launch_fwd_cross<1, 2>(A, grid, st, psky_complex);
+        else if (ti == 2 && tj == 2) launch_fwd_cross<2, 2>(A, grid, st, psky_complex);
+        else launch_fwd_cross<4, 4>(A, grid, st, psky_complex);
         return check_launch();
     }
-#define RIME_FWD_PAIR(TA)                                                                                      \
-    do {                                                                                                       \
-        using SH = FwdShape<TA, TA, false>;                                                                    \
-        if (A.mirror) {                                                                                        \
-            hipLaunchKernelGGL((fringe_ant_fwd_kernel<TA, true, true>), grid, dim3(SH::NW * 64), SH::LDS, st, A);  \
-            if (rowmin) hipLaunchKernelGGL((fringe_ant_fwd_kernel<TA, false, true>), grid, dim3(SH::NW * 64), SH::LDS, st, A); \
-            break;                                                                                             \
-        }                                                                                                      \
-        hipLaunchKernelGGL((fringe_ant_fwd_kernel<TA, true>), grid, dim3(SH::NW * 64), SH::LDS, st, A);        \
-        if (rowmin) hipLaunchKernelGGL((fringe_ant_fwd_kernel<TA, false>), grid, dim3(SH::NW * 64), SH::LDS, st, A); \
-    } while (0)
+    // RIME_FWD_PACKED=0: arrays of 33..48 antennas keep the generic two-tile forward kernel (A/B measurements; ops.py reads
+    // the same variable for its count of executed MFMAs)
+    static const bool packed = env_flag("RIME_FWD_PACKED", 1);
     switch ((Nrows + 31) / 32) {
-        case 1: RIME_FWD_PAIR(1); break;
+        case 1: launch_fwd_diag<1>(A, grid, st); break;
         case 2:
-            if (Nrows <= 48 && fwd_packed_enabled()) {        // <= 16 antennas in the second row tile: packed planes
+            if (Nrows <= 48 && packed) {                      // <= 16 antennas in the second row tile: packed planes
                 A.mirror &= 3;                                // (no mirror pairs in the packed second row tile)
-                if (A.mirror) {
-                    hipLaunchKernelGGL((fringe_ant_fwd_packed_kernel<true, true>), grid, dim3(PK::NW * 64), PK::LDS, st, A);
-                    if (rowmin) hipLaunchKernelGGL((fringe_ant_fwd_packed_kernel<false, true>), grid, dim3(PK::NW * 64), PK::LDS, st, A);
-                    break;
-                }
-                hipLaunchKernelGGL((fringe_ant_fwd_packed_kernel<true>), grid, dim3(PK::NW * 64), PK::LDS, st, A);
-                if (rowmin) hipLaunchKernelGGL((fringe_ant_fwd_packed_kernel<false>), grid, dim3(PK::NW * 64), PK::LDS, st, A);
+                with_bool(A.mirror != 0, [&](auto MIR) {
+                    launch_real_plane(fringe_ant_fwd_packed_kernel<true, MIR()>, fringe_ant_fwd_packed_kernel<false, MIR()>, grid,
+                                      PK::NW * 64, PK::LDS, st, A);
+                });
                 break;
             }
-            RIME_FWD_PAIR(2);
+            launch_fwd_diag<2>(A, grid, st);
             break;
-        case 3: RIME_FWD_PAIR(3); break;
+        case 3: launch_fwd_diag<3>(A, grid, st); break;
         default:
-            RIME_FWD_PAIR(4);
+            launch_fwd_diag<4>(A, grid, st);
             break;
     }
-#undef RIME_FWD_PAIR
     return check_launch();
 }
 
@@ -2653,11 +2537,10 @@ extern "C" int rime_fringe_ant_fwd_finish(const void* workspace, size_t workspac
                                           int Nbl, int Nt, int Nf, int Pstride, void* stream)
 {
     if (!vis || Nbl <= 0 || Nt <= 0 || Nf <= 0 || Pstride <= 0 || Pstride % 64 != 0) return RIME_EINVAL;
-    if (!workspace || workspace_bytes < rime_fringe_ant_workspace(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
-    int S, pps;
-    ant_split_plan(Nt, Nf, Pstride, S, pps);
+    if (!workspace || workspace_bytes < fwd_workspace_bytes(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
     hipLaunchKernelGGL(reduce_vis_kernel, dim3((Nbl + 31) / 32, (Nf + 31) / 32, Nt), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), (const float*)workspace, vis, Nbl, Nt, Nf, S);
+                       reinterpret_cast<hipStream_t>(stream), (const float*)workspace, vis, Nbl, Nt, Nf,
+                       fwd_split_plan(Nt, Nf, Pstride).S);
     return check_launch();
 }
 
@@ -2701,36 +2584,21 @@ extern "C" int rime_fringe_ant_bwd_block(const double* antpos, int Nrows, int cr
     if (!antpos || !sdir || !freqs || !gscale || !pair_direct || !pair_conj || !gpsky) return RIME_EINVAL;
     if (!ant_common_ok(Nrows, cross, Nbl, Nt, Nf, Pstride, st_p, sign, psky_complex)) return RIME_EINVAL;
     if (!workspace || workspace_bytes < rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)) return RIME_EWORKSPACE;
+    if (!mirror_ok(mirror, Nrows)) return RIME_EINVAL;
     AntBwdArgs A{};
-    A.antpos = antpos; A.sdir = sdir; A.freqs = freqs; A.gvis = nullptr; A.gscale = gscale;
-    A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.gpsky = gpsky; A.gvt = (const float*)workspace;
-    A.Nant = Nrows; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
-    A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign; A.accumulate = accumulate ? 1 : 0;
-    A.rows_i = cross; A.imsign = psky_complex < 0 ? -1.f : 1.f;
-    if (mirror < 0 || (Nrows > 0 && Nrows <= MF_NA && (mirror >> ((Nrows + 15) / 16)) != 0)) return RIME_EINVAL;
+    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
+    const dim3 grid = fill_backward(A, gscale, gpsky, workspace, accumulate);
+    A.Nant = Nrows; A.rows_i = cross; A.imsign = psky_complex < 0 ? -1.f : 1.f;
     A.mirror = cross ? 0 : mirror;                       // diagonal blocks, real or complex psky
-    // pixel ranges are independent outputs: split freely for parallelism (>= 256 pixel tiles/block
-    // amortise the G staging; fewer when the grid would otherwise be small)
-    const int ntile = Pstride / 32;
-    int per = 256;
-    while (per > 8 && (long)Nt * Nf * ((ntile + per - 1) / per) < 1024) per /= 2;
-    A.tiles_per_split = per;
-    A.S = (ntile + per - 1) / per;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)Nt * A.S * Nf, 1, 1);
-    if (cross) {
-        if (psky_complex) hipLaunchKernelGGL(fringe_ant_bwd_cross_kernel<true>, grid, dim3(512), MX_LDS, st, A);
-        else hipLaunchKernelGGL(fringe_ant_bwd_cross_kernel<false>, grid, dim3(512), MX_LDS, st, A);
-    } else {
-        const bool small = Nrows <= 64 && bwd_small_enabled();
-        if (psky_complex) {
-            if (small) hipLaunchKernelGGL((fringe_ant_bwd_kernel<true, 2>), grid, dim3(512), MB_LDS, st, A);
-            else hipLaunchKernelGGL((fringe_ant_bwd_kernel<true, 4>), grid, dim3(512), MB_LDS, st, A);
-        } else {
-            if (small) hipLaunchKernelGGL((fringe_ant_bwd_kernel<false, 2>), grid, dim3(512), MB_LDS, st, A);
-            else hipLaunchKernelGGL((fringe_ant_bwd_kernel<false, 4>), grid, dim3(512), MB_LDS, st, A);
-        }
-    }
+    // RIME_BWD_SMALL=0: arrays of up to 64 antennas keep the four-tile instantiation of the backward kernel (A/B measurements)
+    static const bool small_on = env_flag("RIME_BWD_SMALL", 1);
+    with_bool(psky_complex != 0, [&](auto CPLX) {
+        if (cross) hipLaunchKernelGGL(fringe_ant_bwd_cross_kernel<CPLX()>, grid, dim3(512), MX_LDS, st, A);
+        else with_bool(Nrows <= 64 && small_on, [&](auto SMALL) {
+            hipLaunchKernelGGL((fringe_ant_bwd_kernel<CPLX(), SMALL() ? 2 : 4>), grid, dim3(512), MB_LDS, st, A);
+        });
+    });
     return check_launch();
 }
 
@@ -2760,39 +2628,27 @@ extern "C" int rime_fringe_pair_fwd_block(const double* antpos, int Nrows, const
 {
     if (!antpos || !sdir || !freqs || !psky || !scale || !pair_direct || !pair_conj) return RIME_EINVAL;
     if (!pair_common_ok(Nrows, Nbl, Nt, Nf, Pstride, st_p, sign)) return RIME_EINVAL;
+    if (!workspace || workspace_bytes < fwd_workspace_bytes(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
     PairArgs A{};
-    A.antpos = antpos; A.sdir = sdir; A.freqs = freqs; A.psky = psky; A.scale = scale; A.rowmin = rowmin;
-    A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.vis = nullptr; A.ws = (float*)workspace;
-    A.Nant = Nrows; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
-    A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign; A.imsign = 1.f; A.mirror = 0;
-    A.centre = centre;
-    ant_split_plan(Nt, Nf, Pstride, A.S, A.panels_per_split);
-    if (!workspace || workspace_bytes < rime_fringe_ant_workspace(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
+    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
+    const dim3 grid = fill_forward(A, psky, scale, rowmin, workspace);
+    A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)Nt * A.S * Nf, 1, 1);
-    if (Nrows <= 32 && !centre) {                        // one row tile
-        // LDS: two image buffers (18.5 KB) during the loop, then the epilogue's transposition tiles + two partial tiles per wave pair
-        constexpr size_t lds1 = 4 * 33 * 32 * 4 + 2 * 2 * 16 * 64 * 4;
-        static_assert(lds1 >= 2 * (size_t)FwdShape<1, 1, false>::BUF, "the image buffers fit into the epilogue's scratch");
-        if (flat) {
-            hipLaunchKernelGGL((fringe_pair_fwd1_kernel<true, true>), grid, dim3(256), lds1, st, A);
-            if (rowmin) hipLaunchKernelGGL((fringe_pair_fwd1_kernel<false, true>), grid, dim3(256), lds1, st, A);
-        } else {
-            hipLaunchKernelGGL((fringe_pair_fwd1_kernel<true, false>), grid, dim3(256), lds1, st, A);
-            if (rowmin) hipLaunchKernelGGL((fringe_pair_fwd1_kernel<false, false>), grid, dim3(256), lds1, st, A);
+    with_bool(flat != 0, [&](auto FLAT) {
+        if (Nrows <= 32 && !centre) {                    // one row tile
+            // LDS: two image buffers (18.5 KB) during the loop, then the epilogue's transposition tiles + two partial tiles per wave pair
+            constexpr size_t lds1 = 4 * 33 * 32 * 4 + 2 * 2 * 16 * 64 * 4;
+            static_assert(lds1 >= 2 * (size_t)FwdShape<1, 1, false>::BUF, "the image buffers fit into the epilogue's scratch");
+            launch_real_plane(fringe_pair_fwd1_kernel<true, FLAT()>, fringe_pair_fwd1_kernel<false, FLAT()>, grid, 256, lds1, st, A);
+            return;
         }
-        return check_launch();
-    }
-    using SH = FwdShape<2, 2, false>;
-    static_assert(SH::LDS >= 4 * 33 * 32 * 4 + 2 * 64 * 2 * 4, "epilogue scratch: transposition tiles + the hub's column sums");
-#define RIME_PAIR_FWD(CEN_, FLAT_)                                                                                       \
-    do {                                                                                                                 \
-        hipLaunchKernelGGL((fringe_pair_fwd_kernel<true, CEN_, FLAT_>), grid, dim3(256), SH::LDS, st, A);                \
-        if (rowmin) hipLaunchKernelGGL((fringe_pair_fwd_kernel<false, CEN_, FLAT_>), grid, dim3(256), SH::LDS, st, A);   \
-    } while (0)
-    if (centre) { if (flat) RIME_PAIR_FWD(true, true); else RIME_PAIR_FWD(true, false); }
-    else { if (flat) RIME_PAIR_FWD(false, true); else RIME_PAIR_FWD(false, false); }
-#undef RIME_PAIR_FWD
+        using SH = FwdShape<2, 2, false>;
+        static_assert(SH::LDS >= 4 * 33 * 32 * 4 + 2 * 64 * 2 * 4, "epilogue scratch: transposition tiles + the hub's column sums");
+        with_bool(centre != nullptr, [&](auto CEN) {
+            launch_real_plane(fringe_pair_fwd_kernel<true, CEN(), FLAT()>, fringe_pair_fwd_kernel<false, CEN(), FLAT()>, grid, 256,
+                              SH::LDS, st, A);
+        });
+    });
     return check_launch();
 }
 
@@ -2806,27 +2662,20 @@ extern "C" int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const
     if (!pair_common_ok(Nrows, Nbl, Nt, Nf, Pstride, st_p, sign)) return RIME_EINVAL;
     if (!workspace || workspace_bytes < rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)) return RIME_EWORKSPACE;
     PairBwdArgs A{};
-    A.antpos = antpos; A.sdir = sdir; A.freqs = freqs; A.gvis = nullptr; A.gscale = gscale;
-    A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.gpsky = gpsky; A.gvt = (const float*)workspace;
-    A.Nant = Nrows; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
-    A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign; A.accumulate = accumulate ? 1 : 0;
-    A.rows_i = 0; A.imsign = 1.f; A.mirror = 0; A.centre = centre; A.ap = pair_ap_enabled() ? 1 : 0;
-    const int ntile = Pstride / 32;
-    int per = 256;
-    while (per > 8 && (long)Nt * Nf * ((ntile + per - 1) / per) < 1024) per /= 2;
-    A.tiles_per_split = per;
-    A.S = (ntile + per - 1) / per;
+    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
+    const dim3 grid = fill_backward(A, gscale, gpsky, workspace, accumulate);
+    A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
+    // RIME_PAIR_AP=0: the pair backward evaluates every phasor (no rotation within progressions; A/B measurements; ops.py reads the
+    // same variable and keeps the plain row order)
+    static const bool ap = env_flag("RIME_PAIR_AP", 1);
+    A.ap = ap ? 1 : 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)Nt * A.S * Nf, 1, 1);
-    if (Nrows <= 32 && !centre) {                        // one row tile
-        if (flat) hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, true, 1>), grid, dim3(PB_THREADS), pb_lds<1>(), st, A);
-        else hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, false, 1>), grid, dim3(PB_THREADS), pb_lds<1>(), st, A);
-    } else if (centre) {
-        if (flat) hipLaunchKernelGGL((fringe_pair_bwd_kernel<true, true, 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, A);
-        else hipLaunchKernelGGL((fringe_pair_bwd_kernel<true, false, 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, A);
-    } else {
-        if (flat) hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, true, 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, A);
-        else hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, false, 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, A);
-    }
+    with_bool(flat != 0, [&](auto FLAT) {
+        if (Nrows <= 32 && !centre)                      // one row tile
+            hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, FLAT(), 1>), grid, dim3(PB_THREADS), pb_lds<1>(), st, A);
+        else with_bool(centre != nullptr, [&](auto CEN) {
+            hipLaunchKernelGGL((fringe_pair_bwd_kernel<CEN(), FLAT(), 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, A);
+        });
+    });
     return check_launch();
 }

@@ -20,18 +20,14 @@
 //
 // The operand formats, the f16 hi / lo split, the f64 phase with hardware sine / cosine in turns, the LDS image layout, the
 // pixel-split slabs of the forward (summed by rime_fringe_ant_fwd_finish) and the transposed gradient of the backward (written by
-// rime_fringe_ant_bwd_prepare) are those of fringe_mfma.hip; the small device helpers are restated here so that this file can be
-// built, scanned and changed on its own.  Blocks of these kernels share a CU, so -- like the pair kernels -- they hold no packed
-// f32 instruction (keep_scalar in fringe_mfma.hip; the build scans for them).  The kernels' names carry `xpair`.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include "rime_common.h"
+// rime_fringe_ant_bwd_prepare) are those of fringe_mfma.hip; the small device helpers and the host layer between the C ABI and the
+// launches are shared with it (fringe_mfma_common.h).  This file stays a translation unit of its own: built and scanned on its
+// own.  Blocks of these kernels share a CU, so -- like the pair kernels -- they hold no packed f32 instruction (keep_scalar in
+// fringe_mfma_common.h; the build scans for them).  The kernels' names carry `xpair`.
+#include "fringe_mfma_common.h"
 
 namespace rime {
 namespace xp {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int NA = 128;                      // rows / columns of the slot tables (virtual block: 64 firsts + 64 mirrors a side)
 constexpr int XR = 64;                       // rows of one group
@@ -42,40 +38,7 @@ constexpr int IMG = 2 * XR * ROWB;           // one image (hi or lo): rows 0..63
 constexpr int BUF = 2 * IMG + 64;            // hi + lo + sign dwords of the panel
 constexpr size_t FWD_LDS = 2 * (size_t)BUF;
 
-__device__ __forceinline__ uint32_t pack_rtz(float a, float b)
-{
-    auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    return __builtin_bit_cast(uint32_t, h);
-}
-// split (a, b) into f16 hi and lo pairs: x = hi + lo + O(2^-21 |x|)
-__device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo)
-{
-    auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    hi = __builtin_bit_cast(uint32_t, h);
-    const float ra = a - (float)h[0];
-    const float rb = b - (float)h[1];
-    lo = pack_rtz(ra, rb);
-}
-__device__ __forceinline__ void split2_plain(float a, float b, uint32_t& hi, uint32_t& lo)
-{
-    auto h = __builtin_amdgcn_cvt_pkrtz(a, b);
-    hi = __builtin_bit_cast(uint32_t, h);
-    float ra, rb;
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "v"(hi));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "v"(hi));
-    lo = pack_rtz(ra, rb);
-}
-__device__ __forceinline__ void keep_scalar(float& x) { asm("" : "+v"(x)); }
-template <bool FLAT>
-__device__ __forceinline__ double phase_of(double ax, double sx, double ay, double sy, double az, double sz)
-{
-    if constexpr (FLAT) return ax * sx + ay * sy;
-    else return ax * sx + ay * sy + az * sz;
-}
-__device__ __forceinline__ float turn_frac(double ph) { return (float)__builtin_amdgcn_fract(ph); }
-__device__ __forceinline__ f16x8 as_frag(const uint4& v) { return __builtin_bit_cast(f16x8, v); }
-
-#define RIME_XMFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag(a), as_frag(b), c, 0, 0, 0)
+static_assert(KP == MF_KP, "the forward split plan (fringe_mfma_common.h) counts panels of MF_KP pixels");
 
 struct FwdArgs {
     const double* antpos;      // [rows_i + rows_j, 3] from the centre of symmetry: group I, then group J
@@ -218,18 +181,18 @@ __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* 
             const uint4 Lrl = sgn(frag(ti, 1, 0, ks), sg), Lil = sgn(frag(ti, 1, 1, ks), sg);
             const uint4 Brh = frag(2 + tj, 0, 0, ks), Bih = frag(2 + tj, 0, 1, ks);
             const uint4 Brl = frag(2 + tj, 1, 0, ks), Bil = frag(2 + tj, 1, 1, ks);
-            acc[0] = RIME_XMFMA(Lrh, Brh, acc[0]);
-            acc[1] = RIME_XMFMA(Lih, Bih, acc[1]);
-            acc[2] = RIME_XMFMA(Lrh, Bih, acc[2]);
-            acc[3] = RIME_XMFMA(Lih, Brh, acc[3]);
-            acc[0] = RIME_XMFMA(Lrh, Brl, acc[0]);
-            acc[1] = RIME_XMFMA(Lih, Bil, acc[1]);
-            acc[2] = RIME_XMFMA(Lrh, Bil, acc[2]);
-            acc[3] = RIME_XMFMA(Lih, Brl, acc[3]);
-            acc[0] = RIME_XMFMA(Lrl, Brh, acc[0]);
-            acc[1] = RIME_XMFMA(Lil, Bih, acc[1]);
-            acc[2] = RIME_XMFMA(Lrl, Bih, acc[2]);
-            acc[3] = RIME_XMFMA(Lil, Brh, acc[3]);
+            acc[0] = RIME_MFMA(Lrh, Brh, acc[0]);
+            acc[1] = RIME_MFMA(Lih, Bih, acc[1]);
+            acc[2] = RIME_MFMA(Lrh, Bih, acc[2]);
+            acc[3] = RIME_MFMA(Lih, Brh, acc[3]);
+            acc[0] = RIME_MFMA(Lrh, Brl, acc[0]);
+            acc[1] = RIME_MFMA(Lih, Bil, acc[1]);
+            acc[2] = RIME_MFMA(Lrh, Bil, acc[2]);
+            acc[3] = RIME_MFMA(Lih, Brl, acc[3]);
+            acc[0] = RIME_MFMA(Lrl, Brh, acc[0]);
+            acc[1] = RIME_MFMA(Lil, Bih, acc[1]);
+            acc[2] = RIME_MFMA(Lrl, Bih, acc[2]);
+            acc[3] = RIME_MFMA(Lil, Brh, acc[3]);
         }
     };
 
@@ -452,18 +415,18 @@ fringe_xpair_bwd_kernel(BwdArgs A)
                     const uint4 Ics_l = *reinterpret_cast<const uint4*>(g_img + gl0 + 5 * XB_PLANE + tk);
                     const uint4 Isc_l = *reinterpret_cast<const uint4*>(g_img + gl0 + 6 * XB_PLANE + tk);
                     const uint4 Iss_l = *reinterpret_cast<const uint4*>(g_img + gl0 + 7 * XB_PLANE + tk);
-                    accC[ti] = RIME_XMFMA(Icc_h, Erh, accC[ti]);
-                    accS[ti] = RIME_XMFMA(Isc_h, Erh, accS[ti]);
-                    accC[ti] = RIME_XMFMA(Ics_h, Eih, accC[ti]);
-                    accS[ti] = RIME_XMFMA(Iss_h, Eih, accS[ti]);
-                    accC[ti] = RIME_XMFMA(Icc_h, Erl, accC[ti]);
-                    accS[ti] = RIME_XMFMA(Isc_h, Erl, accS[ti]);
-                    accC[ti] = RIME_XMFMA(Ics_h, Eil, accC[ti]);
-                    accS[ti] = RIME_XMFMA(Iss_h, Eil, accS[ti]);
-                    accC[ti] = RIME_XMFMA(Icc_l, Erh, accC[ti]);
-                    accS[ti] = RIME_XMFMA(Isc_l, Erh, accS[ti]);
-                    accC[ti] = RIME_XMFMA(Ics_l, Eih, accC[ti]);
-                    accS[ti] = RIME_XMFMA(Iss_l, Eih, accS[ti]);
+                    accC[ti] = RIME_MFMA(Icc_h, Erh, accC[ti]);
+                    accS[ti] = RIME_MFMA(Isc_h, Erh, accS[ti]);
+                    accC[ti] = RIME_MFMA(Ics_h, Eih, accC[ti]);
+                    accS[ti] = RIME_MFMA(Iss_h, Eih, accS[ti]);
+                    accC[ti] = RIME_MFMA(Icc_h, Erl, accC[ti]);
+                    accS[ti] = RIME_MFMA(Isc_h, Erl, accS[ti]);
+                    accC[ti] = RIME_MFMA(Ics_h, Eil, accC[ti]);
+                    accS[ti] = RIME_MFMA(Iss_h, Eil, accS[ti]);
+                    accC[ti] = RIME_MFMA(Icc_l, Erh, accC[ti]);
+                    accS[ti] = RIME_MFMA(Isc_l, Erh, accS[ti]);
+                    accC[ti] = RIME_MFMA(Ics_l, Eih, accC[ti]);
+                    accS[ti] = RIME_MFMA(Iss_l, Eih, accS[ti]);
                 }
             }
         }
@@ -494,22 +457,6 @@ fringe_xpair_bwd_kernel(BwdArgs A)
     }
 }
 
-// the pixel-split plan of the forward slabs: the one of fringe_mfma.hip (ant_split_plan), whose workspace size the entry point
-// compares with the result
-static void split_plan(int Nt, int Nf, int Pstride, int& S, int& panels_per_split)
-{
-    constexpr int SPLIT_PIX = 16384;
-    long s = (Pstride + SPLIT_PIX - 1) / SPLIT_PIX;
-    const long blocks = (long)Nt * Nf;
-    const long maxS = std::max(1, Pstride / 1024);
-    while (blocks * s < 1024 && s < maxS) ++s;
-    S = (int)std::max<long>(1, s);
-    const int npanel = Pstride / KP;
-    panels_per_split = (npanel + S - 1) / S;
-    panels_per_split = ((panels_per_split + 3) / 4) * 4;
-    S = (npanel + panels_per_split - 1) / panels_per_split;
-}
-
 static bool common_ok(int rows_i, int rows_j, int Nbl, int Nt, int Nf, int Pstride, long long st_p, int sign)
 {
     if (rows_i <= 0 || rows_i > XR || rows_j <= 0 || rows_j > XR) return false;
@@ -531,24 +478,16 @@ extern "C" int rime_fringe_pair_cross_fwd_block(const double* antpos, int rows_i
 {
     if (!antpos || !sdir || !freqs || !psky || !scale || !pair_direct || !pair_conj) return RIME_EINVAL;
     if (!xp::common_ok(rows_i, rows_j, Nbl, Nt, Nf, Pstride, st_p, sign)) return RIME_EINVAL;
+    if (!workspace || workspace_bytes < fwd_workspace_bytes(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
     xp::FwdArgs A{};
-    A.antpos = antpos; A.sdir = sdir; A.freqs = freqs; A.psky = psky; A.scale = scale; A.rowmin = rowmin;
-    A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.ws = (float*)workspace;
-    A.rows_i = rows_i; A.rows_j = rows_j; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
-    A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign;
-    xp::split_plan(Nt, Nf, Pstride, A.S, A.panels_per_split);
-    const size_t need = rime_fringe_ant_workspace(Nbl, Nt, Nf, Pstride);
-    if (need != (size_t)A.S * Nbl * Nt * Nf * 2 * sizeof(float)) return RIME_EUNSUPPORTED;      // the two plans must be one
-    if (!workspace || workspace_bytes < need) return RIME_EWORKSPACE;
+    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
+    const dim3 grid = fill_forward(A, psky, scale, rowmin, workspace);
+    A.rows_i = rows_i; A.rows_j = rows_j;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)Nt * A.S * Nf, 1, 1);
-    if (flat) {
-        hipLaunchKernelGGL((xp::fringe_xpair_fwd_kernel<true, true>), grid, dim3(256), xp::FWD_LDS, st, A);
-        if (rowmin) hipLaunchKernelGGL((xp::fringe_xpair_fwd_kernel<false, true>), grid, dim3(256), xp::FWD_LDS, st, A);
-    } else {
-        hipLaunchKernelGGL((xp::fringe_xpair_fwd_kernel<true, false>), grid, dim3(256), xp::FWD_LDS, st, A);
-        if (rowmin) hipLaunchKernelGGL((xp::fringe_xpair_fwd_kernel<false, false>), grid, dim3(256), xp::FWD_LDS, st, A);
-    }
+    with_bool(flat != 0, [&](auto FLAT) {
+        launch_real_plane(xp::fringe_xpair_fwd_kernel<true, FLAT()>, xp::fringe_xpair_fwd_kernel<false, FLAT()>, grid, 256,
+                          xp::FWD_LDS, st, A);
+    });
     return check_launch();
 }
 
@@ -562,18 +501,12 @@ extern "C" int rime_fringe_pair_cross_bwd_block(const double* antpos, int rows_i
     if (!xp::common_ok(rows_i, rows_j, Nbl, Nt, Nf, Pstride, st_p, sign)) return RIME_EINVAL;
     if (!workspace || workspace_bytes < rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)) return RIME_EWORKSPACE;
     xp::BwdArgs A{};
-    A.antpos = antpos; A.sdir = sdir; A.freqs = freqs; A.gscale = gscale;
-    A.pair_direct = pair_direct; A.pair_conj = pair_conj; A.gpsky = gpsky; A.gvt = (const float*)workspace;
-    A.rows_i = rows_i; A.rows_j = rows_j; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Pstride = Pstride;
-    A.st_t = st_t; A.st_f = st_f; A.st_p = st_p; A.sign = (double)sign; A.accumulate = accumulate ? 1 : 0;
-    const int ntile = Pstride / 32;
-    int per = 256;
-    while (per > 8 && (long)Nt * Nf * ((ntile + per - 1) / per) < 1024) per /= 2;
-    A.tiles_per_split = per;
-    A.S = (ntile + per - 1) / per;
+    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
+    const dim3 grid = fill_backward(A, gscale, gpsky, workspace, accumulate);
+    A.rows_i = rows_i; A.rows_j = rows_j;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)Nt * A.S * Nf, 1, 1);
-    if (flat) hipLaunchKernelGGL((xp::fringe_xpair_bwd_kernel<true>), grid, dim3(xp::XB_THREADS), xp::XB_LDS, st, A);
-    else hipLaunchKernelGGL((xp::fringe_xpair_bwd_kernel<false>), grid, dim3(xp::XB_THREADS), xp::XB_LDS, st, A);
+    with_bool(flat != 0, [&](auto FLAT) {
+        hipLaunchKernelGGL(xp::fringe_xpair_bwd_kernel<FLAT()>, grid, dim3(xp::XB_THREADS), xp::XB_LDS, st, A);
+    });
     return check_launch();
 }

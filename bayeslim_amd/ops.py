@@ -720,6 +720,30 @@ def _pow2_scale(amax):
     return torch.where(amax > 0, torch.exp2(e), torch.ones_like(amax))
 
 
+def _block_launch(blk, backward, cflag):
+    """
+    how one planned block is launched: (entry point, its leading arguments, its slot tables, the complex-pass flag where the
+    entry point takes one, MFMAs per 16 pixels).  Kinds: self (forward only: a diagonal block in one complex pass, as the
+    cross block of its rows with themselves), xpair and pair (one real plane per call), plain (cflag != 0: one complex pass).
+    """
+    d = 'bwd' if backward else 'fwd'
+    rows, flag, mf = blk, (), blk['mf_bwd_real'] if backward else blk['mf_fwd']
+    if not backward and cflag != 0 and blk['cross'] == 0:
+        n = int(blk['self_pos'].shape[0])
+        name, lead, flag, mf = 'rime_fringe_ant_fwd_block', (_ptr(blk['self_pos']), n, n, 0), (cflag,), blk['mf_self']
+    elif blk.get('xpair'):
+        name, lead = 'rime_fringe_pair_cross_%s_block' % d, (_ptr(blk['pos']), blk['rows_i'], blk['rows_j'], blk['flat'])
+    elif blk.get('pair'):
+        if backward:
+            rows = blk.get('bwd') or blk                         # the backward's own row order, where one exists
+        name, lead = 'rime_fringe_pair_%s_block' % d, (_ptr(rows['pos']), blk['nrows'], _ptr(rows['centre']), blk['flat'])
+    else:
+        name, lead, flag = 'rime_fringe_ant_%s_block' % d, (_ptr(blk['pos']), blk['nrows'], blk['cross'], blk['mirror']), (cflag,)
+        if backward and cflag != 0:
+            mf = blk['mf_bwd']
+    return name, lead, (_ptr(rows['direct']), _ptr(rows['conj'])), flag, mf
+
+
 def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
     """
     antenna-factored kernels: one launch per block of the pair matrix (ops._antenna_blocks), each on
@@ -777,34 +801,11 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
 
         def launch(blk, pp, c, cflag):
             mp = blk['mp']
-            src = ctypes.c_void_p(inp.data_ptr() + 4 * (mp * st_mp + pp * st_pp + c))
-            if cflag != 0 and blk['cross'] == 0:             # diagonal block, complex single pass: self block
-                n = int(blk['self_pos'].shape[0])
-                rc = lib.rime_fringe_ant_fwd_block(_ptr(blk['self_pos']), n, n, 0, *geo, src, _ptr(scale[mp, pp]),
-                                                   _ptr(rowmin[c][mp, pp]), _ptr(blk['direct']), _ptr(blk['conj']),
-                                                   *shape, cflag, _ptr(ws), ws.numel(), _stream())
-                check(rc, 'rime_fringe_ant_fwd_block')
-                return blk['mf_self']
-            if blk.get('xpair'):                             # pair cross block: one real plane per call
-                rc = lib.rime_fringe_pair_cross_fwd_block(_ptr(blk['pos']), blk['rows_i'], blk['rows_j'], blk['flat'], *geo, src,
-                                                          _ptr(scale[mp, pp]), _ptr(rowmin[c][mp, pp]),
-                                                          _ptr(blk['direct']), _ptr(blk['conj']),
-                                                          *shape, _ptr(ws), ws.numel(), _stream())
-                check(rc, 'rime_fringe_pair_cross_fwd_block')
-                return blk['mf_fwd']
-            if blk.get('pair'):                              # conjugate-pair form: one real plane per call (c picks it)
-                rc = lib.rime_fringe_pair_fwd_block(_ptr(blk['pos']), blk['nrows'], _ptr(blk['centre']), blk['flat'], *geo, src,
-                                                    _ptr(scale[mp, pp]), _ptr(rowmin[c][mp, pp]),
-                                                    _ptr(blk['direct']), _ptr(blk['conj']),
-                                                    *shape, _ptr(ws), ws.numel(), _stream())
-                check(rc, 'rime_fringe_pair_fwd_block')
-                return blk['mf_fwd']
-            rc = lib.rime_fringe_ant_fwd_block(_ptr(blk['pos']), blk['nrows'], blk['cross'], blk['mirror'], *geo, src,
-                                               _ptr(scale[mp, pp]), _ptr(rowmin[c][mp, pp]),
-                                               _ptr(blk['direct']), _ptr(blk['conj']),
-                                               *shape, cflag, _ptr(ws), ws.numel(), _stream())
-            check(rc, 'rime_fringe_ant_fwd_block')
-            return blk['mf_fwd']
+            src = ctypes.c_void_p(inp.data_ptr() + 4 * (mp * st_mp + pp * st_pp + c))     # pair forms: c picks the real plane
+            name, lead, tables, flag, mf = _block_launch(blk, False, cflag)
+            check(getattr(lib, name)(*lead, *geo, src, _ptr(scale[mp, pp]), _ptr(rowmin[c][mp, pp]), *tables, *shape, *flag,
+                                     _ptr(ws), ws.numel(), _stream()), name)
+            return mf
 
         for pp in range(Npp):
             for blk in blocks:
@@ -850,27 +851,10 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
                     assert all((pl in written) == bool(acc) for pl in planes)
                     written.update(planes)
                     dst = ctypes.c_void_p(out.data_ptr() + 4 * (mp * st_mp + pp * st_pp + (0 if single else c)))
-                    if blk.get('xpair'):
-                        rc = lib.rime_fringe_pair_cross_bwd_block(_ptr(blk['pos']), blk['rows_i'], blk['rows_j'], blk['flat'], *geo,
-                                                                  _ptr(scale_pp), _ptr(blk['direct']), _ptr(blk['conj']),
-                                                                  *shape, acc, dst, _ptr(ws), ws.numel(), _stream())
-                        check(rc, 'rime_fringe_pair_cross_bwd_block')
-                        flops += blk['mf_bwd_real']
-                        continue
-                    if blk.get('pair'):
-                        rows = blk.get('bwd') or blk             # the backward's own row order, where one exists
-                        rc = lib.rime_fringe_pair_bwd_block(_ptr(rows['pos']), blk['nrows'], _ptr(rows['centre']), blk['flat'], *geo,
-                                                            _ptr(scale_pp), _ptr(rows['direct']), _ptr(rows['conj']),
-                                                            *shape, acc, dst, _ptr(ws), ws.numel(), _stream())
-                        check(rc, 'rime_fringe_pair_bwd_block')
-                        flops += blk['mf_bwd_real']
-                        continue
-                    rc = lib.rime_fringe_ant_bwd_block(_ptr(blk['pos']), blk['nrows'], blk['cross'], blk['mirror'], *geo,
-                                                       _ptr(scale_pp), _ptr(blk['direct']), _ptr(blk['conj']),
-                                                       *shape, blk['cpass'] if single else 0, acc, dst,
-                                                       _ptr(ws), ws.numel(), _stream())
-                    check(rc, 'rime_fringe_ant_bwd_block')
-                    flops += blk['mf_bwd'] if single else blk['mf_bwd_real']
+                    name, lead, tables, flag, mf = _block_launch(blk, True, blk['cpass'] if single else 0)
+                    check(getattr(lib, name)(*lead, *geo, _ptr(scale_pp), *tables, *shape, *flag, acc, dst,
+                                             _ptr(ws), ws.numel(), _stream()), name)
+                    flops += mf
             assert len(written) == Nmp * m, 'every psky plane must be written by a block'
     return flops * per16
 

@@ -13,7 +13,7 @@ for ops.lib and records the block launches.
 
 `dispatch` restates the C dispatch of rime_fringe_ant_{fwd,bwd}_block and rime_fringe_pair_{fwd,bwd}_block: the rows one
 accepted call launches, with the default switches of the library (RIME_FWD_PACKED, RIME_BWD_SMALL on).  `grid` restates
-the launch grid of the same calls (ant_split_plan for the forward, the `per` loop for the backward).
+the launch grid of the same calls (fwd_split_plan and bwd_split_plan of csrc/fringe_mfma_common.h).
 
 Plain data and host arithmetic only: the CPU tests import it as well as the GPU tests.
 """
@@ -26,7 +26,7 @@ import numpy as np
 FWD, BWD = 'rime_fringe_ant_fwd_block', 'rime_fringe_ant_bwd_block'
 PFWD, PBWD = 'rime_fringe_pair_fwd_block', 'rime_fringe_pair_bwd_block'
 
-MF_SPLIT_PIX, MF_KP = 16384, 32           # fringe_mfma.hip: pixels per forward block at most, pixels per panel
+MF_SPLIT_PIX, MF_KP = 16384, 32           # fringe_mfma_common.h: pixels per forward block at most, pixels per panel
 
 # Argument names of the selecting arguments (include/rime_hip.h): Nrows, cross, mirror, psky_complex, accumulate, and
 # rowmin (a non-null row-minimum pointer: real planes) for the forward; centre (a hub slot table) and flat for the pair form.
@@ -225,7 +225,7 @@ def dispatch(entry, a):
 
 
 def fwd_splits(Nt, Nf, Pstride):
-    """S of the forward launches (ant_splits + ant_split_plan): grid = Nt S Nf"""
+    """S of the forward launches (fwd_split_plan): grid = Nt S Nf"""
     S = (Pstride + MF_SPLIT_PIX - 1) // MF_SPLIT_PIX
     maxS = max(1, Pstride // 1024)
     while Nt * Nf * S < 1024 and S < maxS:
@@ -245,7 +245,7 @@ def fwd_split_pixels(Nt, Nf, Pstride):
 
 
 def bwd_splits(Nt, Nf, Pstride):
-    """(S, pixels per split) of the backward launches (the `per` loop of rime_fringe_ant_bwd_block / _pair_bwd_block)"""
+    """(S, pixels per split) of the backward launches (bwd_split_plan)"""
     ntile = Pstride // 32
     per = 256
     while per > 8 and Nt * Nf * ((ntile + per - 1) // per) < 1024:

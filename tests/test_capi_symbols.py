@@ -94,7 +94,7 @@ def test_bad_arguments_are_rejected_without_launching():
 
 def test_build_scan_refuses_packed_f32_in_the_pair_kernels(tmp_path):
     """round 5: kernels whose blocks share a CU (the conjugate-pair kernels) must hold no v_pk_{add,mul,fma}_f32 at all
-    (csrc/fringe_mfma.hip, keep_scalar); tools/scan_packed_readers.py --no-packed=... is what the Makefile runs -- here on two
+    (csrc/fringe_mfma_common.h, keep_scalar); tools/scan_packed_readers.py --no-packed=... is what the Makefile runs -- here on two
     synthetic listings, and the record of the shipped build names the kernels it covered"""
     import subprocess, sys
     tool = os.path.join(ROOT, 'tools', 'scan_packed_readers.py')

@@ -83,7 +83,7 @@ def test_dispatch_restates_the_c_dispatch_rules():
 @pytest.mark.parametrize('Nt,Nf,P,S_fwd,S_bwd', [(3, 520, 1024, 1, 1), (3, 520, 17024, 2, 3), (2, 7, 17024, 15, 67),
                                                  (1, 1, 98304, 96, 384)])
 def test_split_plans(Nt, Nf, P, S_fwd, S_bwd):
-    """the pixel splits restated from ant_split_plan and the backward's `per` loop, and the workspace the library sizes
+    """the pixel splits restated from fwd_split_plan and bwd_split_plan, and the workspace the library sizes
     from the same forward split"""
     from bayeslim_amd import ops
     assert kt.fwd_splits(Nt, Nf, P) == S_fwd

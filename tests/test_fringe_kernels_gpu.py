@@ -1,7 +1,7 @@
 """
 Every matrix-core fringe kernel instantiation (tests/fringe_kernel_table.py) in the regime where the round-5 defect appeared:
 launch grids of at least two blocks per CU times the kernel's minimum blocks per CU, so that most blocks are dispatched while
-others stream MFMAs on the same CU (keep_scalar in csrc/fringe_mfma.hip).
+others stream MFMAs on the same CU (keep_scalar in csrc/fringe_mfma_common.h).
 
 Each case builds one antenna array (random or point-symmetric, partial pair sets with autocorrelations, beam-model pairs,
 groups of 32 / 64 / 128 antennas, real or complex psky, both fringe signs) on a pixel axis with a ragged tail, and checks

@@ -506,7 +506,7 @@ def test_conjugate_pair_kernels_at_the_headline_size_are_repeatable(ops, hub, mo
     """the conjugate-pair kernels are the first here whose blocks share a CU (three per CU): at the headline size -- 98 304
     directions, enough blocks that many are dispatched while others stream MFMAs on the same SIMDs -- both directions must
     be bit-identical from run to run and agree with the mirror-pair kernels.  (Round 5: packed-f32 adds in the backward's
-    staging code gave wrong G planes in a fraction of the late blocks, different every run; csrc/fringe_mfma.hip, keep_scalar.)"""
+    staging code gave wrong G planes in a fraction of the late blocks, different every run; csrc/fringe_mfma_common.h, keep_scalar.)"""
     from bayeslim_amd import utils
     ant = utils._make_hex(7, D=14.6)[1]
     if hub:

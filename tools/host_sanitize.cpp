@@ -53,6 +53,15 @@ int main()
     bad += rime_fringe_pair_fwd_block(d.data(), 64, nullptr, 0, d.data(), d.data(), f.data(), f.data(), nullptr, tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, f.data(), 4, nullptr) != RIME_EWORKSPACE;
     bad += rime_fringe_pair_bwd_block(d.data(), 0, nullptr, 0, d.data(), d.data(), f.data(), tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, 0, f.data(), f.data(), 1 << 20, nullptr) != RIME_EINVAL;
     bad += rime_fringe_pair_bwd_block(d.data(), 64, nullptr, 0, d.data(), d.data(), f.data(), tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, 0, f.data(), f.data(), 0, nullptr) != RIME_EWORKSPACE;
+    // pair cross blocks: more than 64 rows a side, a pixel stride other than 1 or 2, a missing table -> RIME_EINVAL; a workspace that is too small
+    bad += rime_fringe_pair_cross_fwd_block(d.data(), 65, 64, 0, d.data(), d.data(), f.data(), f.data(), nullptr, tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, f.data(), 1 << 20, nullptr) != RIME_EINVAL;
+    bad += rime_fringe_pair_cross_fwd_block(d.data(), 64, 64, 0, d.data(), d.data(), f.data(), f.data(), nullptr, tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 3, 1, f.data(), 1 << 20, nullptr) != RIME_EINVAL;
+    bad += rime_fringe_pair_cross_fwd_block(d.data(), 64, 64, 0, d.data(), d.data(), f.data(), f.data(), nullptr, nullptr, tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, f.data(), 1 << 20, nullptr) != RIME_EINVAL;
+    bad += rime_fringe_pair_cross_fwd_block(d.data(), 64, 64, 0, d.data(), d.data(), f.data(), f.data(), nullptr, tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, f.data(), 4, nullptr) != RIME_EWORKSPACE;
+    bad += rime_fringe_pair_cross_bwd_block(d.data(), 64, 65, 0, d.data(), d.data(), f.data(), tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, 0, f.data(), f.data(), 1 << 20, nullptr) != RIME_EINVAL;
+    bad += rime_fringe_pair_cross_bwd_block(d.data(), 64, 64, 0, d.data(), d.data(), f.data(), tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 3, 1, 0, f.data(), f.data(), 1 << 20, nullptr) != RIME_EINVAL;
+    bad += rime_fringe_pair_cross_bwd_block(d.data(), 64, 64, 0, d.data(), d.data(), f.data(), tab.data(), nullptr, 1, 1, 1, 64, 64, 64, 1, 1, 0, f.data(), f.data(), 1 << 20, nullptr) != RIME_EINVAL;
+    bad += rime_fringe_pair_cross_bwd_block(d.data(), 64, 64, 0, d.data(), d.data(), f.data(), tab.data(), tab.data(), 1, 1, 1, 64, 64, 64, 1, 1, 0, f.data(), f.data(), 4, nullptr) != RIME_EWORKSPACE;
     bad += rime_eq2top(d.data(), d.data(), -1, d.data(), d.data(), 0.0, d.data(), d.data(), nullptr) != RIME_EINVAL;
     bad += rime_eq2top(d.data(), d.data(), 0, d.data(), d.data(), 0.0, d.data(), d.data(), nullptr) != RIME_OK;
     bad += rime_interp_gather_fwd(0, 0, nullptr, nullptr, nullptr, 1, 1, 1, 1, nullptr, 1, nullptr) == RIME_OK;

@@ -10,7 +10,7 @@ have none within 30.  `limit` 24 = the 16 wait states RIME_MFMA_SETTLE guarantee
 recogniser places between an 8-pass MFMA and a VALU read of its result -- an empirical margin, not an ISA number.
 --no-packed=SUBSTRING (round 5): kernels whose mangled name contains SUBSTRING must hold NO v_pk_{add,mul,fma}_f32 at all -- the
 conjugate-pair kernels, whose blocks share a CU: packed f32 arithmetic of one block beside the MFMA stream of another gave
-wrong results there (csrc/fringe_mfma.hip, keep_scalar).
+wrong results there (csrc/fringe_mfma_common.h, keep_scalar).
 usage: python tools/scan_packed_readers.py file.s [limit] [--fail] [--no-packed=SUBSTRING]     (--fail: exit 1 on a hit)"""
 import re, sys
 argv = [a for a in sys.argv[1:] if not a.startswith('--')]
