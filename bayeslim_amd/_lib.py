@@ -92,6 +92,9 @@ SIGNATURES = {
     'rime_filt_apply': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _d, _vp, _vp]),
     'rime_fft_apply': (_i, [_i, _vp, _vp, _vp, _i, _ip, _i, _i, _ll, _i, _i, _i, _d, _i, _d, _d, _vp, _vp]),
     'rime_lm_apply': (_i, [_i, _i, _i, _i, _vp, _vp, _ll, _ll, _vp, _vp, _vp, _ll, _i, _i, _i, _ll, _vp, _vp]),
+    'rime_lbfgs_workspace': (_sz, [_i, _ll]),
+    'rime_lbfgs_dots': (_i, [_i, _vp, _vp, _i, _ll, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    'rime_lbfgs_combine': (_i, [_i, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
 }
 
 

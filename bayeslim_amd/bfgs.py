@@ -1,0 +1,541 @@
+"""
+L-BFGS optimiser with its search direction on the fused kernels of csrc/lbfgs.hip: the counterpart of the reference's
+bfgs.py (LBFGS, two_loop_recursion, strong_wolfe, cubic_interpolate) for a starting inverse Hessian that is the identity, a
+scalar or a diagonal.
+
+The two-loop recursion over m pairs (s_j, y_j) with H0 = gamma * diag(d) is a function of the inner products
+SY[i, j] = s_i . y_j, YDY[i, j] = y_i . (d o y_j), Sv[i] = s_i . v and YDv[i] = y_i . (d o v) (the compact representation of
+Byrd, Nocedal & Schnabel, Math. Prog. 63, 1994):
+
+    alpha_i = rho_i (Sv_i - sum_{j > i} alpha_j SY[i, j])                                      i = m - 1 ... 0
+    beta_i  = rho_i (gamma (YDv_i - sum_j alpha_j YDY[i, j]) + sum_{j < i} (alpha_j - beta_j) SY[j, i])      i = 0 ... m - 1
+    r = gamma * d o (v - sum_j alpha_j y_j) + sum_j (alpha_j - beta_j) s_j
+
+compact_coeffs() is that recurrence on the host in float64; rime_lbfgs_dots gives the inner products in one pass over the
+history and rime_lbfgs_combine the last line in another.  LBFGS keeps SY and YDY: a new pair adds one row and one column, from
+the same dots launch that serves the next direction.  The history is handed to the kernels as tables of row addresses (the
+tensors the optimiser holds anyway), so nothing is copied when the ring wraps.
+
+Complex parameters pass through the kernels as their interleaved real views: Re(s^H q) is the real dot product of the views,
+and a real diagonal is repeated per component.  There is no CPU path.
+
+Out of scope (the reference's dense BFGS, FactoredInvHessian, implicit_to_dense, lbfgs_approx_cov, the hmat starting
+matrices and the ParamDict line search).
+"""
+import ctypes
+import math
+from collections import deque
+
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _require_cuda, _stream, _ptr
+
+# elements of one work-group of rime_lbfgs_dots (256 lanes x 64 bytes): the unit of its first reduction stage
+DOTS_SPAN = {torch.float32: 4096, torch.float64: 2048}
+
+
+def compact_coeffs(SY, YDY, Sv, YDv, gamma, rho=None):
+    """
+    The two loops of the recursion on the Gram quantities of the module docstring, float64 on the host.
+
+    SY, YDY : (m, m) array-likes;  Sv, YDv : (m,);  gamma : float;  rho : (m,) or None for 1 / diag(SY).
+    Returns (a, b), float64 arrays of length m with r = gamma d o (v - sum a_j y_j) + sum b_j s_j.
+    """
+    SY, YDY = np.asarray(SY, dtype=np.float64), np.asarray(YDY, dtype=np.float64)
+    Sv, YDv = np.asarray(Sv, dtype=np.float64), np.asarray(YDv, dtype=np.float64)
+    m = len(Sv)
+    rho = 1.0 / np.diagonal(SY) if rho is None else np.asarray([float(x) for x in rho], dtype=np.float64)
+    gamma = float(gamma)
+    alpha, b = np.zeros(m), np.zeros(m)
+    for i in range(m - 1, -1, -1):
+        alpha[i] = rho[i] * (Sv[i] - SY[i, i + 1:] @ alpha[i + 1:])
+    t = gamma * (YDv - YDY @ alpha)
+    for i in range(m):
+        beta = rho[i] * (t[i] + b[:i] @ SY[:i, i])
+        b[i] = alpha[i] - beta
+    return alpha, b
+
+
+def _dtype_code(dtype):
+    if dtype == torch.float32:
+        return _lib.RIME_F32
+    if dtype == torch.float64:
+        return _lib.RIME_F64
+    raise TypeError('bfgs: float32 / float64 (or complex64 / complex128) vectors only, got %s' % dtype)
+
+
+def _real_view(t):
+    """the contiguous 1-D real vector the kernels read: t itself, or the interleaved view of a complex t"""
+    if t.ndim != 1:
+        t = t.reshape(-1)
+    if not t.is_contiguous():
+        t = t.contiguous()
+    if t.is_conj():
+        t = t.resolve_conj()
+    return torch.view_as_real(t).reshape(-1) if t.is_complex() else t
+
+
+def _split_H0(H0, numel, dtype, device):
+    """(gamma, d) of a starting matrix gamma * diag(d) for `numel` parameters of `dtype` on `device`: None -> (1, None), a 0-d
+    tensor -> (its value, None), a 1-d tensor -> (1, the diagonal as a real vector, repeated per component for a complex dtype)"""
+    if H0 is None:
+        return 1.0, None
+    if isinstance(H0, torch.Tensor) and not H0.is_complex():
+        if H0.ndim == 0 or (H0.ndim == 1 and H0.numel() == 1 and numel != 1):
+            return float(H0), None
+        if H0.ndim == 1:
+            if H0.numel() != numel:
+                raise ValueError('bfgs: a diagonal H0 of %d elements for %d parameters' % (H0.numel(), numel))
+            d = H0.detach().to(device=device, dtype=torch.empty(0, dtype=dtype).real.dtype)
+            if dtype.is_complex:
+                d = d.repeat_interleave(2)
+            return 1.0, d.contiguous()
+    raise NotImplementedError('bfgs: H0 must be None, a real 0-d tensor (scalar) or a real 1-d tensor (diagonal); the hmat '
+                              'starting matrices of the reference (DiagMat, SparseMat, PartitionedMat, ...) are not provided')
+
+
+class _History:
+    """the pairs as the kernels see them: real views, the two device tables of their addresses, and the launches"""
+
+    def __init__(self, N, dtype, device, d):
+        if torch.device(device).type != 'cuda':
+            raise RuntimeError("bayeslim_amd ops need tensors on the GPU (got device '%s'); there is no CPU implementation" % device)
+        self.N, self.dtype, self.device, self.d = N, dtype, device, d
+        self.code = _dtype_code(dtype)
+        self.s, self.y = [], []                    # real views, oldest first (they keep the storage alive)
+        self.table = None
+        self.ws = None
+
+    def check(self, t):
+        _require_cuda(t)
+        if t.dtype != self.dtype or t.numel() != self.N or t.device != self.device:
+            raise ValueError('bfgs: a vector of %s [%d] on %s where %s [%d] on %s is needed'
+                             % (t.dtype, t.numel(), t.device, self.dtype, self.N, self.device))
+        return t
+
+    def set_rows(self, s, y):
+        self.s, self.y = [self.check(_real_view(t)) for t in s], [self.check(_real_view(t)) for t in y]
+        m = len(self.s)
+        if m:
+            ptrs = [t.data_ptr() for t in self.s] + [t.data_ptr() for t in self.y]
+            self.table = torch.tensor(ptrs, dtype=torch.int64).to(self.device)
+            nbytes = int(_lib.lib.rime_lbfgs_workspace(m, self.N))
+            if self.ws is None or self.ws.numel() * 8 < nbytes:
+                self.ws = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+
+    def _tables(self):
+        m = len(self.s)
+        return ctypes.c_void_p(self.table.data_ptr()), ctypes.c_void_p(self.table.data_ptr() + 8 * m), m
+
+    def dots(self, v, k=-1):
+        """(2 or 5, m) float64 numpy array of rime_lbfgs_dots for the vector v (a real view)"""
+        S, Y, m = self._tables()
+        out = torch.empty((5 if k >= 0 else 2, m), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.rime_lbfgs_dots(self.code, S, Y, m, self.N, _ptr(self.check(v)), _ptr(self.d), k, _ptr(out),
+                                                _ptr(self.ws), self.ws.numel() * 8, _stream()), 'rime_lbfgs_dots')
+        return out.cpu().numpy()
+
+    def combine(self, v, a, b, gamma):
+        S, Y, m = self._tables()
+        ab = torch.as_tensor(np.stack([a, b])).to(self.device)
+        r = torch.empty_like(v)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.rime_lbfgs_combine(self.code, S, Y, m, self.N, _ptr(self.check(v)), _ptr(self.d), _ptr(ab[0]),
+                                                   _ptr(ab[1]), float(gamma), _ptr(r), _stream()), 'rime_lbfgs_combine')
+        return r
+
+
+def _shape_like(r, vec):
+    return torch.view_as_complex(r.reshape(-1, 2)) if vec.is_complex() else r
+
+
+def _start(vec, d, gamma):
+    """gamma * d o vec without a history (nothing to fuse: one elementwise product)"""
+    r = _real_view(vec)
+    return _shape_like(r * gamma if d is None else (gamma * d) * r, vec)
+
+
+def two_loop_recursion(vec, s, y, rho, H0=None):
+    """
+    The product of the implicit L-BFGS matrix defined by s, y, rho and H0 with vec (reference bfgs.two_loop_recursion), on
+    the kernels.  s, y: sequences of tensors, oldest first; rho: sequence of 1 / (s_i . y_i); H0: None, a 0-d tensor or a
+    1-d tensor (the diagonal).  The Gram matrices are formed here from len(s) dots launches; LBFGS.hvp keeps them instead.
+    """
+    _require_cuda(vec)
+    gamma, d = _split_H0(H0, vec.numel(), vec.dtype, vec.device)
+    m = len(s)
+    if m == 0:
+        return _start(vec, d, gamma)
+    v = _real_view(vec)
+    hist = _History(v.numel(), v.dtype, v.device, d)
+    hist.set_rows(list(s), list(y))
+    SY, YDY = np.zeros((m, m)), np.zeros((m, m))
+    for k in range(m):
+        out = hist.dots(v, k)
+        SY[:, k], YDY[:, k] = out[2], out[4]
+    a, b = compact_coeffs(SY, YDY, out[0], out[1], gamma, rho=rho)
+    return _shape_like(hist.combine(v, a, b, gamma), vec)
+
+
+class LBFGS:
+    """
+    Limited-memory BFGS (Nocedal & Wright, Numerical Optimization, 2nd ed., algorithm 7.4 and 7.5) with the interface of the
+    reference's bfgs.LBFGS.  All parameters live on one GPU.
+
+    H0: None (identity), a 0-d tensor (scalar) or a 1-d tensor (diagonal) -- the starting inverse Hessian, kept as
+    gamma * diag(d): with update_Hdiag the scalar gamma is reset to (y . s) / (y . d o y) whenever a pair is stored (eqn 7.20
+    with the given diagonal as the metric), which is the reference's scalar_mul applied to H and _Hdiag together.
+    _exit after step(): 0 max_iter reached, 1 directional derivative above -tolerance_change, 2 gradient below tolerance_grad
+    (or not finite), 3 step below tolerance_change, 4 loss change below tolerance_change.
+    """
+    _history_cls = _History            # what holds the pairs and runs the two passes (the tests put a float64 oracle here)
+
+    def __init__(self, params, H0=None, lr=1.0, max_iter=10, max_ls_eval=10, history_size=100, tolerance_grad=1e-14,
+                 tolerance_change=1e-16, line_search_fn='strong_wolfe', store_Hy=False, update_Hdiag=True):
+        self.update_Hdiag = update_Hdiag
+        self.history_size = history_size
+        self.lr = lr
+        self.max_iter = max_iter
+        self.max_ls_eval = max_ls_eval
+        self.tolerance_grad = tolerance_grad
+        self.tolerance_change = tolerance_change
+        self.line_search_fn = line_search_fn
+        self.store_Hy = store_Hy
+        self.params = list(params)
+        self.func_evals = 0
+        self.n_iter = 0
+        self._loss = None
+        self._flat_grad = None
+        self._numel_cache = None
+        self._exit = None
+        self._g = None
+        self._s, self._y, self._Hy = deque(), deque(), deque()
+        self._rho, self._alpha = [], []
+        self._init_H(H0)
+
+    # ------------------------------------------------------------------ starting matrix and history
+    def _init_H(self, H0):
+        p0 = self.params[0]
+        gamma, d = _split_H0(H0, self._numel(), p0.dtype, p0.device)
+        self.H = H0
+        self._gamma, self._d = gamma, d
+        self._complex = p0.is_complex()
+        rdt = p0.real.dtype if self._complex else p0.dtype
+        self._hist = self._history_cls(self._numel() * (2 if self._complex else 1), rdt, p0.device, d)
+        self._SY, self._YDY = np.zeros((0, 0)), np.zeros((0, 0))
+        self._pending = None
+
+    @property
+    def _Hdiag(self):
+        """the diagonal of the current starting matrix (ones without update_Hdiag, as in the reference)"""
+        n, dev = self._numel(), self.params[0].device
+        if not self.update_Hdiag:
+            return torch.ones(n, dtype=self._hist.dtype, device=dev)
+        d = self._d if self._d is None or not self._complex else self._d[::2]
+        return torch.full((n,), self._gamma, dtype=self._hist.dtype, device=dev) if d is None else self._gamma * d
+
+    def _set_history(self, s, y, idx):
+        """keep the pairs `idx` of the candidate lists s, y (and of the Gram matrices, which cover the candidates)"""
+        self._s, self._y = deque(s[i] for i in idx), deque(y[i] for i in idx)
+        self._SY, self._YDY = self._SY[np.ix_(idx, idx)], self._YDY[np.ix_(idx, idx)]
+        self._hist.set_rows(list(self._s), list(self._y))
+
+    def _update(self, s, y, alpha, v):
+        """
+        Offer the pair (s, y); v (a real view) is the vector whose inner products with the history come from the same
+        launch.  Returns (Sv, YDv) over the pairs kept -- with or without the new one.
+        """
+        Hy = self.hvp(y) if self.store_Hy else None
+        s_all, y_all = list(self._s) + [s], list(self._y) + [y]
+        m = len(s_all)
+        k = m - 1
+        self._hist.set_rows(s_all, y_all)
+        out = self._hist.dots(v, k)
+        ys = out[2, k]
+        self._pending = None
+        if not ys > self.tolerance_grad:
+            # not enough curvature: the pair is not stored; history, Gram matrices and gamma stay as they were
+            self._hist.set_rows(list(self._s), list(self._y))
+            return out[0, :k], out[1, :k]
+        SY, YDY = np.zeros((m, m)), np.zeros((m, m))
+        SY[:k, :k], YDY[:k, :k] = self._SY, self._YDY
+        SY[:, k], SY[k, :] = out[2], out[3]
+        YDY[:, k], YDY[k, :] = out[4], out[4]
+        self._SY, self._YDY = SY, YDY
+        keep = list(range(1, m)) if m > self.history_size else list(range(m))
+        if len(keep) < m:
+            self._rho, self._alpha = self._rho[1:], self._alpha[1:]
+            if self.store_Hy:
+                self._Hy.popleft()
+        self._set_history(s_all, y_all, keep)
+        self._rho.append(1.0 / ys)
+        self._alpha.append(alpha)
+        self._g = self.gather_flat_grad()
+        if self.store_Hy:
+            self._Hy.append(Hy)
+        if self.update_Hdiag:
+            self._gamma = float(ys / out[4, k])
+        return out[0, keep], out[1, keep]
+
+    def update_hessian(self, s, y, alpha=None):
+        """store the pair (s, y) if it has enough curvature, 1 / rho = y . s > tolerance_grad (reference LBFGS.update_hessian)"""
+        self._update(s, y, alpha, _real_view(y))
+
+    def _direction(self, vec, dots=None):
+        if len(self._s) == 0:
+            return _start(vec, self._d, self._gamma)
+        v = _real_view(vec)
+        Sv, YDv = self._hist.dots(v) if dots is None else dots
+        a, b = compact_coeffs(self._SY, self._YDY, Sv, YDv, self._gamma)
+        return _shape_like(self._hist.combine(v, a, b, self._gamma), vec)
+
+    def hvp(self, vec):
+        """implicit inverse-Hessian vector product (reference LBFGS.hvp)"""
+        return self._direction(vec)
+
+    # ------------------------------------------------------------------ parameters
+    def _numel(self):
+        if self._numel_cache is None:
+            self._numel_cache = sum(p.numel() for p in self.params)
+        return self._numel_cache
+
+    def gather_flat_grad(self):
+        views = []
+        for p in self.params:
+            if p.grad is None:
+                views.append(p.new_zeros(p.numel()))
+            elif p.grad.is_sparse:
+                views.append(p.grad.to_dense().reshape(-1))
+            else:
+                views.append(p.grad.reshape(-1))
+        return torch.cat(views, dim=0)
+
+    def update_params(self, step_size, update):
+        """move the parameters along the flat direction `update` by `step_size`"""
+        offset = 0
+        for p in self.params:
+            n = p.numel()
+            p.add_(update[offset:offset + n].view_as(p), alpha=step_size)
+            offset += n
+        assert offset == self._numel()
+
+    def clone_param(self):
+        return [p.clone(memory_format=torch.contiguous_format) for p in self.params]
+
+    def set_param(self, params_data):
+        for p, pdata in zip(self.params, params_data):
+            p.copy_(pdata)
+
+    def directional_evaluate(self, closure, x, alpha, p):
+        """loss and flat gradient at x + alpha p; the parameters are x again afterwards"""
+        self.update_params(alpha, p)
+        loss = float(closure())
+        flat_grad = self.gather_flat_grad()
+        self.set_param(x)
+        return loss, flat_grad
+
+    def zero_grad(self, set_to_none=True):
+        for p in self.params:
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    if p.grad.grad_fn is not None:
+                        p.grad.detach_()
+                    else:
+                        p.grad.requires_grad_(False)
+                    p.grad.zero_()
+
+    # ------------------------------------------------------------------ the step
+    @torch.no_grad()
+    def step(self, closure):
+        """up to max_iter iterations; closure evaluates the model, fills the gradients and returns the loss"""
+        self._exit = 0
+        closure = torch.enable_grad()(closure)
+        current_evals = 0
+        if self._loss is None:
+            loss = float(closure())
+            current_evals += 1
+            flat_grad = self.gather_flat_grad()
+        else:
+            loss, flat_grad = self._loss, self._flat_grad
+        is_finite = math.isfinite(loss) and bool(torch.isfinite(flat_grad.sum()))
+        if bool(flat_grad.abs().max() <= self.tolerance_grad) or not is_finite:
+            self._exit = 2
+            return loss
+
+        n_iter = 0
+        while n_iter < self.max_iter:
+            # direction; the inner products of this gradient with the history came with the last update, when there was one
+            dots = self._pending[1] if self._pending is not None and self._pending[0] is flat_grad else None
+            p = -self._direction(flat_grad, dots)
+
+            if self.n_iter == 0 and self.line_search_fn is None:
+                alpha = float(min(1., 1. / flat_grad.abs().sum())) * self.lr
+            else:
+                alpha = self.lr
+
+            gp = float((flat_grad.conj() @ p).real)
+            if gp > -self.tolerance_change:
+                self._exit = 1
+                break
+
+            prev_loss, prev_grad = loss, flat_grad
+            if self.line_search_fn is None:
+                self.update_params(alpha, p)
+                loss = float(closure())
+                flat_grad = self.gather_flat_grad()
+                ls_func_evals = 1
+            elif self.line_search_fn == 'strong_wolfe':
+                x = self.clone_param()
+
+                def obj_func(x, alpha, p):
+                    return self.directional_evaluate(closure, x, alpha, p)
+
+                loss, flat_grad, alpha, ls_func_evals = strong_wolfe(
+                    obj_func, x, alpha, p, loss, flat_grad, gp, tolerance_change=self.tolerance_change, max_ls=self.max_ls_eval)
+                alpha = float(alpha)
+                self.update_params(alpha, p)
+            else:
+                raise NameError("didn't recognize line_search {}".format(self.line_search_fn))
+            opt_cond = bool(flat_grad.abs().max() <= self.tolerance_grad)
+            current_evals += ls_func_evals
+            self.func_evals += ls_func_evals
+
+            if opt_cond:
+                self._exit = 2
+                break
+            if float(p.mul(alpha).abs().max()) <= self.tolerance_change:
+                self._exit = 3
+                break
+            if abs(loss - prev_loss) < self.tolerance_change:
+                self._exit = 4
+                break
+
+            # new pair and the inner products of the next direction from ONE dots launch
+            s = alpha * p
+            y = flat_grad - prev_grad
+            self._pending = (flat_grad, self._update(s, y, alpha, _real_view(flat_grad)))
+
+            n_iter += 1
+            self.n_iter += 1
+
+        self._loss = loss
+        self._flat_grad = flat_grad
+        return loss
+
+
+def cubic_interpolate(x1, f1, g1, x2, f2, g2, bounds=None):
+    """
+    Minimiser of the cubic through (x1, f1) and (x2, f2) with slopes g1, g2, clipped to bounds (default: the interval
+    between the points); the midpoint of the bounds when the cubic has no real stationary point.  Floats or 0-d tensors.
+    """
+    if bounds is not None:
+        lo, hi = bounds
+    elif x1 <= x2:
+        lo, hi = x1, x2
+    else:
+        lo, hi = x2, x1
+    d1 = g1 + g2 - 3 * (f1 - f2) / (x1 - x2)
+    d2_square = d1 ** 2 - g1 * g2
+    if not d2_square >= 0:
+        return (lo + hi) / 2.
+    d2 = d2_square.sqrt() if isinstance(d2_square, torch.Tensor) else math.sqrt(d2_square)
+    if x1 <= x2:
+        min_pos = x2 - (x2 - x1) * ((g2 + d2 - d1) / (g2 - g1 + 2 * d2))
+    else:
+        min_pos = x1 - (x1 - x2) * ((g1 + d2 - d1) / (g1 - g2 + 2 * d2))
+    return min(max(min_pos, lo), hi)
+
+
+def strong_wolfe(obj_func, x, alpha, p, f, g, gp, c1=1e-4, c2=0.9, tolerance_change=1e-9, max_ls=25):
+    """
+    Line search for a step satisfying the strong Wolfe conditions (Nocedal & Wright, algorithms 3.5 and 3.6, in the
+    arrangement of torch.optim.lbfgs that the reference uses): a bracketing phase that grows the step by cubic
+    extrapolation, then a zoom phase that shrinks the bracket by cubic interpolation, guarded against stalling at an end.
+
+    obj_func(x, alpha, p) -> (loss, flat gradient) at x + alpha p;  x: what obj_func takes as the starting point;  p: flat
+    direction;  f, g, gp: loss, flat gradient and directional derivative g . p at x.  Scalars are handled as Python floats
+    (one read-back per evaluation).  Returns (f_new, g_new, alpha, evaluations).
+    """
+    f, gp = float(f), float(gp)
+    p_norm = float(p.abs().max())
+    g = g.clone(memory_format=torch.contiguous_format)
+
+    def evaluate(a):
+        fa, ga = obj_func(x, a, p)
+        return float(fa), ga, float(ga.dot(p.conj()).real)
+
+    f_new, g_new, gp_new = evaluate(alpha)
+    ls_func_evals = 1
+
+    # bracketing
+    alpha_prev, f_prev, g_prev, gp_prev = 0, f, g, gp
+    done = False
+    ls_iter = 0
+    while ls_iter < max_ls:
+        if f_new > (f + c1 * alpha * gp) or (ls_iter > 1 and f_new >= f_prev) or (abs(gp_new) > -c2 * gp and gp_new >= 0):
+            # sufficient decrease fails, or the slope turned positive: a minimiser lies between the last two trials
+            bracket = [alpha_prev, alpha]
+            bracket_f = [f_prev, f_new]
+            bracket_g = [g_prev, g_new.clone(memory_format=torch.contiguous_format)]
+            bracket_gp = [gp_prev, gp_new]
+            break
+        if abs(gp_new) <= -c2 * gp:
+            bracket, bracket_f, bracket_g = [alpha], [f_new], [g_new]
+            done = True
+            break
+        # extrapolate
+        min_step = alpha + 0.01 * (alpha - alpha_prev)
+        max_step = alpha * 10
+        last = alpha
+        alpha = cubic_interpolate(alpha_prev, f_prev, gp_prev, alpha, f_new, gp_new, bounds=(min_step, max_step))
+        alpha_prev, f_prev, gp_prev = last, f_new, gp_new
+        g_prev = g_new.clone(memory_format=torch.contiguous_format)
+        f_new, g_new, gp_new = evaluate(alpha)
+        ls_func_evals += 1
+        ls_iter += 1
+
+    if ls_iter == max_ls:
+        bracket, bracket_f, bracket_g = [0, alpha], [f, f_new], [g, g_new]
+
+    # zoom
+    stalled = False
+    low, high = (0, 1) if bracket_f[0] <= bracket_f[-1] else (1, 0)
+    while not done and ls_iter < max_ls:
+        if abs(bracket[1] - bracket[0]) * p_norm < tolerance_change:
+            break
+        alpha = cubic_interpolate(bracket[0], bracket_f[0], bracket_gp[0], bracket[1], bracket_f[1], bracket_gp[1])
+        # a trial within a tenth of the bracket from an end: accept it once, then step a tenth in from the nearer end
+        top, bottom = max(bracket), min(bracket)
+        eps = 0.1 * (top - bottom)
+        if min(top - alpha, alpha - bottom) < eps:
+            if stalled or alpha >= top or alpha <= bottom:
+                alpha = top - eps if abs(alpha - top) < abs(alpha - bottom) else bottom + eps
+                stalled = False
+            else:
+                stalled = True
+        else:
+            stalled = False
+
+        f_new, g_new, gp_new = evaluate(alpha)
+        ls_func_evals += 1
+        ls_iter += 1
+
+        if f_new > (f + c1 * alpha * gp) or f_new >= bracket_f[low]:
+            bracket[high], bracket_f[high], bracket_gp[high] = alpha, f_new, gp_new
+            bracket_g[high] = g_new.clone(memory_format=torch.contiguous_format)
+            low, high = (0, 1) if bracket_f[0] <= bracket_f[1] else (1, 0)
+        else:
+            if abs(gp_new) <= -c2 * gp:
+                done = True
+            elif gp_new * (bracket[high] - bracket[low]) >= 0:
+                bracket[high], bracket_f[high], bracket_gp[high] = bracket[low], bracket_f[low], bracket_gp[low]
+                bracket_g[high] = bracket_g[low]
+            bracket[low], bracket_f[low], bracket_gp[low] = alpha, f_new, gp_new
+            bracket_g[low] = g_new.clone(memory_format=torch.contiguous_format)
+
+    return bracket_f[low], bracket_g[low], bracket[low], ls_func_evals

@@ -1,7 +1,7 @@
 """
 End-to-end use of the drop-in modules the way the reference's notebooks drive them: simulate visibilities of a
 HERA-37 array over a diffuse pixel sky with an Airy beam, add noise, then recover the sky by minimising the
-(negative log) posterior with torch.optim.LBFGS through optim.LogProb -- forward model, chi-square and backward all on
+(negative log) posterior with bfgs.LBFGS through optim.LogProb -- forward model, chi-square and backward all on
 the HIP kernels.  usage: python examples/fit_sky.py [iterations]
 """
 import os
@@ -9,7 +9,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from bayeslim_amd import utils, telescope_model, beam_model, sky_model, rime_model, optim, dataset
+from bayeslim_amd import utils, telescope_model, beam_model, sky_model, rime_model, optim, dataset, bfgs
 
 
 def build(dev, Nf=8, Npix=768, Nt=4, seed=0):
@@ -55,10 +55,12 @@ def main(niter=8, dev=None, verbose=True):
                                                           density=False)])
     prob = optim.LogProb(model, dataset.Dataset([target]), device=dev)
     prob.set_main_params(['rime.sky.params'])
-    opt = torch.optim.LBFGS([prob.main_params], lr=1.0, max_iter=4, history_size=10, line_search_fn='strong_wolfe')
+    opt = bfgs.LBFGS([prob.main_params], lr=1.0, max_iter=4, history_size=10, line_search_fn='strong_wolfe')
     losses = []
     for it in range(niter):
-        losses.append(float(opt.step(prob.closure)))
+        # the loss at the start of the step, as torch.optim.LBFGS reports it (bfgs.LBFGS.step returns the loss at its end)
+        losses.append(float(prob.closure()) if opt._loss is None else opt._loss)
+        opt.step(prob.closure)
         if verbose:
             print('iteration %2d: -log posterior %.6g' % (it, losses[-1]), flush=True)
     with torch.no_grad():

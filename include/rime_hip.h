@@ -547,6 +547,29 @@ int rime_redvis_bwd(int dtype, int NP, const void* gout, const int* goff, const 
                     void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * L-BFGS search direction in its compact form (bfgs.LBFGS, bfgs.two_loop_recursion; reference bfgs.py:619-678): the
+ * two-loop recursion over m pairs (s_j, y_j) with the starting matrix gamma * diag(d) restated as one pass of inner products,
+ * an m x m recurrence on the host and one linear combination.
+ *   s_rows, y_rows   DEVICE arrays of m device addresses, oldest pair first; each address is a contiguous T [N], aligned to
+ *                    sizeof(T) (a row that is not 16-byte aligned is read with element loads; the result has the same bits)
+ *   v T [N];  d T [N] real diagonal or NULL (ones);  complex vectors are passed as their interleaved real views of length 2 N
+ * rime_lbfgs_dots: out is double [2][m], out[0][j] = s_j . v, out[1][j] = y_j . (d o v); with 0 <= k < m (the index of a new
+ *   pair that is already in the tables; k = -1: none) out is double [5][m] with also out[2][j] = s_j . y_k, out[3][j] = y_j . s_k,
+ *   out[4][j] = y_j . (d o y_k).  Products and the per-lane chains (64 bytes of a row) run in T, every sum across lanes, waves
+ *   and work-groups in float64; work-groups write partial sums to the workspace (rime_lbfgs_workspace(m, N) bytes, either
+ *   dtype) and a second kernel of the same call adds them in a fixed order: no atomics, bit-reproducible, and a row's results
+ *   do not depend on k, m or the other rows.
+ * rime_lbfgs_combine: r T [N] = gamma * d o (v - sum_j a_j y_j) + sum_j b_j s_j in one pass; a, b double [m] on the device.
+ * Checked before any HIP call: RIME_EINVAL for m < 1, N < 1, an unknown dtype, a null table, v, out, a, b or r, k outside
+ * [-1, m); RIME_EWORKSPACE for a null or short workspace.  The tables live on the device and are not inspected by the host.
+ * ------------------------------------------------------------------------------------- */
+size_t rime_lbfgs_workspace(int m, long long N);
+int rime_lbfgs_dots(int dtype, const void* const* s_rows, const void* const* y_rows, int m, long long N, const void* v,
+                    const void* d, int k, double* out, void* workspace, size_t workspace_bytes, void* stream);
+int rime_lbfgs_combine(int dtype, const void* const* s_rows, const void* const* y_rows, int m, long long N, const void* v,
+                       const void* d, const double* a, const double* b, double gamma, void* r, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
