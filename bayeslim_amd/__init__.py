@@ -9,5 +9,7 @@ from . import filt                 # noqa: F401,E402
 from . import fft                  # noqa: F401,E402
 from . import linear_model         # noqa: F401,E402
 from . import bfgs                 # noqa: F401,E402
+from . import paramdict            # noqa: F401,E402
+from . import sampler              # noqa: F401,E402
 
 __version__ = '0.1.0'

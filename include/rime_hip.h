@@ -570,6 +570,29 @@ int rime_lbfgs_combine(int dtype, const void* const* s_rows, const void* const* 
                        const void* d, const double* a, const double* b, double gamma, void* r, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One leapfrog stage of Hamiltonian Monte Carlo with a diagonal mass (sampler.leapfrog, sampler.HMC.K; reference
+ * sampler.py:391-450, 1433-1583): momentum kick, position drift and kinetic energy in one pass over the flat parameter vector.
+ *   q, p   T [N] updated in place;  g T [N] the potential's gradient;  eps T [N] step size per element or NULL (ones);
+ *   c      T [N] diagonal Cholesky factor of the covariance or NULL (ones);  all aligned to sizeof(T) (a base that is not
+ *          16-byte aligned takes element accesses; the result has the same bits);  complex parameters are passed as their
+ *          interleaved real views of length 2 N with eps and c repeated per component
+ * Per element, in T, in this order:
+ *     kick  != 0:   p <- fma(-(T(kick) * eps), g, p)
+ *     drift != 0:   q <- fma(T(drift) * eps, c * (c * p), q)          with the updated p
+ *     energy:       energy[0] = 1/2 sum (c * p)^2  (double, device)   with the updated p
+ *   kick = drift = 0 with energy set is the energy-only pass.  g may be NULL only for kick = 0, q only for drift = 0.
+ *   The sum runs as the per-lane chains (64 bytes of p) in T, then float64 across lanes, waves and work-groups; work-groups
+ *   write partial sums to the workspace (rime_hmc_workspace(N) bytes, either dtype; needed only with energy) and a second
+ *   kernel of the same call adds them in a fixed order: no atomics, bit-reproducible, and the same bits with and without
+ *   the kick of the same call.
+ * Checked before any HIP call: RIME_EINVAL for an unknown dtype, N < 0, a null p, a null g with kick != 0, a null q with
+ * drift != 0, a NaN flag or a non-zero flag that rounds to zero in T; RIME_EWORKSPACE for a null or short workspace with energy.
+ * ------------------------------------------------------------------------------------- */
+size_t rime_hmc_workspace(long long N);
+int rime_hmc_step(int dtype, long long N, void* q, void* p, const void* g, const void* eps, const void* c, double kick,
+                  double drift, double* energy, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
