@@ -8,6 +8,7 @@ from . import _lib, ops            # noqa: F401  (loads librime_hip.so)
 from . import filt                 # noqa: F401,E402
 from . import fft                  # noqa: F401,E402
 from . import linear_model         # noqa: F401,E402
+from . import hmat                 # noqa: F401,E402
 from . import bfgs                 # noqa: F401,E402
 from . import paramdict            # noqa: F401,E402
 from . import sampler              # noqa: F401,E402

@@ -1,7 +1,7 @@
 """
 L-BFGS optimiser with its search direction on the fused kernels of csrc/lbfgs.hip: the counterpart of the reference's
 bfgs.py (LBFGS, two_loop_recursion, strong_wolfe, cubic_interpolate) for a starting inverse Hessian that is the identity, a
-scalar or a diagonal.
+scalar, a diagonal or an hmat operator.
 
 The two-loop recursion over m pairs (s_j, y_j) with H0 = gamma * diag(d) is a function of the inner products
 SY[i, j] = s_i . y_j, YDY[i, j] = y_i . (d o y_j), Sv[i] = s_i . v and YDv[i] = y_i . (d o v) (the compact representation of
@@ -19,8 +19,15 @@ tensors the optimiser holds anyway), so nothing is copied when the ring wraps.
 Complex parameters pass through the kernels as their interleaved real views: Re(s^H q) is the real dot product of the views,
 and a real diagonal is repeated per component.  There is no CPU path.
 
-Out of scope (the reference's dense BFGS, FactoredInvHessian, implicit_to_dense, lbfgs_approx_cov, the hmat starting
-matrices and the ParamDict line search).
+With an hmat operator (hmat.BaseMat, hmat.HierMat) as H0 the product H0 q cannot be folded into the Gram quantities, so the
+direction is the two half-recurrences around it, on the same kernels: rime_lbfgs_dots on v for s_j . v, first_loop() on the
+host, rime_lbfgs_combine for q = v - sum_j a_j y_j, z = gamma * H0 q through the operator's plan (hmat.py), rime_lbfgs_dots on z
+for y_j . z, second_loop() on the host and rime_lbfgs_combine for r = z + sum_j b_j s_j.  update_Hdiag keeps the operator as
+it is and rescales gamma with the operator's diagonal as the metric of eqn 7.20 (the reference multiplies the scalar into the
+operator in place; the product gamma * H0 is the same).
+
+Out of scope (the reference's dense BFGS, FactoredInvHessian, implicit_to_dense, lbfgs_approx_cov and the ParamDict line
+search).
 """
 import ctypes
 import math
@@ -29,7 +36,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, hmat
 from .ops import _require_cuda, _stream, _ptr
 
 # elements of one work-group of rime_lbfgs_dots (256 lanes x 64 bytes): the unit of its first reduction stage
@@ -58,6 +65,50 @@ def compact_coeffs(SY, YDY, Sv, YDv, gamma, rho=None):
     return alpha, b
 
 
+def first_loop(SY, Sv, rho=None):
+    """alpha of the first loop of the recursion: alpha_i = rho_i (Sv_i - sum_{j > i} alpha_j SY[i, j]), i = m - 1 ... 0; float64
+    on the host.  q = v - sum_j alpha_j y_j is what the starting matrix is applied to."""
+    SY, Sv = np.asarray(SY, dtype=np.float64), np.asarray(Sv, dtype=np.float64)
+    m = len(Sv)
+    rho = 1.0 / np.diagonal(SY) if rho is None else np.asarray([float(x) for x in rho], dtype=np.float64)
+    alpha = np.zeros(m)
+    for i in range(m - 1, -1, -1):
+        alpha[i] = rho[i] * (Sv[i] - SY[i, i + 1:] @ alpha[i + 1:])
+    return alpha
+
+
+def second_loop(SY, Yz, alpha, rho=None):
+    """b of the second loop for z = H0 q: beta_i = rho_i (Yz_i + sum_{j < i} b_j SY[j, i]), b_i = alpha_i - beta_i, i = 0 ... m - 1,
+    with Yz_i = y_i . z; r = z + sum_j b_j s_j."""
+    SY, Yz = np.asarray(SY, dtype=np.float64), np.asarray(Yz, dtype=np.float64)
+    m = len(Yz)
+    rho = 1.0 / np.diagonal(SY) if rho is None else np.asarray([float(x) for x in rho], dtype=np.float64)
+    b = np.zeros(m)
+    for i in range(m):
+        b[i] = alpha[i] - rho[i] * (Yz[i] + b[:i] @ SY[:i, i])
+    return b
+
+
+def _is_operator(H0):
+    return isinstance(H0, (hmat.BaseMat, hmat.HierMat))
+
+
+def _operator_direction(hist, op, gamma, vec, SY, Sv, rho=None):
+    """the direction with an hmat operator as the starting matrix (module docstring); hist holds the pairs, vec is the vector in
+    the parameters' own dtype, Sv = s_j . v from a dots launch on its real view"""
+    v = _real_view(vec)
+    d, hist.d = hist.d, None                      # the plain inner products and combinations: no diagonal in the passes
+    try:
+        zero = np.zeros(len(Sv))
+        alpha = first_loop(SY, Sv, rho)
+        q = hist.combine(v, alpha, zero, 1.0)
+        z = _real_view(hmat._apply(op, _shape_like(q, vec), scalar=None if gamma == 1.0 else gamma))
+        b = second_loop(SY, hist.dots(z)[1], alpha, rho)
+        return _shape_like(hist.combine(z, zero, b, 1.0), vec)
+    finally:
+        hist.d = d
+
+
 def _dtype_code(dtype):
     if dtype == torch.float32:
         return _lib.RIME_F32
@@ -82,6 +133,8 @@ def _split_H0(H0, numel, dtype, device):
     tensor -> (its value, None), a 1-d tensor -> (1, the diagonal as a real vector, repeated per component for a complex dtype)"""
     if H0 is None:
         return 1.0, None
+    if _is_operator(H0):
+        return 1.0, None
     if isinstance(H0, torch.Tensor) and not H0.is_complex():
         if H0.ndim == 0 or (H0.ndim == 1 and H0.numel() == 1 and numel != 1):
             return float(H0), None
@@ -92,8 +145,8 @@ def _split_H0(H0, numel, dtype, device):
             if dtype.is_complex:
                 d = d.repeat_interleave(2)
             return 1.0, d.contiguous()
-    raise NotImplementedError('bfgs: H0 must be None, a real 0-d tensor (scalar) or a real 1-d tensor (diagonal); the hmat '
-                              'starting matrices of the reference (DiagMat, SparseMat, PartitionedMat, ...) are not provided')
+    raise NotImplementedError('bfgs: H0 must be None, a real 0-d tensor (scalar), a real 1-d tensor (diagonal) or an hmat '
+                              'operator (hmat.DiagMat, SparseMat, PartitionedMat, HierMat, ...)')
 
 
 class _History:
@@ -162,13 +215,14 @@ def two_loop_recursion(vec, s, y, rho, H0=None):
     """
     The product of the implicit L-BFGS matrix defined by s, y, rho and H0 with vec (reference bfgs.two_loop_recursion), on
     the kernels.  s, y: sequences of tensors, oldest first; rho: sequence of 1 / (s_i . y_i); H0: None, a 0-d tensor or a
-    1-d tensor (the diagonal).  The Gram matrices are formed here from len(s) dots launches; LBFGS.hvp keeps them instead.
+    1-d tensor (the diagonal), or an hmat operator.  The Gram matrices are formed here from len(s) dots launches; LBFGS.hvp keeps
+    them instead.
     """
     _require_cuda(vec)
     gamma, d = _split_H0(H0, vec.numel(), vec.dtype, vec.device)
     m = len(s)
     if m == 0:
-        return _start(vec, d, gamma)
+        return H0(vec) if _is_operator(H0) else _start(vec, d, gamma)
     v = _real_view(vec)
     hist = _History(v.numel(), v.dtype, v.device, d)
     hist.set_rows(list(s), list(y))
@@ -176,6 +230,8 @@ def two_loop_recursion(vec, s, y, rho, H0=None):
     for k in range(m):
         out = hist.dots(v, k)
         SY[:, k], YDY[:, k] = out[2], out[4]
+    if _is_operator(H0):
+        return _operator_direction(hist, H0, 1.0, vec, SY, out[0], rho=rho)
     a, b = compact_coeffs(SY, YDY, out[0], out[1], gamma, rho=rho)
     return _shape_like(hist.combine(v, a, b, gamma), vec)
 
@@ -185,8 +241,8 @@ class LBFGS:
     Limited-memory BFGS (Nocedal & Wright, Numerical Optimization, 2nd ed., algorithm 7.4 and 7.5) with the interface of the
     reference's bfgs.LBFGS.  All parameters live on one GPU.
 
-    H0: None (identity), a 0-d tensor (scalar) or a 1-d tensor (diagonal) -- the starting inverse Hessian, kept as
-    gamma * diag(d): with update_Hdiag the scalar gamma is reset to (y . s) / (y . d o y) whenever a pair is stored (eqn 7.20
+    H0: None (identity), a 0-d tensor (scalar), a 1-d tensor (diagonal) or an hmat operator -- the starting inverse Hessian,
+    kept as gamma * diag(d), or as gamma * H0 with d the operator's diagonal: with update_Hdiag the scalar gamma is reset to (y . s) / (y . d o y) whenever a pair is stored (eqn 7.20
     with the given diagonal as the metric), which is the reference's scalar_mul applied to H and _Hdiag together.
     _exit after step(): 0 max_iter reached, 1 directional derivative above -tolerance_change, 2 gradient below tolerance_grad
     (or not finite), 3 step below tolerance_change, 4 loss change below tolerance_change.
@@ -221,9 +277,14 @@ class LBFGS:
         p0 = self.params[0]
         gamma, d = _split_H0(H0, self._numel(), p0.dtype, p0.device)
         self.H = H0
-        self._gamma, self._d = gamma, d
+        self._op = H0 if _is_operator(H0) else None
         self._complex = p0.is_complex()
         rdt = p0.real.dtype if self._complex else p0.dtype
+        if self._op is not None and self.update_Hdiag:
+            # the metric of eqn 7.20: the operator's diagonal, as the reference's _Hdiag
+            d = self._op.diagonal().real.detach().to(device=p0.device, dtype=rdt)
+            d = (d.repeat_interleave(2) if self._complex else d).contiguous()
+        self._gamma, self._d = gamma, d
         self._hist = self._history_cls(self._numel() * (2 if self._complex else 1), rdt, p0.device, d)
         self._SY, self._YDY = np.zeros((0, 0)), np.zeros((0, 0))
         self._pending = None
@@ -285,10 +346,14 @@ class LBFGS:
         self._update(s, y, alpha, _real_view(y))
 
     def _direction(self, vec, dots=None):
+        if self._op is not None and len(self._s) == 0:
+            return hmat._apply(self._op, vec, scalar=None if self._gamma == 1.0 else self._gamma)
         if len(self._s) == 0:
             return _start(vec, self._d, self._gamma)
         v = _real_view(vec)
         Sv, YDv = self._hist.dots(v) if dots is None else dots
+        if self._op is not None:
+            return _operator_direction(self._hist, self._op, self._gamma, vec, self._SY, Sv)
         a, b = compact_coeffs(self._SY, self._YDY, Sv, YDv, self._gamma)
         return _shape_like(self._hist.combine(v, a, b, self._gamma), vec)
 

@@ -593,6 +593,52 @@ int rime_hmc_step(int dtype, long long N, void* q, void* p, const void* g, const
                   double drift, double* energy, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Grouped block mat-vec of a flattened operator tree (hmat.BaseMat.mat_vec_mul / mat_mat_mul; reference hmat.py): y (+)=
+ * scalar * A x, A given as a DEVICE table of ntiles tiles of 64 bytes each:
+ *     struct rime_hmat_tile { const void* a; long long ld, src_off, dst_off; double scale; int rows, cols, flags, stage;
+ *                             long long reserved; };
+ *   a         real matrix T [rows][ld] (ld >= cols) as stored, or, with RIME_HMAT_DIAG, a vector T [rows] (cols = 1) or ONE
+ *             value repeated rows times (cols = 0); aligned to sizeof(T) only: a base or ld that is not a multiple of 16 bytes
+ *             takes element loads of the same elements (the result has the same bits), any other 16-byte loads
+ *   flags     RIME_HMAT_TRANS 1: the tile applies the transpose of the stored matrix (cols outputs from rows inputs);
+ *             RIME_HMAT_DIAG 2;  RIME_HMAT_SRC_SCRATCH 4: the input segment lies in the scratch vector, not in x
+ *   src_off, dst_off   first element of the input / output segment in its vector;  stage: the launch the tile belongs to
+ * The destination of a tile is fixed by the row ranges that list it.  ranges: DEVICE long long [5] per work-group, those of
+ * stage s at entries stage_first[s] ... stage_first[s + 1] - 1 (stage_first: HOST int [nstages + 1]): {flags, first row, rows
+ * (at most 256), first entry of tile_ids, entries}; flags 1: the rows are rows of the scratch vector (written as the plain sum),
+ * 2: the rows of y are added to whatever `accumulate` says (the later stages).  tile_ids: DEVICE int, the tiles of each range
+ * in the order they are visited.  Stage 0 must cover every row of y once (a row without tiles receives 0); the ranges of one
+ * stage must not overlap.  x, y, scratch: T [n][nrhs], the nrhs right-hand sides interleaved per element (a complex vector is
+ * its interleaved real view with nrhs = 2); any nrhs >= 1, served four columns per launch.  The scratch vector is the
+ * workspace: rime_hmat_workspace(dtype, scratch_rows, nrhs) bytes.
+ * Arithmetic, all in T, per output row and right-hand side: acc = 0; for each tile of the range that touches the row, in
+ * tile_ids order, acc = fma(T(scale), s, acc) with s the tile's sum (W = 16 / sizeof(T)):
+ *   plain form, cols > 32 W    lane l of a wave holds columns 128 W c + (64 g + l) W + e (chunk c ascending, g = 0, 1, e < W)
+ *                 and runs one chain p = fma(A[i][col], x[col], p) over them in ascending order; s is the butterfly sum of
+ *                 the 64 chains (p += p of lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1)
+ *   plain form, cols <= 32 W   G = the power of two >= cols / W lanes share the row, lane g its columns g W + e as one chain;
+ *                 s is the butterfly sum over the G lanes (^ G / 2, ..., ^ 1)
+ *   TRANS, cols > 32 W         wave w of the four runs one chain over the stored rows j = w, w + 4, ... ascending;
+ *                 s = ((p0 + p1) + p2) + p3
+ *   TRANS, cols <= 32 W        with G as above and S = 64 / G, wave w and slot u < S run one chain over the stored rows
+ *                 j = S w + u, + 4 S, ... ascending; s is the sum of the 4 S chains in the order (w, u), w major, from the left
+ *   DIAG          s = a[i] * x[i]
+ * then y = T(scalar) * acc, or fma(T(scalar), acc, y) when accumulating; scratch = acc.  No atomics and no communication
+ * between work-groups: bit-reproducible, and a row's result depends on its own tiles and their order only.  Stages are
+ * separate launches on `stream`.
+ * Checked before any HIP call: RIME_EINVAL for an unknown dtype, ntiles < 0, nstages outside [1, 8], nrhs < 1, scratch_rows
+ * < 0, a decreasing or negative stage_first, a null ranges, stage_first, x or y, a null tiles or tile_ids with ntiles > 0;
+ * then RIME_EWORKSPACE for a null or short workspace with scratch_rows > 0.  The device tables are not inspected by the host.
+ * ------------------------------------------------------------------------------------- */
+#define RIME_HMAT_TRANS 1
+#define RIME_HMAT_DIAG 2
+#define RIME_HMAT_SRC_SCRATCH 4
+size_t rime_hmat_workspace(int dtype, long long scratch_rows, int nrhs);
+int rime_hmat_apply(int dtype, const void* tiles, int ntiles, const long long* ranges, const int* tile_ids,
+                    const int* stage_first, int nstages, long long scratch_rows, const void* x, void* y, int nrhs,
+                    double scalar, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
