@@ -71,7 +71,8 @@ __device__ __forceinline__ void split2_prod(float a0, float b0, float a1, float 
 // is therefore (MFMA issue time) + (VALU issue time), and the design minimises both:
 //   * symmetric weighting: L = B = sqrt(|psky| scale) E, so ONE operand image pair (f16 hi, lo) is
 //     generated per (antenna, pixel) instead of two; the sign of psky is applied as an XOR mask on
-//     the row-tile fragments (per wave: 16 v_xor per distinct row tile and panel);
+//     the row-tile fragments (per wave: 16 v_xor per distinct row tile and panel) -- or, where the
+//     row tiles can be two-coloured, generated into the rows of one colour (SIGNED ROWS below);
 //   * re and im live in separate K-planes ([antenna][32 px re | 32 px im]), K = 16 pixels per
 //     MFMA.  Vr = Lr.Br + Li.Bi,  Vi = Lr.Bi - Li.Br with the two Vi products kept in separate
 //     accumulators and subtracted in the epilogue: no operand rotation / negation work at all;
@@ -138,6 +139,24 @@ constexpr int MF_ROWB = 4 * MF_KP + 16;         // [re KP x f16][im KP x f16][pa
 // the upper-triangular tiles (12 MFMAs each: L and B differ, no diagonal-tile symmetry) are contracted: one pass
 // instead of the two real-plane passes of the diagonal kernel (12 TA (TA + 1) / 2 against 2 x (12 TA (TA - 1) / 2
 // + 7 TA) MFMAs per K step, half the trigonometry).
+// SIGNED ROWS.  With symmetric weighting every row holds sqrt(|psky| scale) E and the sign of psky is an XOR mask on the L
+// fragments: 16 v_xor per row tile, K step and wave, re-creating a sign that generation had in a register.  Where the row tiles of
+// a block can be TWO-COLOURED so that every off-diagonal tile pairs the two colours, one colour is GENERATED with the sign in its
+// weight (copysign(w, psky) in place of w: no instruction more per row) and the other without, and an off-diagonal tile needs no
+// mask at all; on a diagonal tile (L and B the same rows) the mask stays and merely toggles: it yields the unsigned side of
+// signed rows and the signed side of unsigned ones.  The stored bits are those the mask produced: cvt_pkrtz rounds toward zero,
+// so hi(-x) = -hi(x), the residual x - hi is the exact negation and so is lo (a residual of exactly zero is +0 where the mask
+// made -0: nothing in a sum).  Which shape takes which rule (real psky, the SIGNED instantiations only):
+//   * cross blocks <TI, TJ, true>: L always group I, B always group J -- group I signed, no mask and no sign dwords;
+//   * the pair kernels' two-tile form (pair_fwd_body): tile 0 signed, tile 1 not; the waves of tile (0,1) read their L
+//     fragments as stored, the two diagonal-tile waves keep the mask;
+//   * the generic two-tile diagonal <2, 2, false> could take the same rule and does NOT: its signed instantiations grew from 128
+//     to 144 registers with it (four -> three waves per SIMD) and the time did not move (64 antennas, 98 304 directions x 64
+//     channels x 4 times: 1.877 ms without, 1.893 with, spread 0.03: profiles/r10/fwd_signed_rows.txt) -- as before;
+//   * one tile (<1, 1, false>, the packed 33..48 kernel, pair_fwd1): diagonal only, nothing to gain -- as before;
+//   * three and four tiles (<3, 3, false>, <4, 4, false>): tiles (0,1) (0,2) (1,2) form a triangle, which has no two-colouring
+//     -- as before;
+//   * complex single-pass cross blocks and self blocks have asymmetric weighting and never had a mask.
 template <int TI_, int TJ_, bool CROSS_, bool SELF_ = false>
 struct FwdShape {
     static_assert(!SELF_ || (CROSS_ && TI_ == TJ_), "a self block is a cross block of a group with itself");
@@ -235,6 +254,11 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
     constexpr int UE = SH::KSPLIT ? U0 + 1 : unit_begin<SH>(W + 1);
     constexpr int MF_IMG = SH::IMG, MF_BUF = SH::BUF;
     constexpr int BROW = SH::CROSS ? SH::TI : 0;     // image row-tile offset of the column (B) side
+    // SIGNED ROWS (see FwdShape): a real-psky cross block generates the rows of group I -- the first SROWS sweeps, of 32 rows in
+    // every mapping these shapes take -- with the sign of psky in their weight; XORL: the L fragments take the XOR mask (diagonal blocks)
+    constexpr bool SROWS_X = SIGNED && !CPLX && SH::CROSS && !SH::SELF;
+    constexpr int SROWS = SROWS_X ? SH::TI : 0;
+    constexpr bool XORL = SIGNED && !SROWS_X;
     const int tid = threadIdx.x, lane = tid & 63;
     // 1-D grid, channel fastest: blocks that run together share (t, split), i.e. the same pointing
     // vectors (L2 hits), and no grid dimension hits the 65535 cap
@@ -339,11 +363,19 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
         if constexpr (OCT) {
             constexpr int hf = W & 1;
             const float w0 = __builtin_amdgcn_sqrtf(fabsf(av[hf].x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av[hf].y) * scl);
-            if (SIGNED && W < 2 && lane < 8)
+            if (SIGNED && !SROWS_X && W < 2 && lane < 8)
                 *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
                     ((__float_as_uint(av[hf].x) >> 16) & 0x8000u) | (__float_as_uint(av[hf].y) & 0x80000000u);
+            // the weight with the sign of psky: sweeps below SROWS store it.  Of the shapes that come this way only the eight-wave
+            // cross blocks (OCT8) have SROWS > 0; in every diagonal instantiation -- MIR included, which implies !CROSS -- SROWS is 0,
+            // `u < SROWS ? g : w` folds to w at compile time and their code is the parent's instruction for instruction
+            float g0 = w0, g1 = w1;
+            if constexpr (SROWS > 0) {
+                g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av[hf].x) & 0x80000000u));
+                g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av[hf].y) & 0x80000000u));
+            }
             // one evaluated sweep: the weighted f16 halves of this lane's pixel pair for the antenna at (bx, by, bz)
-            auto sweep = [&](double bx, double by, double bz, uint32_t& rh, uint32_t& rl, uint32_t& ih, uint32_t& il) {
+            auto sweep = [&](float w0, float w1, double bx, double by, double bz, uint32_t& rh, uint32_t& rl, uint32_t& ih, uint32_t& il) {
                 const double ph0 = phase3(bx, sx[hf].x, by, sy[hf].x, bz, sz[hf].x);
                 const double ph1 = phase3(bx, sx[hf].y, by, sy[hf].y, bz, sz[hf].y);
                 const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
@@ -367,7 +399,7 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                         uint32_t rh, rl, ih, il;
                         if ((u & 1) && ((A.mirror >> (2 * (u >> 1) + (W >> 1))) & 1)) {
                             rh = m_rh; rl = m_rl; ih = m_ih ^ 0x80008000u; il = m_il ^ 0x80008000u;
-                        } else sweep(ax[u], ay[u], az[u], rh, rl, ih, il);
+                        } else sweep(u < SROWS ? g0 : w0, u < SROWS ? g1 : w1, ax[u], ay[u], az[u], rh, rl, ih, il);
                         if (!(u & 1)) { m_rh = rh; m_rl = rl; m_ih = ih; m_il = il; }
                         store(octet_row(u), rh, rl, ih, il);
                     }
@@ -377,7 +409,7 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                 for (int u = 0; u < NGEN; ++u) {
                     if (u < nk) {
                         uint32_t rh, rl, ih, il;
-                        sweep(ax[u], ay[u], az[u], rh, rl, ih, il);
+                        sweep(u < SROWS ? g0 : w0, u < SROWS ? g1 : w1, ax[u], ay[u], az[u], rh, rl, ih, il);
                         store(OCT8 ? 32 * u + growx : octet_row(u), rh, rl, ih, il);
                     }
                 }
@@ -427,19 +459,25 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
 #pragma unroll
         for (int hf = 0; hf < MF_NH; ++hf) {
             const float w0 = __builtin_amdgcn_sqrtf(fabsf(av[hf].x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av[hf].y) * scl);
-            if (SIGNED && tid < 8)
+            if (SIGNED && !SROWS_X && tid < 8)
                 *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
                     ((__float_as_uint(av[hf].x) >> 16) & 0x8000u) | (__float_as_uint(av[hf].y) & 0x80000000u);
+            float g0 = w0, g1 = w1;                  // the weight with the sign of psky: sweeps below SROWS store it
+            if constexpr (SROWS > 0) {
+                g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av[hf].x) & 0x80000000u));
+                g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av[hf].y) & 0x80000000u));
+            }
 #pragma unroll
             for (int u = 0; u < SH::GEN; ++u) {
+                const float m0 = u < SROWS ? g0 : w0, m1 = u < SROWS ? g1 : w1;
                 const double ph0 = phase3(ax[u], sx[hf].x, ay[u], sy[hf].x, az[u], sz[hf].x);
                 const double ph1 = phase3(ax[u], sx[hf].y, ay[u], sy[hf].y, az[u], sz[hf].y);
                 const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
                 const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
                 const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
                 uint32_t rh, rl, ih, il;
-                split2(w0 * c0, w1 * c1, rh, rl);
-                split2(w0 * s0, w1 * s1, ih, il);
+                split2(m0 * c0, m1 * c1, rh, rl);
+                split2(m0 * s0, m1 * s1, ih, il);
                 unsigned char* o = buf + goff + u * SH::GROWS * MF_ROWB + 32 * hf;
                 *reinterpret_cast<uint32_t*>(o) = rh;
                 *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
@@ -459,7 +497,7 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
         };
         auto sfrag = [&](int tile, int img, int im, int ks, const uint4& sg) {
             uint4 v = frag(tile, img, im, ks);
-            if constexpr (SIGNED) { v.x ^= sg.x; v.y ^= sg.y; v.z ^= sg.z; v.w ^= sg.w; }
+            if constexpr (XORL) { v.x ^= sg.x; v.y ^= sg.y; v.z ^= sg.z; v.w ^= sg.w; }
             return v;
         };
         constexpr int T0 = U0 >> 1, T1 = (UE + 1) >> 1;               // its tiles: [T0, T1)
@@ -475,7 +513,7 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                 constexpr int ti = tile_row<SH>(tile), tj = BROW + tile_col<SH>(tile);
                 if constexpr (tile == T0 || tile_row<SH>(tile > 0 ? tile - 1 : 0) != ti) {
                     uint4 sg = make_uint4(0, 0, 0, 0);
-                    if constexpr (SIGNED) sg = *reinterpret_cast<const uint4*>(buf + 2 * MF_IMG + (2 * ks + (lane >> 5)) * 16);
+                    if constexpr (XORL) sg = *reinterpret_cast<const uint4*>(buf + 2 * MF_IMG + (2 * ks + (lane >> 5)) * 16);
                     Lrh = sfrag(ti, 0, 0, ks, sg); Lih = sfrag(ti, 0, 1, ks, sg);
                     Lrl = sfrag(ti, 1, 0, ks, sg); Lil = sfrag(ti, 1, 1, ks, sg);
                 }
@@ -992,8 +1030,12 @@ fringe_ant_fwd_packed_kernel(AntArgs A)
 // conj(B) ((0,2) (0,3) (1,2) (1,3)); the host (ops._pair_block) builds them with the rule of every diagonal block.
 // Deal: wave 0: Pcc, Pss of tile (0,1) (6 MFMAs per K step); wave 1: Pcs, Psc of tile (0,1) (6); wave 2: tile (0,0);
 // wave 3: tile (1,1) (7 each: (hi / 2) x hi + hi x lo of Pcc and of Pss -- the other halves are their transposes --
-// and the three products of Pcs in the two accumulators of the generic kernel's diagonal form).  164 registers: three
+// and the three products of Pcs in the two accumulators of the generic kernel's diagonal form).  164 registers at most, as before: three
 // blocks per CU.
+// The sign s_p (SIGNED ROWS at FwdShape): rows 0..31 are generated as s_p sqrt(|psky| scale) E, rows 32..63 without the sign, so
+// waves 0 and 1 -- tile (0,1): L rows 0..31, B rows 32..63 -- read their fragments as stored; waves 2 and 3 keep the XOR mask of
+// the panel's sign dwords on their L fragments, which toggles: the unsigned side of tile 0's rows, the signed side of tile 1's.
+// The hub's column sums multiply by the weight the row does NOT carry (w on signed rows, +-w on unsigned ones).
 // ---------------------------------------------------------------------------------------
 struct PairArgs : AntArgs {
     const int* centre;         // CEN: [2][128] baseline slots receiving V[c, r] (first 128) / conj(V[c, r]) (last 128), r = virtual row
@@ -1075,9 +1117,10 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
         if (SIGNED && W < 2 && lane < 8)
             *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
                 ((__float_as_uint(av.x) >> 16) & 0x8000u) | (__float_as_uint(av.y) & 0x80000000u);
-        // CEN: sum_p psky scale E = sum_p (+-w)(w E): the weight once more, with the sign of psky
+        // the weight once more, with the sign of psky: the rows of tile 0 are stored with it (SIGNED ROWS above), and with CEN
+        // sum_p psky scale E = sum_p (+-w)(w E) is the product of the two weights whichever of them the row carries
         float g0 = w0, g1 = w1;
-        if constexpr (CEN && SIGNED) {
+        if constexpr (SIGNED) {
             g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av.x) & 0x80000000u));
             g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av.y) & 0x80000000u));
         }
@@ -1089,16 +1132,19 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
                 const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
                 const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
                 const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                // sweeps 0, 1 write tile 0 (signed rows), sweeps 2, 3 tile 1 (unsigned): m the weight stored, n the other one
+                const float m0 = u < 2 ? g0 : w0, m1 = u < 2 ? g1 : w1;
+                const float n0 = u < 2 ? w0 : g0, n1 = u < 2 ? w1 : g1;
                 uint32_t rh, rl, ih, il;
                 if constexpr (!CEN) {
-                    split2(w0 * c0, w1 * c1, rh, rl);
-                    split2(w0 * s0, w1 * s1, ih, il);
+                    split2(m0 * c0, m1 * c1, rh, rl);
+                    split2(m0 * s0, m1 * s1, ih, il);
                 } else {
                     float xr0, xr1, xi0, xi1;
-                    split2_prod(w0, c0, w1, c1, xr0, xr1, rh, rl);
-                    split2_prod(w0, s0, w1, s1, xi0, xi1, ih, il);
-                    cr[u] = fmaf(g0, xr0, cr[u]); keep_scalar(cr[u]); ci[u] = fmaf(g0, xi0, ci[u]);
-                    cr[u] = fmaf(g1, xr1, cr[u]); keep_scalar(cr[u]); ci[u] = fmaf(g1, xi1, ci[u]);
+                    split2_prod(m0, c0, m1, c1, xr0, xr1, rh, rl);
+                    split2_prod(m0, s0, m1, s1, xi0, xi1, ih, il);
+                    cr[u] = fmaf(n0, xr0, cr[u]); keep_scalar(cr[u]); ci[u] = fmaf(n0, xi0, ci[u]);
+                    cr[u] = fmaf(n1, xr1, cr[u]); keep_scalar(cr[u]); ci[u] = fmaf(n1, xi1, ci[u]);
                 }
                 unsigned char* o = buf + octet_row(u) * MF_ROWB + pp * 4 + 32 * hf;
                 *reinterpret_cast<uint32_t*>(o) = rh;
@@ -1122,10 +1168,10 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
 #pragma unroll
         for (int ks = 0; ks < MF_NH; ++ks) {
             uint4 sg = make_uint4(0, 0, 0, 0);
-            if constexpr (SIGNED) sg = *reinterpret_cast<const uint4*>(buf + 2 * MF_IMG + (2 * ks + (lane >> 5)) * 16);
-            if constexpr (W == 0) {                  // tile (0,1): Pcc -> acc[0], Pss -> acc[1]
-                const uint4 Lrh = sgn(frag(0, 0, 0, ks), sg), Lih = sgn(frag(0, 0, 1, ks), sg);
-                const uint4 Lrl = sgn(frag(0, 1, 0, ks), sg), Lil = sgn(frag(0, 1, 1, ks), sg);
+            if constexpr (SIGNED && W >= 2) sg = *reinterpret_cast<const uint4*>(buf + 2 * MF_IMG + (2 * ks + (lane >> 5)) * 16);
+            if constexpr (W == 0) {                  // tile (0,1): Pcc -> acc[0], Pss -> acc[1]; L the signed rows, B the unsigned
+                const uint4 Lrh = frag(0, 0, 0, ks), Lih = frag(0, 0, 1, ks);
+                const uint4 Lrl = frag(0, 1, 0, ks), Lil = frag(0, 1, 1, ks);
                 const uint4 Brh = frag(1, 0, 0, ks), Bih = frag(1, 0, 1, ks), Brl = frag(1, 1, 0, ks), Bil = frag(1, 1, 1, ks);
                 acc[0] = RIME_MFMA(Lrh, Brh, acc[0]);
                 acc[1] = RIME_MFMA(Lih, Bih, acc[1]);
@@ -1134,8 +1180,8 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
                 acc[0] = RIME_MFMA(Lrl, Brh, acc[0]);
                 acc[1] = RIME_MFMA(Lil, Bih, acc[1]);
             } else if constexpr (W == 1) {           // tile (0,1): Pcs = Lr.Bi -> acc[0], Psc = Li.Br -> acc[1]
-                const uint4 Lrh = sgn(frag(0, 0, 0, ks), sg), Lih = sgn(frag(0, 0, 1, ks), sg);
-                const uint4 Lrl = sgn(frag(0, 1, 0, ks), sg), Lil = sgn(frag(0, 1, 1, ks), sg);
+                const uint4 Lrh = frag(0, 0, 0, ks), Lih = frag(0, 0, 1, ks);
+                const uint4 Lrl = frag(0, 1, 0, ks), Lil = frag(0, 1, 1, ks);
                 const uint4 Brh = frag(1, 0, 0, ks), Bih = frag(1, 0, 1, ks), Brl = frag(1, 1, 0, ks), Bil = frag(1, 1, 1, ks);
                 acc[0] = RIME_MFMA(Lrh, Bih, acc[0]);
                 acc[1] = RIME_MFMA(Lih, Brh, acc[1]);
@@ -1143,8 +1189,8 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
                 acc[1] = RIME_MFMA(Lih, Brl, acc[1]);
                 acc[0] = RIME_MFMA(Lrl, Bih, acc[0]);
                 acc[1] = RIME_MFMA(Lil, Brh, acc[1]);
-            } else {                                 // diagonal tile W - 2: L and B are the same rows (up to the pixel sign)
-                constexpr int tt = W - 2;
+            } else {                                 // diagonal tile W - 2: L and B are the same rows (up to the pixel sign);
+                constexpr int tt = W - 2;            // sgn() toggles: the unsigned side of tile 0's signed rows, the signed side of tile 1's
                 const uint4 Brh = frag(tt, 0, 0, ks), Bih = frag(tt, 0, 1, ks), Brl = frag(tt, 1, 0, ks), Bil = frag(tt, 1, 1, ks);
                 const uint4 Lrh = sgn(Brh, sg), Lih = sgn(Bih, sg);
                 // Pcc = h + h^T with h = (Lrh / 2).Brh + Lrh.Brl (the lo x hi product is the transpose of hi x lo), Pss alike: the

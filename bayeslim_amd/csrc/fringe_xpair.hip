@@ -35,7 +35,7 @@ constexpr int KP = 32;                       // pixels per panel; 16 per MFMA
 constexpr int NH = KP / 16;
 constexpr int ROWB = 4 * KP + 16;            // [re KP x f16][im KP x f16][pad]: odd number of 16-B granules
 constexpr int IMG = 2 * XR * ROWB;           // one image (hi or lo): rows 0..63 group I, 64..127 group J
-constexpr int BUF = 2 * IMG + 64;            // hi + lo + sign dwords of the panel
+constexpr int BUF = 2 * IMG + 64;            // hi + lo (+ 64 bytes that held the panel's sign dwords: unused, the offsets stay)
 constexpr size_t FWD_LDS = 2 * (size_t)BUF;
 
 static_assert(KP == MF_KP, "the forward split plan (fringe_mfma_common.h) counts panels of MF_KP pixels");
@@ -65,8 +65,10 @@ __device__ __forceinline__ bool row_is_signed(const FwdArgs& A)
 
 // Forward.  Block = one (t, f, pixel split), four waves.  Generation as in the pair kernels: lane = (pixel pair, row of an octet),
 // a wave writes one 16-pixel half of the panel for every second 16-row group of the 128 image rows (8 sweeps; octets that hold
-// padding rows only are skipped).  Symmetric weighting: both groups' rows hold sqrt(|psky| scale) E, the sign of psky is an XOR
-// mask on the group-I fragments.  Wave W contracts output tile (W >> 1, W & 1): Pcc, Pss, Pcs, Psc in four accumulators, 12
+// padding rows only are skipped).  Symmetric weighting: both groups' rows hold sqrt(|psky| scale) E, and the rows of group I are
+// GENERATED with the sign of psky in their weight (SIGNED ROWS in fringe_mfma.hip: L always comes from group I, B from group J, so
+// no fragment is signed after it is read; the stored f16 pairs are bit for bit those an XOR mask on the group-I fragments gave:
+// cvt_pkrtz is odd, the residual of the split an exact negation).  Wave W contracts output tile (W >> 1, W & 1): Pcc, Pss, Pcs, Psc in four accumulators, 12
 // MFMAs per K step.
 template <int W, bool SIGNED, bool FLAT>
 __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* smem)
@@ -137,18 +139,22 @@ __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* 
     };
     auto generate = [&](unsigned char* buf, int next_panel) {
         const float w0 = __builtin_amdgcn_sqrtf(fabsf(av.x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av.y) * scl);
-        if (SIGNED && W < 2 && lane < 8)
-            *reinterpret_cast<uint32_t*>(buf + 2 * IMG + 4 * (8 * hf + pp)) =
-                ((__float_as_uint(av.x) >> 16) & 0x8000u) | (__float_as_uint(av.y) & 0x80000000u);
+        // the weight of group I's rows (sweeps 0..3) carries the sign of psky
+        float g0 = w0, g1 = w1;
+        if constexpr (SIGNED) {
+            g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av.x) & 0x80000000u));
+            g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av.y) & 0x80000000u));
+        }
 #pragma unroll
         for (int u = 0; u < NGEN; ++u) {
             if ((live >> u) & 1u) {
+                const float m0 = u < 4 ? g0 : w0, m1 = u < 4 ? g1 : w1;
                 const double ph0 = phase_of<FLAT>(ax[u], sx.x, ay[u], sy.x, az[u], sz.x);
                 const double ph1 = phase_of<FLAT>(ax[u], sx.y, ay[u], sy.y, az[u], sz.y);
                 const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
                 const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
                 const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
-                float xr0 = w0 * c0, xr1 = w1 * c1, xi0 = w0 * s0, xi1 = w1 * s1;
+                float xr0 = m0 * c0, xr1 = m1 * c1, xi0 = m0 * s0, xi1 = m1 * s1;
                 keep_scalar(xr0); keep_scalar(xr1); keep_scalar(xi0); keep_scalar(xi1);
                 uint32_t rh, rl, ih, il;
                 split2(xr0, xr1, rh, rl);
@@ -169,16 +175,10 @@ __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* 
         auto frag = [&](int tile, int img, int im, int ks) {
             return *reinterpret_cast<const uint4*>(buf + img * IMG + tile * 32 * ROWB + foff + im * 2 * KP + 32 * ks);
         };
-        auto sgn = [&](uint4 v, const uint4& sg) {
-            if constexpr (SIGNED) { v.x ^= sg.x; v.y ^= sg.y; v.z ^= sg.z; v.w ^= sg.w; }
-            return v;
-        };
 #pragma unroll
         for (int ks = 0; ks < NH; ++ks) {
-            uint4 sg = make_uint4(0, 0, 0, 0);
-            if constexpr (SIGNED) sg = *reinterpret_cast<const uint4*>(buf + 2 * IMG + (2 * ks + (lane >> 5)) * 16);
-            const uint4 Lrh = sgn(frag(ti, 0, 0, ks), sg), Lih = sgn(frag(ti, 0, 1, ks), sg);
-            const uint4 Lrl = sgn(frag(ti, 1, 0, ks), sg), Lil = sgn(frag(ti, 1, 1, ks), sg);
+            const uint4 Lrh = frag(ti, 0, 0, ks), Lih = frag(ti, 0, 1, ks);
+            const uint4 Lrl = frag(ti, 1, 0, ks), Lil = frag(ti, 1, 1, ks);
             const uint4 Brh = frag(2 + tj, 0, 0, ks), Bih = frag(2 + tj, 0, 1, ks);
             const uint4 Brl = frag(2 + tj, 1, 0, ks), Bil = frag(2 + tj, 1, 1, ks);
             acc[0] = RIME_MFMA(Lrh, Brh, acc[0]);
