@@ -310,6 +310,128 @@ class VisData(TensorData):
                         cov=avg_cov, icov=avg_icov, cov_axis=None, history=self.history)
         return vout
 
+    # ---- LST alignment (dataset.py:1363-1566): rephasing, nearest-LST selection and time averaging on one fused kernel
+    def get_bl_vecs(self, bls):
+        """baseline vectors (Nbl, 3) in ENU [m] of antenna pairs or baseline numbers (dataset.py:534-554)"""
+        if isinstance(bls, (np.ndarray, torch.Tensor)):
+            ant1, ant2 = utils.blnum2ants(bls, separate=True)
+        else:
+            ant1, ant2 = zip(*bls)
+        return self.antpos[list(ant2)] - self.antpos[list(ant1)]
+
+    def _rephase_tau(self, dLST):
+        from . import telescope_model
+        dLST = np.asarray(utils.tensor2numpy(dLST) if isinstance(dLST, torch.Tensor) else dLST, dtype=np.float64)
+        return telescope_model.rephase_tau(dLST, self.telescope.location[1], self.get_bl_vecs(self.bls))
+
+    def lst_rephase(self, dtime=None, dLST=None, inplace=True):
+        """
+        Rephase zenith-pointing drift-scan data by a difference in LST (dataset.py:1363-1399).  dLST [rad]: a scalar or one
+        value per time.  dtime [Julian days] (parity unpinned: the reference takes the sidereal day from astropy, here
+        SDAY_SEC = 86164.0905 s): converted as dLST = dtime 2 pi / sidereal day.  The delay of every (baseline, time) is
+        computed on the host; the phasor is generated and applied inside one launch (ops.vis_timeavg with singleton bins),
+        never stored.  Differentiable with respect to the data.  inplace: this object receives the rephased tensor.
+        """
+        from . import ops
+        if dLST is None:
+            assert dtime is not None
+            dLST = np.asarray(utils.tensor2numpy(dtime) if isinstance(dtime, torch.Tensor) else dtime,
+                              dtype=np.float64) * 2 * np.pi / (SDAY_SEC / 86400.0)
+        tau = self._rephase_tau(dLST)
+        if tau.shape[1] != self.Ntimes:
+            tau = tau.expand(tau.shape[0], self.Ntimes)
+        plan = ops.TimeAvgPlan(np.arange(self.Ntimes)[:, None], self.Ntimes)
+        vd = self if inplace else self.copy(copydata=False)
+        vd.data = ops.vis_timeavg(self.data, plan, tau=tau, freqs=self.freqs)[0]
+        return vd
+
+    def time_nn_interp(self, lsts, rephase=True, inplace=True):
+        """
+        Nearest-neighbour interpolation onto the LST bins `lsts` [rad] (dataset.py:1401-1450): every target takes the
+        integration whose LST is nearest (both LST sets unwrapped across 2 pi by the reference's rule) and, with rephase,
+        is rephased by the remaining difference -- one launch with singleton bins, in which data, flags and cov follow the
+        selected times (icov by a plain gather); `times` becomes the selected times.  An integration may serve several
+        targets, each with its own delay.  Differentiable with respect to the data.
+        """
+        from . import ops, telescope_model
+        lsts = np.array(utils.tensor2numpy(lsts) if isinstance(lsts, torch.Tensor) else lsts, dtype=np.float64)
+        t_idx, dLST = nearest_lst(lsts, telescope_model.JD2LST(utils.tensor2numpy(self.times), self.telescope.location[0]) * utils.D2R)
+        plan = ops.TimeAvgPlan(t_idx[:, None], self.Ntimes)
+        tau = self._rephase_tau(dLST) if rephase else None
+        diag = self.cov_axis is None
+        data, _, cov, flags = ops.vis_timeavg(self.data, plan, cov=self.cov if diag else None, flags=self.flags, tau=tau,
+                                              freqs=self.freqs, tau_by_member=True)
+        icov = self.icov
+        if not diag:
+            cov = self.get_cov(time_inds=t_idx.tolist(), squeeze=False) if self.cov is not None else None
+            icov = self.get_icov(time_inds=t_idx.tolist(), squeeze=False) if self.icov is not None else None
+        elif icov is not None:
+            icov = icov.index_select(-2, torch.as_tensor(t_idx, device=icov.device))
+        vd = self if inplace else self.copy(copydata=False)
+        vd.setup_data(self.blnums, self.times[torch.as_tensor(t_idx)], self.freqs, pol=self.pol, data=data, flags=flags, cov=cov,
+                      cov_axis=self.cov_axis, icov=icov, history=self.history)
+        return vd
+
+    def time_average(self, time_inds=None, wgts=None, rephase=False, inplace=True):
+        """
+        Average time integrations together (dataset.py:1452-1566).  time_inds: list of index sequences into self.times,
+        one per output time (default: all times into one); a time in no entry is dropped, a time in several goes to the
+        last (the reference's rule).  wgts: weights; default self.icov when it holds inverse variances (cov_axis None),
+        else uniform.  rephase: rephase every member to the mean time of its bin (drift-scan data) before averaging.
+        Averaged times are the plain mean of the members; flags (set where every member is flagged), cov and icov
+        (1 / avg_cov.clip(1e-60); cov kept only if it was set) follow the reference.
+        Weights of the data's full shape (or none) with a diagonal covariance go through one launch of the fused kernel
+        (ops.vis_timeavg: phasor, weighting, the sums of data, weights and variances and the flags; fixed summation order,
+        bit-identical from run to run); any other input goes through average_data.  Differentiable with respect to the data
+        only: weights, times and cov receive no gradient.
+        """
+        from . import ops, telescope_model
+        Nt = self.Ntimes
+        if time_inds is None:
+            time_inds = [np.arange(Nt)]
+        Nbin = len(time_inds)
+        bins, index = time_bins(time_inds, Nt)
+        if wgts is None and self.icov is not None and self.cov_axis is None:
+            wgts = self.icov
+        cov = None
+        if self.cov_axis is None:
+            if self.cov is not None:
+                cov = self.cov
+            elif self.icov is not None:
+                cov = 1 / self.icov.clip(1e-60)
+        times = utils.tensor2numpy(self.times).astype(np.float64)
+        avg_times = np.array([times[b].mean() if len(b) else np.nan for b in bins])
+        tau = None
+        if rephase:
+            dtimes = np.where(index < Nbin, np.append(avg_times, 0.0)[index] - times, 0.0)
+            tau = self._rephase_tau(dtimes * 2 * np.pi / (SDAY_SEC / 86400.0))
+        if self.cov_axis is None and (wgts is None or tuple(wgts.shape) == tuple(self.data.shape)):
+            avg_data, _, avg_cov, avg_flags = ops.vis_timeavg(self.data, ops.TimeAvgPlan(bins, Nt), wgts=wgts, cov=cov,
+                                                              flags=self.flags, tau=tau, freqs=self.freqs)
+        else:
+            data = self.data
+            if tau is not None:
+                data = data * ops.rephase_phasor(tau.to(data.device), self.freqs, dtype=data.dtype)
+            truncate = bool((index == Nbin).any())
+            idx = torch.as_tensor(index, device=data.device)
+            avg_data, _, avg_cov = average_data(data, -2, idx, Nbin + int(truncate), wgts=wgts, cov=cov, truncate=truncate)
+            avg_flags = None
+            if self.flags is not None:
+                shape = list(avg_data.shape[-self.flags.ndim:])
+                shape[-2] = Nbin + 1
+                count = torch.zeros(shape, dtype=torch.int64, device=data.device)
+                count.index_add_(-2, idx, (~self.flags).to(torch.int64))
+                avg_flags = (count == 0)[..., :Nbin, :]
+        avg_icov = None
+        if self.icov is not None and avg_cov is not None:
+            avg_icov = 1 / avg_cov.clip(1e-60)
+        if self.cov is None:
+            avg_cov = None
+        vout = self if inplace else self.copy(copydata=False, copymeta=False)
+        vout.setup_data(self.blnums, torch.as_tensor(avg_times), vout.freqs, pol=self.pol, data=avg_data, flags=avg_flags,
+                        cov=avg_cov, icov=avg_icov, cov_axis=None, history=self.history)
+        return vout
+
     def _inflate_by_redundancy(self, new_bls, red_bl_inds, try_view=False):
         """
         new VisData whose baseline axis is self's indexed by red_bl_inds (one redundant-group index per
@@ -338,6 +460,42 @@ class VisData(TensorData):
         keep = [b for b in bls if bl2red[b] in mine]
         return self._inflate_by_redundancy(keep, [mine[bl2red[b]] for b in keep])
 
+
+
+SDAY_SEC = 86164.0905        # mean sidereal day [s] (the reference takes astropy.units.sday)
+
+
+def time_bins(time_inds, Nt):
+    """(bins, index) of VisData.time_average: index [Nt], the bin of every time by the reference's rule (a time listed in
+    several entries goes to the last; len(time_inds) marks a time in none, which is dropped) and bins, the ascending times of
+    every entry -- an empty entry is an empty bin.  Host numpy."""
+    Nbin = len(time_inds)
+    index = np.full(int(Nt), Nbin, dtype=np.int64)
+    for i, tinds in enumerate(time_inds):
+        tinds = np.asarray(tinds.cpu() if isinstance(tinds, torch.Tensor) else tinds)
+        if isinstance(tinds, np.ndarray) and tinds.dtype == object:
+            raise ValueError('time_inds entries must be integer sequences')
+        tinds = tinds.reshape(-1).astype(np.int64) if tinds.size else np.zeros(0, dtype=np.int64)
+        if tinds.size and (tinds.min() < -Nt or tinds.max() >= Nt):
+            raise IndexError('time index outside the %d times' % Nt)
+        index[tinds] = i
+    return [np.where(index == i)[0] for i in range(Nbin)], index
+
+
+def nearest_lst(lsts, self_lsts):
+    """(t_idx, dLST) of VisData.time_nn_interp by the reference's rule (dataset.py:1421-1438): both LST sets [rad] are
+    unwrapped across 2 pi (values below the first get 2 pi added when the last lies below the first), the targets are
+    lifted by 2 pi when they start below the data, every target takes the nearest data LST (the first of equals), and
+    dLST = target - selected.  Copies: the inputs are left as they are."""
+    lsts, self_lsts = np.array(lsts, dtype=np.float64).reshape(-1), np.array(self_lsts, dtype=np.float64).reshape(-1)
+    if lsts[-1] < lsts[0]:
+        lsts[lsts < lsts[0]] += 2 * np.pi
+    if self_lsts[-1] < self_lsts[0]:
+        self_lsts[self_lsts < self_lsts[0]] += 2 * np.pi
+    if lsts[0] < self_lsts[0]:
+        lsts += 2 * np.pi
+    t_idx = np.argmin(np.abs(self_lsts - lsts[:, None]), axis=1)
+    return t_idx, lsts - self_lsts[t_idx]
 
 
 def average_data(data, dim, index, N, wgts=None, cov=None, truncate=False):

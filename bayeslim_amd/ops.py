@@ -2628,3 +2628,171 @@ def redvis(vis, model, plan, undo=False):
     rime_redvis_bwd, whose summation order is fixed by the plan (bit-identical from run to run).  No CPU path.
     """
     return _RedVis.apply(vis, model, plan, -1 if undo else 1)
+
+
+# ---------------------------------------------------------------------------------------
+# LST alignment: rephasing, weighting and the average of the integrations of every bin in one pass (csrc/lstbin.hip)
+# ---------------------------------------------------------------------------------------
+class TimeAvgPlan:
+    """
+    Bin table of rime_vis_timeavg_fwd / rime_vis_timeavg_bwd, built with numpy on the host (no GPU needed), validated here on
+    the host copies and cached per device as int32 tensors.  bins: a list with the time indices of every bin (any integer
+    sequences; an empty entry is an empty bin); a time in no bin is dropped, a time may be in several bins or several times
+    in one.  Forward CSR: bin_ptr [Nbin + 1], members [Nmem]: the members of a bin are summed in the order given.  Transposed
+    table of the backward gather: t_ptr [Nt + 1], t_pos [Nmem] (the table positions that hold every time, ascending) and
+    pos_bin [Nmem] (the bin of every table position).  A member outside [0, Nt) is a ValueError.
+    """
+    def __init__(self, bins, Nt):
+        self.Nt, self.Nbin = int(Nt), len(bins)
+        if self.Nt < 0:
+            raise ValueError('Nt must not be negative')
+        rows = []
+        for b in bins:
+            b = np.asarray(b.cpu() if torch.is_tensor(b) else b).reshape(-1)
+            if b.size and not np.issubdtype(b.dtype, np.integer):
+                raise ValueError('time indices must be integers')
+            rows.append(b.astype(np.int64))
+        self.bin_ptr = np.zeros(self.Nbin + 1, dtype=np.int32)
+        if rows:
+            np.cumsum([r.size for r in rows], out=self.bin_ptr[1:])
+        members = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+        if members.size and (members.min() < 0 or members.max() >= self.Nt):
+            raise ValueError('time index outside [0, %d)' % self.Nt)
+        self.Nmem = int(members.size)
+        self.members = members.astype(np.int32)
+        self.pos_bin = np.repeat(np.arange(self.Nbin), np.diff(self.bin_ptr)).astype(np.int32)
+        self.t_ptr, self.t_pos = _csr(members, self.Nt) if self.Nt else (np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32))
+
+    def tables(self, device):
+        """dict of the five int32 tables on `device`, cached"""
+        key = str(torch.device(device))
+        tabs = self.__dict__.setdefault('_tabs', {})
+        if key not in tabs:
+            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous()
+                         for k in ('bin_ptr', 'members', 't_ptr', 't_pos', 'pos_bin')}
+        return tabs[key]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tabs', None)
+        return state
+
+
+def _host_ip(a):
+    return a.ctypes.data_as(_lib._ip)
+
+
+def _timeavg_tau(tau, freqs, plan, Nbl, Nf, by_member, dev):
+    if tau is None:
+        return None, None
+    if freqs is None:
+        raise ValueError('rephasing needs freqs')
+    tau = torch.as_tensor(tau, dtype=torch.float64).to(dev).contiguous()
+    fr = torch.as_tensor(freqs).detach().to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(tau.shape) != (Nbl, plan.Nmem if by_member else plan.Nt):
+        raise ValueError('tau of shape %s, expected %s' % (tuple(tau.shape), (Nbl, plan.Nmem if by_member else plan.Nt)))
+    if tuple(fr.shape) != (Nf,):
+        raise ValueError('freqs of shape %s, expected (%d,)' % (tuple(fr.shape), Nf))
+    return tau, fr
+
+
+class _VisTimeAvg(torch.autograd.Function):
+    """(avg, sum_w, avg_cov, avg_flag) of rime_vis_timeavg_fwd; backward: the gradient of the data alone, by
+    rime_vis_timeavg_bwd (weights, tau and cov receive no gradient)"""
+    @staticmethod
+    def forward(ctx, data, plan, wgts, cov, flags, tau, freqs, by_member):
+        _require_cuda(data, wgts, cov, flags)
+        assert data.is_complex() and data.ndim >= 3, 'complex data of shape (..., Nbl, Ntimes, Nfreqs)'
+        lead, (Nbl, Nt, Nf) = tuple(data.shape[:-3]), data.shape[-3:]
+        if Nt != plan.Nt:
+            raise ValueError('data of %d times, the plan has %d' % (Nt, plan.Nt))
+        Npp = int(np.prod(lead)) if lead else 1
+        d = data.detach().resolve_conj().contiguous()
+        code, rdt = _real_dtype(d)
+        dev = d.device
+
+        def full(x, dtype):
+            if x is None:
+                return None
+            x = x.detach()
+            if x.dtype != dtype:
+                x = x.to(dtype)
+            return x.expand(d.shape).contiguous()
+
+        w, c, fl = full(wgts, rdt), full(cov, rdt), full(flags, torch.bool)
+        tau, fr = _timeavg_tau(tau, freqs, plan, Nbl, Nf, by_member, dev)
+        T = plan.tables(dev)
+        oshape = lead + (Nbl, plan.Nbin, Nf)
+        avg = torch.empty(oshape, dtype=d.dtype, device=dev)
+        sum_w = torch.empty(oshape, dtype=rdt, device=dev)
+        avg_cov = torch.empty(oshape, dtype=rdt, device=dev) if c is not None else None
+        avg_flag = torch.empty(oshape, dtype=torch.bool, device=dev) if fl is not None else None
+        rc = lib.rime_vis_timeavg_fwd(code, _ptr(torch.view_as_real(d)), _ptr(w), _ptr(c), _ptr(fl), _ptr(tau), int(bool(by_member)),
+                                      _ptr(fr), _ptr(T['bin_ptr']), _ptr(T['members']), _host_ip(plan.bin_ptr),
+                                      _host_ip(plan.members), Npp, Nbl, Nt, Nf, plan.Nbin, plan.Nmem,
+                                      _ptr(torch.view_as_real(avg)), _ptr(sum_w), _ptr(avg_cov), _ptr(avg_flag), _stream())
+        check(rc, 'rime_vis_timeavg_fwd')
+        ctx.plan, ctx.by_member, ctx.shape, ctx.ddtype = plan, bool(by_member), tuple(d.shape), data.dtype
+        ctx.save_for_backward(w, sum_w, tau, fr)
+        outs = (avg, sum_w, avg_cov, avg_flag)
+        ctx.mark_non_differentiable(*[o for o in outs[1:] if o is not None])
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gavg, *unused):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        plan = ctx.plan
+        w, sum_w, tau, fr = ctx.saved_tensors
+        g = gavg.detach().resolve_conj().contiguous()
+        code, _ = _real_dtype(sum_w)
+        if g.dtype != (torch.complex64 if code == RIME_F32 else torch.complex128):
+            g = g.to(torch.complex64 if code == RIME_F32 else torch.complex128)
+        Nbl, Nt, Nf = ctx.shape[-3:]
+        Npp = int(np.prod(ctx.shape[:-3])) if len(ctx.shape) > 3 else 1
+        T = plan.tables(g.device)
+        gd = torch.empty(ctx.shape, dtype=g.dtype, device=g.device)
+        rc = lib.rime_vis_timeavg_bwd(code, _ptr(torch.view_as_real(g)), _ptr(w), _ptr(sum_w), _ptr(tau), int(ctx.by_member),
+                                      _ptr(fr), _ptr(T['t_ptr']), _ptr(T['t_pos']), _ptr(T['pos_bin']), _host_ip(plan.t_ptr),
+                                      _host_ip(plan.t_pos), _host_ip(plan.pos_bin), Npp, Nbl, Nt, Nf, plan.Nbin, plan.Nmem,
+                                      _ptr(torch.view_as_real(gd)), _stream())
+        check(rc, 'rime_vis_timeavg_bwd')
+        if gd.dtype != ctx.ddtype:
+            gd = gd.to(ctx.ddtype)
+        return (gd,) + (None,) * 7
+
+
+def vis_timeavg(data, plan, wgts=None, cov=None, flags=None, tau=None, freqs=None, tau_by_member=False):
+    """
+    (avg, sum_w, avg_cov, avg_flag) of the bins of `plan` (a TimeAvgPlan) in one launch of rime_vis_timeavg_fwd:
+        sum_w = sum w,  avg = sum w V exp(2 pi i freqs tau) / max(sum_w, 1e-40),  avg_cov = sum w^2 cov / max(sum_w, 1e-40)^2,
+        avg_flag = every member flagged
+    over the members of every bin in table order.  data (..., Nbl, Ntimes, Nfreqs) complex64 / complex128; wgts, cov (real)
+    and flags (bool) broadcast against it (None: uniform weights, no avg_cov, no avg_flag); tau float64 (Nbl, Ntimes), or
+    (Nbl, Nmem) -- one delay [s] per table position -- with tau_by_member (None: no rephasing), freqs (Nfreqs,) [Hz].
+    Differentiable once with respect to the DATA only: weights, tau and cov receive no gradient.  The summation order is
+    fixed by the plan (bit-identical from run to run).  No CPU path.
+    """
+    return _VisTimeAvg.apply(data, plan, wgts, cov, flags, tau, freqs, tau_by_member)
+
+
+def rephase_phasor(tau, freqs, dtype=torch.complex64):
+    """exp(2 pi i freqs tau) of shape tau.shape + (Nfreqs,) from the data-less mode of rime_vis_timeavg_fwd: tau float64
+    (Nbl, Ntimes) [s] on the GPU, the phase reduced in float64 before sine and cosine are taken in the precision of `dtype`"""
+    tau = torch.as_tensor(tau, dtype=torch.float64)
+    freqs = torch.as_tensor(freqs)
+    _require_cuda(tau, freqs)
+    assert tau.ndim == 2 and dtype in (torch.complex64, torch.complex128)
+    Nbl, Nt = tau.shape
+    Nf = freqs.numel()
+    plan = TimeAvgPlan(np.arange(Nt)[:, None], Nt)
+    tau, fr = _timeavg_tau(tau, freqs.reshape(-1), plan, Nbl, Nf, False, tau.device)
+    T = plan.tables(tau.device)
+    out = torch.empty((Nbl, Nt, Nf), dtype=dtype, device=tau.device)
+    code, _ = _real_dtype(out)
+    rc = lib.rime_vis_timeavg_fwd(code, _ptr(None), _ptr(None), _ptr(None), _ptr(None), _ptr(tau), 0, _ptr(fr), _ptr(T['bin_ptr']),
+                                  _ptr(T['members']), _host_ip(plan.bin_ptr), _host_ip(plan.members), 1, Nbl, Nt, Nf, Nt, Nt,
+                                  _ptr(torch.view_as_real(out)), _ptr(None), _ptr(None), _ptr(None), _stream())
+    check(rc, 'rime_vis_timeavg_fwd')
+    return out

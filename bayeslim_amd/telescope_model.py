@@ -132,6 +132,39 @@ def JD2LST(jd, longitude):
     return np.mod(gmst + longitude, 360.0)
 
 
+def rephase_tau(dlst, lat, blvecs):
+    """
+    Delay [s] by which a zenith-pointing drift-scan visibility is rephased when its fringe centre moves by dlst [rad] of
+    LST (the geometry of vis_rephase, reference telescope_model.py:594-645; Zhang et al. 2018, eq. 22):
+        s' = R_eq2top(-dlst, lat) R_top2eq(0, lat) z,    tau = b . (s' - z) / 2.99792458e8
+    dlst: scalar or (Nlst,); lat [deg]; blvecs (Nbl, 3) ENU [m].  Host arithmetic in float64 (Nbl x Nlst numbers): a float64
+    CPU tensor (Nbl, Nlst).  dlst = 0 gives 0; an east-west baseline at lat = 0 gives -b_E sin(dlst) / c.
+    """
+    H = -np.atleast_1d(np.asarray(utils.tensor2numpy(dlst) if isinstance(dlst, torch.Tensor) else dlst, dtype=np.float64))
+    d = float(lat) * np.pi / 180
+    b = np.asarray(utils.tensor2numpy(blvecs) if isinstance(blvecs, torch.Tensor) else blvecs, dtype=np.float64).reshape(-1, 3)
+    sH, sd, cd = np.sin(H), np.sin(d), np.cos(d)
+    ver = 2 * np.sin(H / 2) ** 2                             # 1 - cos H without cancellation: dlst = 0 gives exactly 0
+    # R_top2eq(0, lat) z = (cos lat, 0, sin lat); the rows of R_eq2top(H, lat) applied to it, minus z:
+    # (sin H cos lat, sin lat cos lat (1 - cos H), cos^2 lat cos H + sin^2 lat - 1)
+    sdiff = np.stack([sH * cd, sd * cd * ver, -cd * cd * ver])                            # (3, Nlst)
+    return torch.as_tensor(b @ sdiff / 2.99792458e8)
+
+
+def vis_rephase(dlst, lat, blvecs, freqs):
+    """
+    Rephasing tensor exp(2 pi i freqs tau) of shape (Nbl, Nlst, Nfreqs) that moves the fringe centre of zenith-pointing
+    drift-scan visibilities by dlst [rad] (reference telescope_model.py:594-645): tau from rephase_tau on the host, the phasor
+    from the data-less mode of the time-averaging kernel (ops.rephase_phasor), on the device of `freqs` (a GPU tensor; there
+    is no CPU path), complex128 for float64 freqs, else complex64.  VisData.lst_rephase / time_nn_interp / time_average
+    take tau alone and never materialise this tensor.
+    """
+    freqs = torch.as_tensor(freqs)
+    ops._require_cuda(freqs)
+    tau = rephase_tau(dlst, lat, blvecs).to(freqs.device)
+    return ops.rephase_phasor(tau, freqs, dtype=torch.complex128 if freqs.dtype == torch.float64 else torch.complex64)
+
+
 def eq2top(location, time, ra, dec):
     """
     Equatorial (ra, dec) [deg] -> topocentric (zen, az) [deg], az East of North, by a pure

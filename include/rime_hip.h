@@ -639,6 +639,45 @@ int rime_hmat_apply(int dtype, const void* tiles, int ntiles, const long long* r
                     double scalar, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * LST alignment of drift-scan visibilities (telescope_model.vis_rephase, VisData.lst_rephase / time_nn_interp /
+ * time_average; reference dataset.py:1363-1566, telescope_model.py:594-645): rephasing, weighting and the average of the
+ * integrations of every bin in one pass (csrc/lstbin.hip).  Tensors [Npp, Nbl, Nt, Nf] in, [Npp, Nbl, Nbin, Nf] out,
+ * channel fastest, contiguous, aligned to their element size only (a base off 16 bytes, or an Nf that is not a multiple of
+ * 16 / sizeof(T) channels, takes element accesses of the same elements: same bits); data / avg complex (interleaved T),
+ * wgts / cov / sum_w / avg_cov real T, flags / avg_flag one byte per element (0: unflagged).
+ * Bins: a CSR table bin_ptr [Nbin + 1], members [Nmem] (time indices of every bin, ascending table position is the order
+ * of summation); a time may be in no bin (dropped) or in several.  For every (p, b, bin k, f), over the table positions m
+ * of the bin with t = members[m]:
+ *     sum_w    = sum w[p, b, t, f]                                                   (w = 1 when wgts is null)
+ *     avg      = sum w V[p, b, t, f] exp(2 pi i freqs[f] tau[b, j]) / max(sum_w, 1e-40)
+ *     avg_cov  = sum w^2 cov[p, b, t, f] / max(sum_w, 1e-40)^2                       (cov and avg_cov both given or both null)
+ *     avg_flag = 1 where every member is flagged (an empty bin: 1)                   (flags and avg_flag both or neither)
+ * tau: DEVICE float64 [Nbl, Nt] with j = t, or, with tau_by_member = 1, [Nbl, Nmem] with j = m (one delay per table
+ * position: a time that serves several bins); null: no phasor is generated.  freqs: DEVICE float64 [Nf] (needed with tau).
+ * The product freqs[f] * tau is formed and reduced to [-1/2, 1/2] turns in float64, sine and cosine are taken in T.  data
+ * null: V = 1, i.e. with singleton bins and no weights avg is the phasor itself.  sum_w may be null (not written).
+ * rime_vis_timeavg_bwd: the gradient with respect to the data ONLY (weights, tau and cov receive none),
+ *     gdata[p, b, t, f] = sum over the table positions m holding t of
+ *                         w[p, b, t, f] conj(phasor) gavg[p, b, pos_bin[m], f] / max(sum_w[p, b, pos_bin[m], f], 1e-40)
+ * through the transposed table t_ptr [Nt + 1], t_pos [Nmem] (table positions of every time, ascending) and pos_bin [Nmem]
+ * (the bin of every table position); every element of gdata is written (0 for a time in no bin).  sum_w: as the forward wrote.
+ * No atomics, one summation chain per output element in table order: bit-reproducible.
+ * The *_host arguments are HOST copies of the tables; the kernels read the DEVICE ones.  Checked before any HIP call, on the
+ * host copies: RIME_EINVAL for an unknown dtype, a negative size, tau_by_member outside {0, 1}, a null avg / gavg / sum_w (bwd) /
+ * gdata / table, tau without freqs, cov or flags without their output (or the reverse), a table that does not start at 0,
+ * decreases or does not end at Nmem, a member outside [0, Nt), a t_pos outside [0, Nmem), a pos_bin outside [0, Nbin).  The
+ * device tables are not inspected by the host (the kernels skip entries that point outside).
+ * ------------------------------------------------------------------------------------- */
+int rime_vis_timeavg_fwd(int dtype, const void* data, const void* wgts, const void* cov, const void* flags, const double* tau,
+                         int tau_by_member, const double* freqs, const int* bin_ptr, const int* members,
+                         const int* bin_ptr_host, const int* members_host, int Npp, int Nbl, int Nt, int Nf, int Nbin, int Nmem,
+                         void* avg, void* sum_w, void* avg_cov, void* avg_flag, void* stream);
+int rime_vis_timeavg_bwd(int dtype, const void* gavg, const void* wgts, const void* sum_w, const double* tau,
+                         int tau_by_member, const double* freqs, const int* t_ptr, const int* t_pos, const int* pos_bin,
+                         const int* t_ptr_host, const int* t_pos_host, const int* pos_bin_host, int Npp, int Nbl, int Nt,
+                         int Nf, int Nbin, int Nmem, void* gdata, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
