@@ -96,7 +96,7 @@ extern "C" int rime_comm_destroy(void* comm)
 extern "C" int rime_comm_allgather_vis(void* comm, int dtype, const void* vis_local, void* vis_all,
                                        size_t complex_per_rank, void* stream)
 {
-    if (!comm || !vis_local || !vis_all || (dtype != RIME_F32 && dtype != RIME_F64)) return RIME_EINVAL;
+    if (!comm || !vis_local || !vis_all || !rime::real_dtype_ok(dtype)) return RIME_EINVAL;
     if (complex_per_rank == 0) return RIME_OK;
     Rccl& r = rccl();
     if (!r.ok) return RIME_EUNSUPPORTED;
@@ -107,7 +107,7 @@ extern "C" int rime_comm_allgather_vis(void* comm, int dtype, const void* vis_lo
 
 extern "C" int rime_comm_reduce_grads(void* comm, int dtype, void* grads, size_t count, void* stream)
 {
-    if (!comm || !grads || (dtype != RIME_F32 && dtype != RIME_F64)) return RIME_EINVAL;
+    if (!comm || !grads || !rime::real_dtype_ok(dtype)) return RIME_EINVAL;
     if (count == 0) return RIME_OK;
     Rccl& r = rccl();
     if (!r.ok) return RIME_EUNSUPPORTED;

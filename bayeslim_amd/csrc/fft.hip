@@ -313,7 +313,7 @@ extern "C" int rime_fft_apply(int dtype, const void* x, const void* tw, const vo
                               int nradix, int N, long long nlines, int inverse, int shift_in, int shift_out, double scale,
                               int epilogue, double start, double df, void* y, void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     if (N < 1 || N > FFT_MAXN || nlines < 0) return RIME_EINVAL;
     if (epilogue < 0 || epilogue > (FFT_ABS | FFT_PEAKNORM | FFT_SQUARE | FFT_PEAK)) return RIME_EINVAL;
     if ((inverse != 0 && inverse != 1) || (win_on_store != 0 && win_on_store != 1)) return RIME_EINVAL;

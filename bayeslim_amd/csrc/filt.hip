@@ -203,7 +203,7 @@ extern "C" int rime_filt_apply(int dtype, int wcplx, const void* x, const void* 
                                const int* tiles, int Ntile, int Npass, int Nfilt, int M, int K, int Nx, int Ny, long long Nlines,
                                double s, void* y, void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     if (wcplx != 0 && wcplx != 1) return RIME_EINVAL;
     if (M <= 0 || K <= 0 || Nx <= 0 || Ny <= 0 || Nfilt <= 0 || Nlines < 0 || Nlines > 0x7fffffffLL) return RIME_EINVAL;
     if (K > 0x3fffffff || Ntile < 0 || Npass < 0 || Npass > Ntile) return RIME_EINVAL;

@@ -719,7 +719,7 @@ static int fringe_common(bool backward, int dtype, const double* blvecs, const d
     if (Npp == 2 && cplx) return RIME_EUNSUPPORTED;
     if (sign != 1 && sign != -1) return RIME_EINVAL;
     if (mp_off[0] != 0 || mp_off[Nmp] != Nbl) return RIME_EINVAL;
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     FringeArgs A{};
     A.blvecs = blvecs; A.sdir = sdir; A.freqs = freqs; A.in = in; A.out = out; A.ws = ws;
     A.bl_order = bl_order;

@@ -19,10 +19,10 @@
 // lanes of the row (xor G / 2, ..., 1).  Transposed: wave w and row slot u run the chain over the stored rows
 // j = (64 / G) w + u, + 256 / G, ...; the 256 / G chains of an output are added in the order (w, u) ascending, w major.
 // Diagonal: d_i * x_i.  Every tile's sum s enters the accumulator as acc = fma(T(scale), s, acc).
-// A matrix whose base and leading dimension are multiples of 16 bytes is read with 16-byte loads; any other with element
-// loads of the SAME elements into the SAME registers (the branch is uniform across the tile), so the bits do not change.
+// A matrix whose base and leading dimension are multiples of 16 bytes is read with 16-byte loads, any other with element
+// loads (the rule of lane_vec.h; the branch is uniform across the tile), so the bits do not change.
 // Vector ALU only; the register arrays are indexed by unrolled loops only (no scratch memory).
-#include "rime_common.h"
+#include "lane_vec.h"
 
 namespace rime {
 
@@ -39,20 +39,13 @@ struct HmTile {                      // rime_hmat_tile of the header, 64 bytes
 };
 static_assert(sizeof(HmTile) == 64, "tile layout");
 
-template <typename T> struct HmVec;
-template <> struct HmVec<float>  { using type = float4;  static constexpr int W = 4; };
-template <> struct HmVec<double> { using type = double2; static constexpr int W = 2; };
-
-__device__ __forceinline__ void hm_unpack(const float4& q, float (&x)[4]) { x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w; }
-__device__ __forceinline__ void hm_unpack(const double2& q, double (&x)[2]) { x[0] = q.x; x[1] = q.y; }
-
 // W elements of a matrix row from column c on; columns at or beyond `end` read as 0
 template <typename T>
-__device__ __forceinline__ void hm_load(const T* __restrict__ row, long long c, long long end, bool vec, T (&a)[HmVec<T>::W])
+__device__ __forceinline__ void hm_load(const T* __restrict__ row, long long c, long long end, bool vec, T (&a)[Vec16<T>::W])
 {
-    constexpr int W = HmVec<T>::W;
+    constexpr int W = Vec16<T>::W;
     if (vec && c + W <= end) {
-        hm_unpack(*reinterpret_cast<const typename HmVec<T>::type*>(row + c), a);
+        unpack16(*reinterpret_cast<const typename Vec16<T>::type*>(row + c), a);
     } else {
 #pragma unroll
         for (int e = 0; e < W; ++e) a[e] = (c + e < end) ? row[c + e] : (T)0;
@@ -65,7 +58,7 @@ __global__ __launch_bounds__(HM_THREADS) void hmat_apply_kernel(const HmTile* __
                                                                const int* __restrict__ ids, const T* __restrict__ x, T* __restrict__ y,
                                                                T* __restrict__ scratch, int nrhs, int c0, T scalar, int accumulate)
 {
-    constexpr int W = HmVec<T>::W, CK = 64 * W * HM_G, BW = 64 * W;
+    constexpr int W = Vec16<T>::W, CK = 64 * W * HM_G, BW = 64 * W;
     __shared__ T yacc[HM_ROWS * NR];
     __shared__ T xs[CK * NR];
     __shared__ T red[HM_WAVES][BW * NR];
@@ -91,7 +84,7 @@ __global__ __launch_bounds__(HM_THREADS) void hmat_apply_kernel(const HmTile* __
         const T* A = static_cast<const T*>(tile.a);
         const T scale = (T)tile.scale;
         const long long ld = tile.ld;
-        const bool vec = ((reinterpret_cast<unsigned long long>(A) & 15ull) == 0) && (ld % W == 0);
+        const bool vec = aligned16(A) && (ld % W == 0);
 
         if (diag) {
             for (int o = tid; o < n * NR; o += HM_THREADS) {
@@ -172,8 +165,8 @@ __global__ __launch_bounds__(HM_THREADS) void hmat_apply_kernel(const HmTile* __
                     if (i < n) {
 #pragma unroll
                         for (int r = 0; r < NR; ++r) {
-                            T s = acc[k][r];
-#pragma unroll
+                            T s = acc[k][r];                      // wave_sum (lane_vec.h) written out: the call changes this
+#pragma unroll                                                    // kernel's register allocation
                             for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
                             if (lane == 0) yacc[(yb + i) * NR + r] = tfma<T>(scale, s, yacc[(yb + i) * NR + r]);
                         }
@@ -278,15 +271,15 @@ using namespace rime;
 
 extern "C" size_t rime_hmat_workspace(int dtype, long long scratch_rows, int nrhs)
 {
-    if ((dtype != RIME_F32 && dtype != RIME_F64) || scratch_rows < 0 || nrhs < 1 || scratch_rows > 0x0fffffffffffffffLL / nrhs) return 0;
-    return (size_t)scratch_rows * (size_t)nrhs * (dtype == RIME_F32 ? 4 : 8);
+    if (!real_dtype_ok(dtype) || scratch_rows < 0 || nrhs < 1 || scratch_rows > 0x0fffffffffffffffLL / nrhs) return 0;
+    return (size_t)scratch_rows * (size_t)nrhs * real_bytes(dtype);
 }
 
 extern "C" int rime_hmat_apply(int dtype, const void* tiles, int ntiles, const long long* ranges, const int* tile_ids,
                                const int* stage_first, int nstages, long long scratch_rows, const void* x, void* y, int nrhs,
                                double scalar, int accumulate, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     if (ntiles < 0 || nstages < 1 || nstages > HM_MAXSTAGES || nrhs < 1 || scratch_rows < 0) return RIME_EINVAL;
     if (scratch_rows > 0x0fffffffffffffffLL / nrhs) return RIME_EINVAL;
     if (!ranges || !stage_first || !x || !y || (ntiles > 0 && (!tiles || !tile_ids))) return RIME_EINVAL;

@@ -6,11 +6,8 @@
 // with eps (step size per element) and c (diagonal Cholesky factor of the covariance) each optional (null: ones).  A trajectory
 // of N leapfrog steps is N + 1 launches: (kick, drift) = (1/2, 1), (1, 1) x (N - 1), (1/2, 0) with the energy.
 //
-// The layout, the loads and the reduction are those of lbfgs.hip, restated here under the prefix hm_: a lane holds HM_BYTES = 64
-// bytes of every vector it touches, as four 16-byte groups 256 groups apart: E = 64 / sizeof(T) elements per lane, SPAN = 256 E
-// elements per work-group and chunk.  A vector whose base is 16-byte aligned is read and written with 16-byte accesses; any
-// other base takes element accesses of the SAME elements from and into the SAME registers (the branch is uniform across the
-// launch), so every bit of the result is independent of alignment.  There is no misaligned vector access.
+// The vectors are held in the strided lane layout of lane_vec.h (HMC_BYTES = 64 bytes per lane as HMC_GROUPS = 4 groups); the
+// 16-byte / element branch is uniform across the launch.
 //
 // Energy: the per-lane chain of E fused multiply-adds in T (ascending element index), then float64: butterfly across the wave,
 // accumulation over the chunks of a work-group (chunk b, b + gridDim.x, ... in that order) by lane 0 of each wave, waves added
@@ -18,100 +15,58 @@
 // (lane l takes partials l, l + 64, ..., then the same butterfly) and halves the sum.  No atomics; the order is a function of
 // (N, dtype) alone: bit-reproducible, and the same for the energy-only pass and the pass fused with the last kick.
 // Vector ALU only; the register arrays are indexed by unrolled loops only (no scratch).
-#include "rime_common.h"
+#include "lane_vec.h"
 
 namespace rime {
 
-constexpr int HM_THREADS = 256, HM_BYTES = 64, HM_GROUPS = 4, HM_MAXBLOCKS = 1024;
+constexpr int HMC_THREADS = 256, HMC_BYTES = 64, HMC_GROUPS = 4, HMC_MAXBLOCKS = 1024;
 
-template <typename T> struct HmVec;
-template <> struct HmVec<float>  { using type = float4;  static constexpr int W = 4; };
-template <> struct HmVec<double> { using type = double2; static constexpr int W = 2; };
-
-__device__ __forceinline__ void hm_unpack(const float4& v, float (&x)[4]) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-__device__ __forceinline__ void hm_unpack(const double2& v, double (&x)[2]) { x[0] = v.x; x[1] = v.y; }
-__device__ __forceinline__ float4 hm_pack(const float (&x)[4]) { return float4{x[0], x[1], x[2], x[3]}; }
-__device__ __forceinline__ double2 hm_pack(const double (&x)[2]) { return double2{x[0], x[1]}; }
-
-__device__ __forceinline__ bool hm_aligned(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; }
-
-// the E elements of this lane of the chunk starting at c0: group g covers c0 + (g * 256 + tid) * W ... + W - 1; elements at or
-// beyond N read as 0.  vec: the base is 16-byte aligned (c0 and the group offsets are multiples of W, so every group is)
+// the strided layout of lane_vec.h at this file's geometry
 template <typename T>
-__device__ __forceinline__ void hm_load(const T* p, long long c0, long long N, bool vec, T (&x)[HM_BYTES / sizeof(T)])
+__device__ __forceinline__ void hmc_load(const T* p, long long c0, long long N, bool vec, T (&x)[HMC_BYTES / sizeof(T)])
 {
-    constexpr int W = HmVec<T>::W;
-#pragma unroll
-    for (int g = 0; g < HM_GROUPS; ++g) {
-        const long long e = c0 + (long long)(g * HM_THREADS + (int)threadIdx.x) * W;
-        T t[W];
-        if (vec && e + W <= N) {
-            hm_unpack(*reinterpret_cast<const typename HmVec<T>::type*>(p + e), t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i) t[i] = (e + i < N) ? p[e + i] : (T)0;
-        }
-#pragma unroll
-        for (int i = 0; i < W; ++i) x[g * W + i] = t[i];
-    }
+    lane_load<T, HMC_THREADS, HMC_GROUPS>(p, c0, N, vec, x);
 }
 
 template <typename T>
-__device__ __forceinline__ void hm_store(T* p, long long c0, long long N, bool vec, const T (&x)[HM_BYTES / sizeof(T)])
+__device__ __forceinline__ void hmc_store(T* p, long long c0, long long N, bool vec, const T (&x)[HMC_BYTES / sizeof(T)])
 {
-    constexpr int W = HmVec<T>::W;
-#pragma unroll
-    for (int g = 0; g < HM_GROUPS; ++g) {
-        const long long e = c0 + (long long)(g * HM_THREADS + (int)threadIdx.x) * W;
-        T t[W];
-#pragma unroll
-        for (int i = 0; i < W; ++i) t[i] = x[g * W + i];
-        if (vec && e + W <= N) {
-            *reinterpret_cast<typename HmVec<T>::type*>(p + e) = hm_pack(t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i)
-                if (e + i < N) p[e + i] = t[i];
-        }
-    }
+    lane_store<T, HMC_THREADS, HMC_GROUPS>(p, c0, N, vec, x);
 }
 
 // sum of squares: the lane's chain in T, then float64 across the wave (every lane ends with the wave's sum)
 template <typename T>
-__device__ __forceinline__ double hm_sumsq(const T (&z)[HM_BYTES / sizeof(T)])
+__device__ __forceinline__ double hmc_sumsq(const T (&z)[HMC_BYTES / sizeof(T)])
 {
-    constexpr int E = HM_BYTES / sizeof(T);
+    constexpr int E = HMC_BYTES / sizeof(T);
     T c = (T)0;
 #pragma unroll
     for (int i = 0; i < E; ++i) c = tfma<T>(z[i], z[i], c);
-    double s = (double)c;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
+    return wave_sum((double)c);
 }
 
 // q, p in place; g, eps, c read only; null pointers as in the header.  partial [gridDim.x] when want_energy
 template <typename T>
-__global__ __launch_bounds__(HM_THREADS) void hmc_step_kernel(T* q, T* p, const T* __restrict__ g, const T* __restrict__ eps,
+__global__ __launch_bounds__(HMC_THREADS) void hmc_step_kernel(T* q, T* p, const T* __restrict__ g, const T* __restrict__ eps,
                                                               const T* __restrict__ c, T kick, T drift, int want_energy,
                                                               long long N, long long nchunks, double* __restrict__ partial)
 {
-    constexpr int E = HM_BYTES / sizeof(T);
-    constexpr long long SPAN = (long long)HM_THREADS * E;
-    __shared__ double acc[HM_THREADS / 64];
+    constexpr int E = HMC_BYTES / sizeof(T);
+    constexpr long long SPAN = (long long)HMC_THREADS * E;
+    __shared__ double acc[HMC_THREADS / 64];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const bool do_kick = kick != (T)0, do_drift = drift != (T)0;
-    const bool q_vec = hm_aligned(q), p_vec = hm_aligned(p), g_vec = hm_aligned(g), e_vec = hm_aligned(eps), c_vec = hm_aligned(c);
+    const bool q_vec = aligned16(q), p_vec = aligned16(p), g_vec = aligned16(g), e_vec = aligned16(eps), c_vec = aligned16(c);
     double mine = 0.0;                                       // lane 0 of a wave: the wave's sum over this work-group's chunks
     for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         const long long c0 = chunk * SPAN;
         T xp[E], xe[E], xc[E];
-        hm_load<T>(p, c0, N, p_vec, xp);
-        if (eps != nullptr) hm_load<T>(eps, c0, N, e_vec, xe);
-        if (c != nullptr) hm_load<T>(c, c0, N, c_vec, xc);
+        hmc_load<T>(p, c0, N, p_vec, xp);
+        if (eps != nullptr) hmc_load<T>(eps, c0, N, e_vec, xe);
+        if (c != nullptr) hmc_load<T>(c, c0, N, c_vec, xc);
         if (do_kick) {
             T xg[E];
-            hm_load<T>(g, c0, N, g_vec, xg);
+            hmc_load<T>(g, c0, N, g_vec, xg);
             if (eps != nullptr) {
 #pragma unroll
                 for (int i = 0; i < E; ++i) xp[i] = tfma<T>(-(kick * xe[i]), xg[i], xp[i]);
@@ -119,7 +74,7 @@ __global__ __launch_bounds__(HM_THREADS) void hmc_step_kernel(T* q, T* p, const 
 #pragma unroll
                 for (int i = 0; i < E; ++i) xp[i] = tfma<T>(-kick, xg[i], xp[i]);
             }
-            hm_store<T>(p, c0, N, p_vec, xp);
+            hmc_store<T>(p, c0, N, p_vec, xp);
         }
         T z[E];                                              // c o p
         if (c != nullptr) {
@@ -131,16 +86,16 @@ __global__ __launch_bounds__(HM_THREADS) void hmc_step_kernel(T* q, T* p, const 
         }
         if (do_drift) {
             T xq[E];
-            hm_load<T>(q, c0, N, q_vec, xq);
+            hmc_load<T>(q, c0, N, q_vec, xq);
 #pragma unroll
             for (int i = 0; i < E; ++i) {
                 const T de = eps != nullptr ? drift * xe[i] : drift;
                 const T v = c != nullptr ? xc[i] * z[i] : z[i];
                 xq[i] = tfma<T>(de, v, xq[i]);
             }
-            hm_store<T>(q, c0, N, q_vec, xq);
+            hmc_store<T>(q, c0, N, q_vec, xq);
         }
-        if (want_energy) mine += hm_sumsq<T>(z);
+        if (want_energy) mine += hmc_sumsq<T>(z);
     }
     if (want_energy) {
         if (lane == 0) acc[wave] = mine;
@@ -155,25 +110,20 @@ __global__ __launch_bounds__(64) void hmc_energy_final_kernel(const double* __re
     const int lane = threadIdx.x;
     double s = 0.0;
     for (int b = lane; b < nb; b += 64) s += partial[b];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+    s = wave_sum(s);
     if (lane == 0) energy[0] = 0.5 * s;
 }
 
-static long long hm_chunks(long long N, int dtype)
-{
-    const long long span = (long long)HM_THREADS * (HM_BYTES / (dtype == RIME_F32 ? 4 : 8));
-    return (N + span - 1) / span;
-}
+static long long hmc_chunks(long long N, int dtype) { return lane_chunks(N, dtype, HMC_THREADS, HMC_BYTES); }
 
 template <typename T>
-static int hm_step(long long N, void* q, void* p, const void* g, const void* eps, const void* c, double kick, double drift,
+static int hmc_step(long long N, void* q, void* p, const void* g, const void* eps, const void* c, double kick, double drift,
                    double* energy, double* part, hipStream_t st, int dtype)
 {
-    const long long nchunks = hm_chunks(N, dtype);
-    const int nb = (int)std::min<long long>(nchunks, HM_MAXBLOCKS);
+    const long long nchunks = hmc_chunks(N, dtype);
+    const int nb = (int)std::min<long long>(nchunks, HMC_MAXBLOCKS);
     if (nb > 0)
-        hipLaunchKernelGGL((hmc_step_kernel<T>), dim3((unsigned)nb), dim3(HM_THREADS), 0, st, (T*)q, (T*)p, (const T*)g, (const T*)eps,
+        hipLaunchKernelGGL((hmc_step_kernel<T>), dim3((unsigned)nb), dim3(HMC_THREADS), 0, st, (T*)q, (T*)p, (const T*)g, (const T*)eps,
                            (const T*)c, (T)kick, (T)drift, energy != nullptr ? 1 : 0, N, nchunks, part);
     if (energy != nullptr)
         hipLaunchKernelGGL(hmc_energy_final_kernel, dim3(1), dim3(64), 0, st, (const double*)part, nb, energy);
@@ -188,14 +138,14 @@ using namespace rime;
 extern "C" size_t rime_hmc_workspace(long long N)
 {
     if (N < 0 || N > 0x3fffffffffffffffLL) return 0;
-    const long long nb = std::max<long long>(1, std::min<long long>(hm_chunks(N, RIME_F64), HM_MAXBLOCKS));
+    const long long nb = std::max<long long>(1, std::min<long long>(hmc_chunks(N, RIME_F64), HMC_MAXBLOCKS));
     return (size_t)nb * sizeof(double);
 }
 
 extern "C" int rime_hmc_step(int dtype, long long N, void* q, void* p, const void* g, const void* eps, const void* c, double kick,
                              double drift, double* energy, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if ((dtype != RIME_F32 && dtype != RIME_F64) || N < 0 || N > 0x3fffffffffffffffLL || !p) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype) || N < 0 || N > 0x3fffffffffffffffLL || !p) return RIME_EINVAL;
     if (!(kick == kick) || !(drift == drift)) return RIME_EINVAL;                      // NaN flags
     if ((kick != 0.0 && !g) || (drift != 0.0 && !q)) return RIME_EINVAL;
     if (energy != nullptr && (!workspace || workspace_bytes < rime_hmc_workspace(N))) return RIME_EWORKSPACE;
@@ -203,6 +153,6 @@ extern "C" int rime_hmc_step(int dtype, long long N, void* q, void* p, const voi
     if (dtype == RIME_F32 && ((kick != 0.0 && (float)kick == 0.0f) || (drift != 0.0 && (float)drift == 0.0f))) return RIME_EINVAL;
     if (kick == 0.0 && drift == 0.0 && energy == nullptr) return RIME_OK;               // nothing to do
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == RIME_F32 ? hm_step<float>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, st, dtype)
-                             : hm_step<double>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, st, dtype);
+    return dtype == RIME_F32 ? hmc_step<float>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, st, dtype)
+                             : hmc_step<double>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, st, dtype);
 }

@@ -318,11 +318,11 @@ extern "C" int rime_interp_scatter_rows_bwd(int dtype, int is_complex, const voi
 {
     // csr_src may be NULL when the index is EMPTY (every weight 0: csr_ptr is all zeros and no entry is read): the result is 0
     if (!gout || !csr_ptr || !wgts || !gm || R <= 0 || Npb <= 0 || gout_stride <= 0) return RIME_EINVAL;
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     constexpr int RB = 8;
     // rows beyond one grid's reach (65535 x RB) go to further launches on row-offset pointers (was RIME_EUNSUPPORTED)
-    const size_t esz = (dtype == RIME_F32 ? 4 : 8) * (is_complex ? 2 : 1);
+    const size_t esz = real_bytes(dtype) * (is_complex ? 2 : 1);
     const int chunk = 65535 * RB;
     for (int r0 = 0; r0 < R; r0 += chunk) {
         const int Rc = R - r0 < chunk ? R - r0 : chunk;
@@ -704,7 +704,7 @@ extern "C" int rime_beam_sky_fwd(int dtype, const void* bmap, const void* sky, c
 
 extern "C" size_t rime_beam_sky_bwd_workspace(int dtype, int R, int Npix, int Nt)
 {
-    if ((dtype != RIME_F32 && dtype != RIME_F64) || R <= 0 || Npix <= 0 || Nt <= 0) return 0;
+    if (!real_dtype_ok(dtype) || R <= 0 || Npix <= 0 || Nt <= 0) return 0;
     const int S = sky_grad_splits(R, Npix, Nt);
     return S > 1 ? (size_t)S * R * Npix * (dtype == RIME_F64 ? 8 : 4) : 0;
 }

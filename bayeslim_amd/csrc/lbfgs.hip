@@ -5,11 +5,8 @@
 // and one pass for the combination (rime_lbfgs_combine), instead of 4 m dependent vector operations.
 //
 // The history is two device tables of m row addresses (oldest first); every address is a contiguous N-vector of T, aligned to
-// sizeof(T) only.  A lane holds LB_BYTES = 64 bytes of every vector it touches, as four 16-byte groups 256 groups apart (a
-// wave's loads of one group index are contiguous): E = 64 / sizeof(T) elements per lane, SPAN = 256 E elements per work-group.
-// A vector whose base is 16-byte aligned is read with 16-byte loads; any other base takes element loads of the SAME elements
-// into the SAME registers (the branch is uniform across the launch for v, d and r, across the wave for a row), so the
-// arithmetic, its order and hence every bit of the result do not depend on alignment.  There is no misaligned vector load.
+// sizeof(T) only.  The vectors are held in the strided lane layout of lane_vec.h (LB_BYTES = 64 bytes per lane as LB_GROUPS = 4
+// groups); the 16-byte / element branch is uniform across the launch for v, d and r, across the wave for a row.
 //
 // rime_lbfgs_dots, per row j and chunk: the per-lane chains of E fused multiply-adds in T (ascending element index), then
 // float64: butterfly across the wave, accumulation over the chunks of a work-group (chunk c, c + gridDim.x, ... in that
@@ -18,62 +15,17 @@
 // butterfly).  No atomics; the order is a function of (N, dtype) alone: bit-reproducible, and the same for a launch with and
 // without the new-pair index k.  Rows are processed in groups of LB_ROWS over gridDim.y.
 // Vector ALU only; the register arrays are indexed by unrolled loops only (no scratch).
-#include "rime_common.h"
+#include "lane_vec.h"
 
 namespace rime {
 
 constexpr int LB_THREADS = 256, LB_BYTES = 64, LB_GROUPS = 4, LB_ROWS = 128, LB_MAXBLOCKS = 1024;
 
-template <typename T> struct LbVec;
-template <> struct LbVec<float>  { using type = float4;  static constexpr int W = 4; };
-template <> struct LbVec<double> { using type = double2; static constexpr int W = 2; };
-
-__device__ __forceinline__ void lb_unpack(const float4& q, float (&x)[4]) { x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w; }
-__device__ __forceinline__ void lb_unpack(const double2& q, double (&x)[2]) { x[0] = q.x; x[1] = q.y; }
-__device__ __forceinline__ float4 lb_pack(const float (&x)[4]) { return float4{x[0], x[1], x[2], x[3]}; }
-__device__ __forceinline__ double2 lb_pack(const double (&x)[2]) { return double2{x[0], x[1]}; }
-
-__device__ __forceinline__ bool lb_aligned(const void* p) { return (reinterpret_cast<unsigned long long>(p) & 15ull) == 0; }
-
-// the E elements of this lane of the chunk starting at c0: group g covers c0 + (g * 256 + tid) * W ... + W - 1; elements at or
-// beyond N read as 0.  vec: the base is 16-byte aligned (c0 and the group offsets are multiples of W, so every group is)
+// the strided layout of lane_vec.h at this file's geometry
 template <typename T>
-__device__ __forceinline__ void lb_load(const T* __restrict__ p, long long c0, long long N, bool vec, T (&x)[LB_BYTES / sizeof(T)])
+__device__ __forceinline__ void lb_load(const T* p, long long c0, long long N, bool vec, T (&x)[LB_BYTES / sizeof(T)])
 {
-    constexpr int W = LbVec<T>::W;
-#pragma unroll
-    for (int g = 0; g < LB_GROUPS; ++g) {
-        const long long e = c0 + (long long)(g * LB_THREADS + (int)threadIdx.x) * W;
-        T t[W];
-        if (vec && e + W <= N) {
-            lb_unpack(*reinterpret_cast<const typename LbVec<T>::type*>(p + e), t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i) t[i] = (e + i < N) ? p[e + i] : (T)0;
-        }
-#pragma unroll
-        for (int i = 0; i < W; ++i) x[g * W + i] = t[i];
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ void lb_store(T* __restrict__ p, long long c0, long long N, bool vec, const T (&x)[LB_BYTES / sizeof(T)])
-{
-    constexpr int W = LbVec<T>::W;
-#pragma unroll
-    for (int g = 0; g < LB_GROUPS; ++g) {
-        const long long e = c0 + (long long)(g * LB_THREADS + (int)threadIdx.x) * W;
-        T t[W];
-#pragma unroll
-        for (int i = 0; i < W; ++i) t[i] = x[g * W + i];
-        if (vec && e + W <= N) {
-            *reinterpret_cast<typename LbVec<T>::type*>(p + e) = lb_pack(t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i)
-                if (e + i < N) p[e + i] = t[i];
-        }
-    }
+    lane_load<T, LB_THREADS, LB_GROUPS>(p, c0, N, vec, x);
 }
 
 // the lane's chain in T, then float64 across the wave (every lane ends with the wave's sum)
@@ -84,10 +36,7 @@ __device__ __forceinline__ double lb_dot(const T (&a)[LB_BYTES / sizeof(T)], con
     T c = (T)0;
 #pragma unroll
     for (int i = 0; i < E; ++i) c = tfma<T>(a[i], b[i], c);
-    double s = (double)c;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    return s;
+    return wave_sum((double)c);
 }
 
 // partial [gridDim.x][m][NQ]: NQ = 2 (s_j.v, y_j.(d o v)) or, with a new pair k, 5 (+ s_j.y_k, y_j.s_k, y_j.(d o y_k))
@@ -103,10 +52,10 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_dots_kernel(const T* const* 
     const int r0 = blockIdx.y * LB_ROWS, nr = min(LB_ROWS, m - r0);
     for (int o = lane; o < nr * NQ; o += 64) acc[wave][o] = 0.0;
     __syncthreads();
-    const bool v_vec = lb_aligned(v), d_vec = lb_aligned(d);
+    const bool v_vec = aligned16(v), d_vec = aligned16(d);
     const T* sk = HASK ? S[k] : nullptr;
     const T* yk = HASK ? Y[k] : nullptr;
-    const bool sk_vec = lb_aligned(sk), yk_vec = lb_aligned(yk);
+    const bool sk_vec = aligned16(sk), yk_vec = aligned16(yk);
     for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         const long long c0 = chunk * SPAN;
         T xv[E], xdv[E], xsk[E], xyk[E], xdyk[E];
@@ -131,8 +80,8 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_dots_kernel(const T* const* 
             const T* sj = S[r0 + j];
             const T* yj = Y[r0 + j];
             T xs[E], xy[E];
-            lb_load<T>(sj, c0, N, lb_aligned(sj), xs);
-            lb_load<T>(yj, c0, N, lb_aligned(yj), xy);
+            lb_load<T>(sj, c0, N, aligned16(sj), xs);
+            lb_load<T>(yj, c0, N, aligned16(yj), xy);
             double p[NQ];
             p[0] = lb_dot<T>(xs, xv);
             p[1] = lb_dot<T>(xy, xdv);
@@ -160,8 +109,7 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_dots_final_kernel(const doub
     if (o >= m * NQ) return;                                  // whole waves leave together
     double s = 0.0;
     for (int b = lane; b < nb; b += 64) s += partial[(long long)b * m * NQ + o];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+    s = wave_sum(s);
     if (lane == 0) out[(long long)(o % NQ) * m + o / NQ] = s;
 }
 
@@ -176,19 +124,19 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_combine_kernel(const T* cons
     constexpr int E = LB_BYTES / sizeof(T);
     const long long c0 = (long long)blockIdx.x * LB_THREADS * E;
     T q[E];
-    lb_load<T>(v, c0, N, lb_aligned(v), q);
+    lb_load<T>(v, c0, N, aligned16(v), q);
     for (int j = 0; j < m; ++j) {
         const T* yj = Y[j];
         const T na = (T)(-a[j]);
         T x[E];
-        lb_load<T>(yj, c0, N, lb_aligned(yj), x);
+        lb_load<T>(yj, c0, N, aligned16(yj), x);
 #pragma unroll
         for (int i = 0; i < E; ++i) q[i] = tfma<T>(na, x[i], q[i]);
     }
     const T g = (T)gamma;
     if (d != nullptr) {
         T x[E];
-        lb_load<T>(d, c0, N, lb_aligned(d), x);
+        lb_load<T>(d, c0, N, aligned16(d), x);
 #pragma unroll
         for (int i = 0; i < E; ++i) q[i] = (g * x[i]) * q[i];
     } else {
@@ -199,23 +147,19 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_combine_kernel(const T* cons
         const T* sj = S[j];
         const T bj = (T)b[j];
         T x[E];
-        lb_load<T>(sj, c0, N, lb_aligned(sj), x);
+        lb_load<T>(sj, c0, N, aligned16(sj), x);
 #pragma unroll
         for (int i = 0; i < E; ++i) q[i] = tfma<T>(bj, x[i], q[i]);
     }
-    lb_store<T>(r, c0, N, lb_aligned(r), q);
+    lane_store<T, LB_THREADS, LB_GROUPS>(r, c0, N, aligned16(r), q);
 }
 
-// chunks of the dots pass; the workspace is sized for the smaller span (float64) so that it serves either dtype
-static long long lb_chunks(long long N, int dtype)
-{
-    const long long span = (long long)LB_THREADS * (LB_BYTES / (dtype == RIME_F32 ? 4 : 8));
-    return (N + span - 1) / span;
-}
+// chunks of a pass; the workspace is sized for the smaller span (float64) so that it serves either dtype
+static long long lb_chunks(long long N, int dtype) { return lane_chunks(N, dtype, LB_THREADS, LB_BYTES); }
 
 static bool lb_bad(int dtype, const void* s_rows, const void* y_rows, int m, long long N)
 {
-    return (dtype != RIME_F32 && dtype != RIME_F64) || m < 1 || N < 1 || N > 0x3fffffffffffffffLL || !s_rows || !y_rows;
+    return !real_dtype_ok(dtype) || m < 1 || N < 1 || N > 0x3fffffffffffffffLL || !s_rows || !y_rows;
 }
 
 template <typename T>

@@ -319,7 +319,7 @@ extern "C" int rime_lm_apply(int dtype, int xcplx, int mcplx, int out_real, cons
                              long long m_ks, const int* idx, const void* pre, const void* post, long long O, int K, int K_in,
                              int R, long long I, void* y, void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     if ((xcplx != 0 && xcplx != 1) || (mcplx != 0 && mcplx != 1) || (out_real != 0 && out_real != 1)) return RIME_EINVAL;
     if (out_real && !xcplx) return RIME_EINVAL;               // Re(M x) of a real x is Re(M) x: the caller passes Re(M)
     if (K <= 0 || R <= 0 || O <= 0 || I <= 0) return RIME_EINVAL;

@@ -13,107 +13,59 @@
 // the fringe kernels, fringe.hip; rephasing phases reach tens of turns).  Sums in T, one chain per output element, ascending
 // table position: no atomics, no communication between lanes, the bits are a function of the inputs and the table alone.
 //
-// Layout: a lane owns LB_BYTES = 16 bytes of a real row = CH = 16 / sizeof(T) consecutive channels (4 in float32, 2 in float64)
+// Layout: a lane owns TA_BYTES = 16 bytes of a real row = CH = 16 / sizeof(T) consecutive channels (4 in float32, 2 in float64)
 // of one (p, b, k): 32 bytes of data, 16 of weights and of variances, CH flag bytes per member.  Consecutive lanes take
 // consecutive channel groups, then the next bin / baseline / pol entry (the flat index runs over [p][b][k][channel group]),
 // so a work-group of 256 lanes spans 256 CH channels and short channel axes are filled up with further rows.  A launch
 // whose tensors all have 16-byte aligned bases, with Nf a multiple of CH (every row then starts aligned), reads and writes
-// with 16-byte accesses (the VEC instantiation, chosen on the host); any other takes element accesses of the SAME elements
-// into the SAME registers and the same arithmetic: the bits do not depend on alignment and there is no misaligned vector access.  Flags are bytes, read and written one by one.
+// with 16-byte accesses (the VEC instantiation, chosen on the host); any other takes element accesses (the contiguous-row
+// layout of lane_vec.h): the bits do not depend on alignment.  Flags are bytes, read and written one by one.
 //
 // Backward (data only): gV[p, b, t, f] = sum over the table positions m that hold t (transposed table, built on the host,
 // ascending m) of  w[p, b, t, f] conj(phasor) g_avg[p, b, k(m), f] / max(sum_w[p, b, k(m), f], 1e-40),  one lane per
 // (p, b, t, channel group), every element of gV written once (0 for a time in no bin).  Weights, tau and cov get no gradient.
 // Table entries are clamped / skipped in the kernels, never followed outside the tensors; the host checks them beforehand.
 // Vector ALU only.
-#include "rime_common.h"
+#include "lane_vec.h"
 #include <initializer_list>
 
 namespace rime {
 
-constexpr int LB_THREADS = 256, LB_BYTES = 16, LB_MAXBLOCKS = 1 << 20;
-
-template <typename T> struct LbVec;
-template <> struct LbVec<float>  { using type = float4;  static constexpr int W = 4; };
-template <> struct LbVec<double> { using type = double2; static constexpr int W = 2; };
-
-__device__ __forceinline__ void lb_unpack(const float4& v, float* x) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
-__device__ __forceinline__ void lb_unpack(const double2& v, double* x) { x[0] = v.x; x[1] = v.y; }
-__device__ __forceinline__ float4 lb_pack(const float* x) { return float4{x[0], x[1], x[2], x[3]}; }
-__device__ __forceinline__ double2 lb_pack(const double* x) { return double2{x[0], x[1]}; }
+constexpr int TA_THREADS = 256, TA_BYTES = 16, TA_MAXBLOCKS = 1 << 20;
 
 // the 16-byte form serves a launch whose rows all start on 16 bytes: every tensor given has an aligned base (null counts as
 // aligned) and Nf is a multiple of CH
-static bool lb_vec(int dtype, long long Nf, std::initializer_list<const void*> ptrs)
+static bool ta_vec(int dtype, long long Nf, std::initializer_list<const void*> ptrs)
 {
-    if (Nf % (LB_BYTES / (dtype == RIME_F32 ? 4 : 8)) != 0) return false;
+    if (Nf % (TA_BYTES / real_bytes(dtype)) != 0) return false;
     for (const void* p : ptrs)
-        if ((reinterpret_cast<unsigned long long>(p) & 15ull) != 0) return false;
+        if (!aligned16(p)) return false;
     return true;
-}
-
-// N reals (N a multiple of W) starting at element e; those at or beyond nvalid read as 0.  vec: e is a multiple of W off a
-// 16-byte aligned base and all N are valid
-template <typename T, int N>
-__device__ __forceinline__ void lb_load(const T* p, size_t e, int nvalid, bool vec, T (&x)[N])
-{
-    constexpr int W = LbVec<T>::W;
-#pragma unroll
-    for (int g = 0; g < N / W; ++g) {
-        T t[W];
-        if (vec) {
-            lb_unpack(*reinterpret_cast<const typename LbVec<T>::type*>(p + e + g * W), t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i) t[i] = (g * W + i < nvalid) ? p[e + g * W + i] : (T)0;
-        }
-#pragma unroll
-        for (int i = 0; i < W; ++i) x[g * W + i] = t[i];
-    }
-}
-
-template <typename T, int N>
-__device__ __forceinline__ void lb_store(T* p, size_t e, int nvalid, bool vec, const T (&x)[N])
-{
-    constexpr int W = LbVec<T>::W;
-#pragma unroll
-    for (int g = 0; g < N / W; ++g) {
-        T t[W];
-#pragma unroll
-        for (int i = 0; i < W; ++i) t[i] = x[g * W + i];
-        if (vec) {
-            *reinterpret_cast<typename LbVec<T>::type*>(p + e + g * W) = lb_pack(t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i)
-                if (g * W + i < nvalid) p[e + g * W + i] = t[i];
-        }
-    }
 }
 
 // sine and cosine of nu * tau turns: the product and its reduction to [-1/2, 1/2] in float64, the functions in T.  The
 // fraction is fma(nu, tau, -rint(nu * tau)), written out so that -ffp-contract has nothing left to decide: every
 // instantiation computes the same bits (a contracted and an uncontracted ph - rint(ph) differ by an ulp of the phase)
-__device__ __forceinline__ double lb_fraction(double nu, double tau)
+__device__ __forceinline__ double ta_fraction(double nu, double tau)
 {
     return fma(nu, tau, -rint(nu * tau));
 }
 
-__device__ __forceinline__ void lb_phasor(double nu, double tau, float& s, float& c)
+__device__ __forceinline__ void ta_phasor(double nu, double tau, float& s, float& c)
 {
-    const float r = (float)lb_fraction(nu, tau);
+    const float r = (float)ta_fraction(nu, tau);
     s = __builtin_amdgcn_sinf(r);                       // the hardware functions take revolutions (fringe.hip, sincos_turns)
     c = __builtin_amdgcn_cosf(r);
 }
 
-__device__ __forceinline__ void lb_phasor(double nu, double tau, double& s, double& c)
+__device__ __forceinline__ void ta_phasor(double nu, double tau, double& s, double& c)
 {
-    sincospi(2.0 * lb_fraction(nu, tau), &s, &c);
+    sincospi(2.0 * ta_fraction(nu, tau), &s, &c);
 }
 
 // (xr + i xi) (c + i sgn s), one product and one fused multiply-add per part, the same in every instantiation
 template <typename T>
-__device__ __forceinline__ void lb_rotate(T& xr, T& xi, T s, T c, bool conj)
+__device__ __forceinline__ void ta_rotate(T& xr, T& xi, T s, T c, bool conj)
 {
     const T sr = conj ? -s : s;
     const T zr = tfma<T>(xr, c, -(xi * sr)), zi = tfma<T>(xr, sr, xi * c);
@@ -133,9 +85,9 @@ struct LstBinArgs {
 };
 
 template <typename T, bool VEC>
-__global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs A)
+__global__ __launch_bounds__(TA_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs A)
 {
-    constexpr int CH = LB_BYTES / sizeof(T);
+    constexpr int CH = TA_BYTES / sizeof(T);
     const T* data = reinterpret_cast<const T*>(A.data);
     const T* wgts = reinterpret_cast<const T*>(A.wgts);
     const T* cov = reinterpret_cast<const T*>(A.cov);
@@ -146,7 +98,7 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs 
     const size_t nfg = (size_t)((A.Nf + CH - 1) / CH);
     const size_t total = (size_t)A.Npp * A.Nbl * A.Nbin * nfg;
     const size_t Ntau = (size_t)(A.by_member ? A.Nmem : A.Nt);
-    for (size_t i = (size_t)blockIdx.x * LB_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * LB_THREADS) {
+    for (size_t i = (size_t)blockIdx.x * TA_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * TA_THREADS) {
         const size_t fg = i % nfg, row = i / nfg;              // row = (p * Nbl + b) * Nbin + k
         const size_t k = row % (size_t)A.Nbin, pb = row / (size_t)A.Nbin, b = pb % (size_t)A.Nbl;
         const long long f0 = (long long)fg * CH;
@@ -167,13 +119,13 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs 
             const size_t e = (pb * (size_t)A.Nt + (size_t)t) * (size_t)A.Nf + (size_t)f0;
             T v[2 * CH], w[CH];
             if (data != nullptr) {
-                lb_load<T, 2 * CH>(data, 2 * e, 2 * nvalid, d_vec, v);
+                row_load<T, 2 * CH>(data, 2 * e, 2 * nvalid, d_vec, v);
             } else {
 #pragma unroll
                 for (int c = 0; c < CH; ++c) { v[2 * c] = (T)1; v[2 * c + 1] = (T)0; }
             }
             if (wgts != nullptr) {
-                lb_load<T, CH>(wgts, e, nvalid, w_vec, w);
+                row_load<T, CH>(wgts, e, nvalid, w_vec, w);
             } else {
 #pragma unroll
                 for (int c = 0; c < CH; ++c) w[c] = (T)1;
@@ -183,8 +135,8 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs 
 #pragma unroll
                 for (int c = 0; c < CH; ++c) {
                     T s, co;
-                    lb_phasor(nu[c], tau, s, co);
-                    lb_rotate<T>(v[2 * c], v[2 * c + 1], s, co, false);
+                    ta_phasor(nu[c], tau, s, co);
+                    ta_rotate<T>(v[2 * c], v[2 * c + 1], s, co, false);
                 }
             }
 #pragma unroll
@@ -195,7 +147,7 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs 
             }
             if (cov != nullptr) {
                 T cv[CH];
-                lb_load<T, CH>(cov, e, nvalid, c_vec, cv);
+                row_load<T, CH>(cov, e, nvalid, c_vec, cv);
 #pragma unroll
                 for (int c = 0; c < CH; ++c) ac[c] = tfma<T>(w[c] * w[c], cv[c], ac[c]);
             }
@@ -213,9 +165,9 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs 
             out[2 * c] = are[c] / d; out[2 * c + 1] = aim[c] / d;
             oc[c] = ac[c] / (d * d);
         }
-        lb_store<T, 2 * CH>(avg, 2 * o, 2 * nvalid, a_vec, out);
-        if (sum_w != nullptr) lb_store<T, CH>(sum_w, o, nvalid, s_vec, sw);
-        if (avg_cov != nullptr) lb_store<T, CH>(avg_cov, o, nvalid, ac_vec, oc);
+        row_store<T, 2 * CH>(avg, 2 * o, 2 * nvalid, a_vec, out);
+        if (sum_w != nullptr) row_store<T, CH>(sum_w, o, nvalid, s_vec, sw);
+        if (avg_cov != nullptr) row_store<T, CH>(avg_cov, o, nvalid, ac_vec, oc);
         if (A.avg_flag != nullptr) {
 #pragma unroll
             for (int c = 0; c < CH; ++c)
@@ -225,9 +177,9 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_fwd_kernel(LstBinArgs 
 }
 
 template <typename T, bool VEC>
-__global__ __launch_bounds__(LB_THREADS) void vis_timeavg_bwd_kernel(LstBinArgs A)
+__global__ __launch_bounds__(TA_THREADS) void vis_timeavg_bwd_kernel(LstBinArgs A)
 {
-    constexpr int CH = LB_BYTES / sizeof(T);
+    constexpr int CH = TA_BYTES / sizeof(T);
     const T* gavg = reinterpret_cast<const T*>(A.gavg);
     const T* wgts = reinterpret_cast<const T*>(A.wgts);
     const T* sum_w = reinterpret_cast<const T*>(A.sum_w);
@@ -236,7 +188,7 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_bwd_kernel(LstBinArgs 
     const size_t nfg = (size_t)((A.Nf + CH - 1) / CH);
     const size_t total = (size_t)A.Npp * A.Nbl * A.Nt * nfg;
     const size_t Ntau = (size_t)(A.by_member ? A.Nmem : A.Nt);
-    for (size_t i = (size_t)blockIdx.x * LB_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * LB_THREADS) {
+    for (size_t i = (size_t)blockIdx.x * TA_THREADS + threadIdx.x; i < total; i += (size_t)gridDim.x * TA_THREADS) {
         const size_t fg = i % nfg, row = i / nfg;              // row = (p * Nbl + b) * Nt + t
         const size_t t = row % (size_t)A.Nt, pb = row / (size_t)A.Nt, b = pb % (size_t)A.Nbl;
         const long long f0 = (long long)fg * CH;
@@ -251,7 +203,7 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_bwd_kernel(LstBinArgs 
         T w[CH], acc[2 * CH];
 #pragma unroll
         for (int c = 0; c < CH; ++c) { w[c] = (T)1; acc[2 * c] = (T)0; acc[2 * c + 1] = (T)0; }
-        if (wgts != nullptr && q1 > q0) lb_load<T, CH>(wgts, e, nvalid, w_vec, w);
+        if (wgts != nullptr && q1 > q0) row_load<T, CH>(wgts, e, nvalid, w_vec, w);
         for (long long q = q0; q < q1; ++q) {
             const int m = A.t_pos[q];
             if ((unsigned)m >= (unsigned)A.Nmem) continue;
@@ -259,8 +211,8 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_bwd_kernel(LstBinArgs 
             if ((unsigned)k >= (unsigned)A.Nbin) continue;
             const size_t o = (pb * (size_t)A.Nbin + (size_t)k) * (size_t)A.Nf + (size_t)f0;
             T g[2 * CH], sw[CH];
-            lb_load<T, 2 * CH>(gavg, 2 * o, 2 * nvalid, g_vec, g);
-            lb_load<T, CH>(sum_w, o, nvalid, s_vec, sw);
+            row_load<T, 2 * CH>(gavg, 2 * o, 2 * nvalid, g_vec, g);
+            row_load<T, CH>(sum_w, o, nvalid, s_vec, sw);
             double tau = 0.0;
             if (A.tau != nullptr) tau = A.tau[b * Ntau + (A.by_member ? (size_t)m : t)];
 #pragma unroll
@@ -270,26 +222,26 @@ __global__ __launch_bounds__(LB_THREADS) void vis_timeavg_bwd_kernel(LstBinArgs 
                 T gr = g[2 * c], gi = g[2 * c + 1];
                 if (A.tau != nullptr) {                        // conj(phasor) * g
                     T s, co;
-                    lb_phasor(nu[c], tau, s, co);
-                    lb_rotate<T>(gr, gi, s, co, true);
+                    ta_phasor(nu[c], tau, s, co);
+                    ta_rotate<T>(gr, gi, s, co, true);
                 }
                 acc[2 * c] = tfma<T>(coef, gr, acc[2 * c]);
                 acc[2 * c + 1] = tfma<T>(coef, gi, acc[2 * c + 1]);
             }
         }
-        lb_store<T, 2 * CH>(gdata, 2 * e, 2 * nvalid, o_vec, acc);
+        row_store<T, 2 * CH>(gdata, 2 * e, 2 * nvalid, o_vec, acc);
     }
 }
 
-static int lb_blocks(long long rows, long long Nf, int dtype)
+static int ta_blocks(long long rows, long long Nf, int dtype)
 {
-    const long long ch = LB_BYTES / (dtype == RIME_F32 ? 4 : 8);
+    const long long ch = TA_BYTES / real_bytes(dtype);
     const long long items = rows * ((Nf + ch - 1) / ch);
-    return (int)std::min<long long>((items + LB_THREADS - 1) / LB_THREADS, LB_MAXBLOCKS);
+    return (int)std::min<long long>((items + TA_THREADS - 1) / TA_THREADS, TA_MAXBLOCKS);
 }
 
 // sizes: non-negative, and the element counts of the tensors fit in 62 bits
-static bool lb_sizes_ok(long long Npp, long long Nbl, long long Nt, long long Nf, long long Nbin, long long Nmem)
+static bool ta_sizes_ok(long long Npp, long long Nbl, long long Nt, long long Nf, long long Nbin, long long Nmem)
 {
     if (Npp < 0 || Nbl < 0 || Nt < 0 || Nf < 0 || Nbin < 0 || Nmem < 0) return false;
     const long double lim = 4.0e18L;
@@ -297,7 +249,7 @@ static bool lb_sizes_ok(long long Npp, long long Nbl, long long Nt, long long Nf
 }
 
 // a host CSR table: ptr [n + 1] from 0, non-decreasing, ending at nmem; idx [nmem] in [0, bound)
-static bool lb_table_ok(const int* ptr, long long n, const int* idx, long long nmem, long long bound)
+static bool ta_table_ok(const int* ptr, long long n, const int* idx, long long nmem, long long bound)
 {
     if (ptr[0] != 0) return false;
     for (long long i = 0; i < n; ++i)
@@ -318,14 +270,14 @@ extern "C" int rime_vis_timeavg_fwd(int dtype, const void* data, const void* wgt
                                     int Nt, int Nf, int Nbin, int Nmem, void* avg, void* sum_w, void* avg_cov, void* avg_flag,
                                     void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
-    if (!lb_sizes_ok(Npp, Nbl, Nt, Nf, Nbin, Nmem)) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
+    if (!ta_sizes_ok(Npp, Nbl, Nt, Nf, Nbin, Nmem)) return RIME_EINVAL;
     if (tau_by_member != 0 && tau_by_member != 1) return RIME_EINVAL;
     if (!avg || !bin_ptr || !bin_ptr_host || (Nmem > 0 && (!members || !members_host))) return RIME_EINVAL;
     if (tau != nullptr && !freqs) return RIME_EINVAL;
     if ((cov != nullptr) != (avg_cov != nullptr) || (flags != nullptr) != (avg_flag != nullptr)) return RIME_EINVAL;
-    if (!lb_table_ok(bin_ptr_host, Nbin, members_host, Nmem, Nt)) return RIME_EINVAL;
-    const int nb = lb_blocks((long long)Npp * Nbl * Nbin, Nf, dtype);
+    if (!ta_table_ok(bin_ptr_host, Nbin, members_host, Nmem, Nt)) return RIME_EINVAL;
+    const int nb = ta_blocks((long long)Npp * Nbl * Nbin, Nf, dtype);
     if (nb == 0) return RIME_OK;                               // an empty output
     LstBinArgs A{};
     A.data = data; A.wgts = wgts; A.cov = cov; A.flags = (const unsigned char*)flags; A.tau = tau; A.freqs = freqs;
@@ -333,8 +285,8 @@ extern "C" int rime_vis_timeavg_fwd(int dtype, const void* data, const void* wgt
     A.avg_flag = (unsigned char*)avg_flag; A.by_member = tau_by_member;
     A.Npp = Npp; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nbin = Nbin; A.Nmem = Nmem;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool vec = lb_vec(dtype, Nf, {data, wgts, cov, avg, sum_w, avg_cov});
-    const dim3 grid((unsigned)nb), block(LB_THREADS);
+    const bool vec = ta_vec(dtype, Nf, {data, wgts, cov, avg, sum_w, avg_cov});
+    const dim3 grid((unsigned)nb), block(TA_THREADS);
     if (dtype == RIME_F32) {
         if (vec) hipLaunchKernelGGL((vis_timeavg_fwd_kernel<float, true>), grid, block, 0, st, A);
         else hipLaunchKernelGGL((vis_timeavg_fwd_kernel<float, false>), grid, block, 0, st, A);
@@ -350,24 +302,24 @@ extern "C" int rime_vis_timeavg_bwd(int dtype, const void* gavg, const void* wgt
                                     const int* pos_bin, const int* t_ptr_host, const int* t_pos_host, const int* pos_bin_host,
                                     int Npp, int Nbl, int Nt, int Nf, int Nbin, int Nmem, void* gdata, void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
-    if (!lb_sizes_ok(Npp, Nbl, Nt, Nf, Nbin, Nmem)) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
+    if (!ta_sizes_ok(Npp, Nbl, Nt, Nf, Nbin, Nmem)) return RIME_EINVAL;
     if (tau_by_member != 0 && tau_by_member != 1) return RIME_EINVAL;
     if (!gavg || !sum_w || !gdata || !t_ptr || !t_ptr_host) return RIME_EINVAL;
     if (Nmem > 0 && (!t_pos || !pos_bin || !t_pos_host || !pos_bin_host)) return RIME_EINVAL;
     if (tau != nullptr && !freqs) return RIME_EINVAL;
-    if (!lb_table_ok(t_ptr_host, Nt, t_pos_host, Nmem, Nmem)) return RIME_EINVAL;
+    if (!ta_table_ok(t_ptr_host, Nt, t_pos_host, Nmem, Nmem)) return RIME_EINVAL;
     for (long long m = 0; m < Nmem; ++m)
         if (pos_bin_host[m] < 0 || pos_bin_host[m] >= Nbin) return RIME_EINVAL;
-    const int nb = lb_blocks((long long)Npp * Nbl * Nt, Nf, dtype);
+    const int nb = ta_blocks((long long)Npp * Nbl * Nt, Nf, dtype);
     if (nb == 0) return RIME_OK;
     LstBinArgs A{};
     A.gavg = gavg; A.wgts = wgts; A.sum_w = const_cast<void*>(sum_w); A.tau = tau; A.freqs = freqs;
     A.t_ptr = t_ptr; A.t_pos = t_pos; A.pos_bin = pos_bin; A.gdata = gdata; A.by_member = tau_by_member;
     A.Npp = Npp; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nbin = Nbin; A.Nmem = Nmem;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool vec = lb_vec(dtype, Nf, {gavg, wgts, sum_w, gdata});
-    const dim3 grid((unsigned)nb), block(LB_THREADS);
+    const bool vec = ta_vec(dtype, Nf, {gavg, wgts, sum_w, gdata});
+    const dim3 grid((unsigned)nb), block(TA_THREADS);
     if (dtype == RIME_F32) {
         if (vec) hipLaunchKernelGGL((vis_timeavg_bwd_kernel<float, true>), grid, block, 0, st, A);
         else hipLaunchKernelGGL((vis_timeavg_bwd_kernel<float, false>), grid, block, 0, st, A);

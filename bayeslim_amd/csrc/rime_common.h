@@ -20,6 +20,10 @@ inline int check_launch()
     return RIME_ELAUNCH;
 }
 
+// The real working types of the C ABI: whether dtype names one, and its size in bytes (8 for anything but RIME_F32).
+inline bool real_dtype_ok(int dtype) { return dtype == RIME_F32 || dtype == RIME_F64; }
+inline int real_bytes(int dtype) { return dtype == RIME_F32 ? 4 : 8; }
+
 // Reads of matrix-core results by the vector ALU.  hipcc (ROCm 7.2) places the wait states of the ISA hazard table
 // between an MFMA and the first VALU read of its destination.  Observed on gfx950 (round 2, complex-psky backward of
 // the diagonal fringe blocks at 393 216 pixels): when that first reader was a PACKED f32 op (v_pk_fma_f32 with op_sel,

@@ -137,7 +137,7 @@ template <bool BWD>
 static int sfb_launch(int dtype, int cplx, const void* X, const void* g, const int* blocks, const int* cols, const int* tiles,
                       int Nblk, int Ntile, int B, int Nlmn, int Nr, int Nlm, void* res, void* stream)
 {
-    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
     if (cplx != 0 && cplx != 1) return RIME_EINVAL;
     if (Nr <= 0 || Nlm <= 0 || Nlmn < 0 || B < 0 || Nblk < 0 || Ntile < 0) return RIME_EINVAL;
     if (Nblk > 0 && (!blocks || !cols)) return RIME_EINVAL;

@@ -8,6 +8,8 @@ import ctypes
 
 import pytest
 
+import kernel_asm
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -137,15 +139,10 @@ def test_product_kernels_carry_no_laboratory_code_and_no_scratch():
         assert word not in src, word
     obj = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj')
     for name in ('fringe_mfma', 'alm'):
-        path = os.path.join(obj, name + '-hip-amdgcn-amd-amdhsa-gfx950.s')
-        if not os.path.exists(path):
-            subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-        asm = open(path).read()
-        kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+        asm, kernels, sizes = kernel_asm.read(name)
         assert len(kernels) >= 10
         assert not [k for k in kernels if 'pipe' in k or '_v2_' in k], kernels
         assert not re.findall(r'^\s*scratch_(?:load|store)', asm, flags=re.M)
-        sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
         assert len(sizes) == len(kernels) and max(sizes) == 0, sizes
     lib = open(os.path.join(ROOT, 'bayeslim_amd', 'lib', 'librime_hip.so'), 'rb').read()
     assert b'fringe_ant_bwd_pipe_kernel' not in lib and b'fringe_ant_fwd_v2_kernel' not in lib

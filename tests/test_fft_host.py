@@ -6,17 +6,14 @@ tests assert is one the reference's own float32 transform meets.
 """
 import copy
 import ctypes
-import os
 import pickle
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import fft_common as fc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_asm
 
 
 @pytest.fixture
@@ -215,14 +212,8 @@ def test_fft_apply_refuses_cpu_tensors():
 
 def test_fft_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/fft.hip: two kernels (f32, f64), no private segment"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'fft-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    _, kernels, sizes = kernel_asm.read('fft')
     assert len(kernels) == 2 and all('fft_kernel' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 2 and max(sizes) == 0, sizes
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_asm
 from filt_common import golden, oracle_filter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -200,15 +201,9 @@ def test_bad_arguments_are_rejected_without_launching():
 
 
 def test_filt_assembly_uses_no_scratch():
-    import subprocess
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'filt-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    asm, kernels, sizes = kernel_asm.read('filt')
     assert len(kernels) == 4 and all('filt_kernel' in k for k in kernels), kernels       # {f32, f64} x {real, complex W}
     assert not re.findall(r'^\s*scratch_(?:load|store)', asm, flags=re.M)
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 4 and max(sizes) == 0, sizes
     lds = [int(x) for x in re.findall(r'\.amdhsa_group_segment_fixed_size (\d+)', asm)]
     assert max(lds) < 160 * 1024, lds

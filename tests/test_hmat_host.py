@@ -5,7 +5,6 @@ deviation list of the module docstring, the half-recurrences of bfgs against com
 no-scratch property of the built kernels.
 """
 import ctypes
-import os
 import pickle
 import re
 
@@ -15,8 +14,7 @@ import torch
 
 import hmat_common as hc
 import lbfgs_common as lc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_asm
 
 
 def flatten(op, transpose=False):
@@ -235,13 +233,7 @@ def test_bfgs_refusals_and_no_apply_without_an_operator(monkeypatch):
 
 def test_hmat_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/hmat.hip: no kernel has a private segment"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'hmat-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    _, kernels, sizes = kernel_asm.read('hmat')
     # 2 precisions x 1, 2, 3, 4 right-hand sides per launch
     assert len(kernels) == 8 and all('hmat_apply_kernel' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 8 and max(sizes) == 0, sizes

@@ -5,16 +5,13 @@ decisions, argument validation of the two entry points without a GPU, the worksp
 files, and the no-scratch property of the built kernels.
 """
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import hmc_common as hc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_asm
 
 
 def pdict(seed=0, dtype=torch.float64):
@@ -344,13 +341,7 @@ def test_uturn_and_chain_files(tmp_path):
 
 def test_hmc_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/hmc.hip: no kernel has a private segment"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'hmc-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    _, kernels, sizes = kernel_asm.read('hmc')
     # the stage in 2 precisions + the second reduction stage
     assert len(kernels) == 3 and all('hmc_' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 3 and max(sizes) == 0, sizes

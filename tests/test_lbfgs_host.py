@@ -5,16 +5,13 @@ step() on the float64 oracle of tests/lbfgs_common.py against the recorded traje
 the workspace size, and the no-scratch property of the built kernels.
 """
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import lbfgs_common as lc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_asm
 
 
 @pytest.fixture
@@ -187,13 +184,7 @@ def test_cpu_tensors_raise(f64):
 
 def test_lbfgs_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/lbfgs.hip: no kernel has a private segment"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'lbfgs-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    _, kernels, sizes = kernel_asm.read('lbfgs')
     # 2 precisions x (dots with and without a new pair + combine) + the second reduction stage
     assert len(kernels) == 7 and all('lbfgs_' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 7 and max(sizes) == 0, sizes

@@ -6,9 +6,7 @@ A^H tables of the plan, argument validation without a GPU, and the no-scratch pr
 """
 import copy
 import ctypes
-import os
 import pickle
-import re
 import warnings
 
 import numpy as np
@@ -16,8 +14,7 @@ import pytest
 import torch
 
 import lm_common as lc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import kernel_asm
 
 
 @pytest.fixture
@@ -257,13 +254,7 @@ def test_linear_model_attributes_pickle_and_containers(f64):
 
 def test_lm_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/lm.hip: no kernel has a private segment"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'lm-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    _, kernels, sizes = kernel_asm.read('lm')
     # 2 precisions x 6 type combinations x (9 few-in + 9 few-out (register size, columns per lane) pairs + 1 last-axis)
     assert len(kernels) == 228 and all('lm_' in k for k in kernels), len(kernels)
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 228 and max(sizes) == 0, sizes

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import lstbin_common as lc
+import kernel_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -161,14 +162,8 @@ def test_cpu_tensors_raise_the_no_cpu_error():
 
 def test_kernels_use_no_scratch_and_sixteen_byte_accesses():
     """the gfx950 assembly of this build: eight kernels (dtype x 16-byte / element form), none with a private segment, and 16-byte loads and stores present"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'lstbin-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    asm, kernels, sizes = kernel_asm.read('lstbin')
     assert len(kernels) == 8 and all('vis_timeavg' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert sizes == [0] * 8, sizes
     assert not re.findall(r'^\s*scratch_(?:load|store)', asm, flags=re.M)
     assert 'global_load_dwordx4' in asm and 'global_store_dwordx4' in asm
@@ -177,6 +172,6 @@ def test_kernels_use_no_scratch_and_sixteen_byte_accesses():
 
 def test_layout_constants_match_the_source():
     src = open(os.path.join(ROOT, 'bayeslim_amd', 'csrc', 'lstbin.hip')).read()
-    assert re.search(r'LB_THREADS = 256, LB_BYTES = 16\b', src)
+    assert re.search(r'TA_THREADS = 256, TA_BYTES = 16\b', src)
     assert lc.LANE_F == {'f32': 16 // 4, 'f64': 16 // 8} and lc.GROUP_F == {'f32': 1024, 'f64': 512}
     assert lc.NF == {'f32': [1, 3, 4, 5, 1023, 1024, 1025], 'f64': [1, 2, 3, 511, 512, 513]}

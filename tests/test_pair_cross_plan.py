@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+import kernel_asm
 from pair_cross_cases import CROSS_KINDS, EXPECTED, UNCHANGED_KINDS, make_array, make_pairs, seed_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -153,11 +154,10 @@ def test_scan_record_of_the_pair_cross_kernels():
     m = re.search(r'no packed f32 instruction in the (\d+) kernels named \*fringe_xpair_\*', rec)
     assert m and int(m.group(1)) == 6, rec
     assert os.path.getmtime(os.path.join(obj, 'fringe_xpair.scan')) >= os.path.getmtime(os.path.join(obj, 'fringe_xpair.o'))
-    asm = open(os.path.join(obj, 'fringe_xpair-hip-amdgcn-amd-amdhsa-gfx950.s')).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    asm, kernels, sizes = kernel_asm.read('fringe_xpair')
     assert len(kernels) == 6 and all('fringe_xpair_' in k and 'fringe_pair_' not in k for k in kernels), kernels
     assert not re.findall(r'^\s*scratch_(?:load|store)', asm, flags=re.M)
-    assert [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)] == [0] * 6
+    assert sizes == [0] * 6
     assert not re.findall(r'^\s*v_pk_(?:add|mul|fma)_f32', asm, flags=re.M)
     src = open(os.path.join(ROOT, 'bayeslim_amd', 'csrc', 'fringe_xpair.hip')).read()
     assert '#if' not in src

@@ -5,7 +5,6 @@ reference's recorded results (tests/golden/redcal.npz, float64, rtol 1e-10), vis
 of CPU tensors, argument validation of the two entry points without a GPU, and the no-scratch property of the built kernels.
 """
 import ctypes
-import os
 import pickle
 import re
 
@@ -14,8 +13,8 @@ import pytest
 import torch
 
 import redcal_common as rc
+import kernel_asm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL = 1e-10
 
 
@@ -228,13 +227,7 @@ def test_entry_points_reject_bad_arguments_without_launching():
 def test_redvis_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/redvis.hip: 4 forward (precision x Npol) and 2 backward kernels, no private
     segment in any"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'redvis-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    asm, kernels, sizes = kernel_asm.read('redvis')
     assert len(kernels) == 6 and all('redvis_' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 6 and max(sizes) == 0, sizes
     assert not re.findall(r'global_atomic|flat_atomic', asm)

@@ -5,17 +5,15 @@ tests/golden/sfb.npz), the in-file oracle of the GPU tests against the same vect
 rime_sfb_fwd / rime_sfb_bwd.  No GPU.
 """
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 import torch
 
+import kernel_asm
 from conftest import load_golden
 from sfb_common import oracle_grad, unpack_basis, relmax
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope='module')
@@ -199,14 +197,8 @@ def test_sfb_entry_points_reject_bad_arguments_without_launching():
 def test_sfb_kernels_use_no_scratch():
     """the gfx950 assembly of THIS build of csrc/sfb.hip: eight kernels (f32 / f64, real / complex, forward / backward), no
     private segment, no matrix-core instruction"""
-    path = os.path.join(ROOT, 'bayeslim_amd', 'lib', 'obj', 'sfb-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(path):
-        import subprocess
-        subprocess.run(['make', '-C', os.path.join(ROOT, 'bayeslim_amd', 'csrc')], check=True, capture_output=True)
-    asm = open(path).read()
-    kernels = re.findall(r'\.amdhsa_kernel (\S+)', asm)
+    asm, kernels, sizes = kernel_asm.read('sfb')
     assert len(kernels) == 8 and all('sfb_kernel' in k for k in kernels), kernels
-    sizes = [int(x) for x in re.findall(r'\.amdhsa_private_segment_fixed_size (\d+)', asm)]
     assert len(sizes) == 8 and max(sizes) == 0, sizes
     assert not re.findall(r'^\s*scratch_(?:load|store)', asm, flags=re.M)
     assert 'v_mfma' not in asm
