@@ -105,7 +105,10 @@ interp_gather_kernel(const T* __restrict__ m, const int* __restrict__ inds,
                 const int id = inds[(size_t)p * Nnn + k];
                 const T w = wgts[(size_t)p * Nnn + k];
 #pragma unroll
-                for (int c = 0; c < NC; ++c) acc[c] = tfma<T>(w, row[(size_t)id * NC + c], acc[c]);
+                for (int c = 0; c < NC; ++c) {
+                    const T v = row[(size_t)id * NC + c];
+                    acc[c] = w != T(0) ? tfma<T>(w, v, acc[c]) : acc[c];      // as above: weight 0 = no term
+                }
             }
 #pragma unroll
             for (int c = 0; c < NC; ++c) out[((size_t)r * out_stride + p) * NC + c] = acc[c];
@@ -203,20 +206,26 @@ template <typename T, int NC>
 static int gather_launch(const void* m, const int* inds, const void* wgts, int R, int Npb, int P,
                          int Nnn, void* out, int out_stride, hipStream_t st)
 {
-    dim3 grid((P + 255) / 256, (R + RT - 1) / RT), block(256);
-    const T* m_ = reinterpret_cast<const T*>(m);
     const T* w_ = reinterpret_cast<const T*>(wgts);
-    T* o_ = reinterpret_cast<T*>(out);
-#define RIME_G(N) hipLaunchKernelGGL((interp_gather_kernel<T, NC, N>), grid, block, 0, st, m_, inds, w_, R, Npb, P, Nnn, o_, out_stride)
-    switch (Nnn) {
-        case 1: RIME_G(1); break;
-        case 4: RIME_G(4); break;
-        case 6: RIME_G(6); break;
-        case 9: RIME_G(9); break;
-        case 16: RIME_G(16); break;
-        default: RIME_G(0); break;
-    }
+    // rows beyond one grid's reach (65535 x RT) go to further launches on row-offset pointers, as in the row-major adjoint
+    // (rime_interp_scatter_rows_bwd): the redundant inflation gathers Npol^2 Nt Nf rows
+    const int chunk = 65535 * RT;
+    for (int r0 = 0; r0 < R; r0 += chunk) {
+        const int Rc = R - r0 < chunk ? R - r0 : chunk;
+        dim3 grid((P + 255) / 256, (Rc + RT - 1) / RT), block(256);
+        const T* m_ = reinterpret_cast<const T*>(m) + (size_t)r0 * Npb * NC;
+        T* o_ = reinterpret_cast<T*>(out) + (size_t)r0 * out_stride * NC;
+#define RIME_G(N) hipLaunchKernelGGL((interp_gather_kernel<T, NC, N>), grid, block, 0, st, m_, inds, w_, Rc, Npb, P, Nnn, o_, out_stride)
+        switch (Nnn) {
+            case 1: RIME_G(1); break;
+            case 4: RIME_G(4); break;
+            case 6: RIME_G(6); break;
+            case 9: RIME_G(9); break;
+            case 16: RIME_G(16); break;
+            default: RIME_G(0); break;
+        }
 #undef RIME_G
+    }
     return check_launch();
 }
 
