@@ -23,6 +23,10 @@ The degeneracy tools (`compute_redcal_degen`, `redcal_degen_gains`, `remove_redc
 BaseResponse.setup_projection(abs_amp_gain=, phs_slope_gain=, wgts_gain=) projects them out of the gains through
 remove_redcal_degen.  `vis2JonesModel` / `vis2RedVisModel` (:2918-2983) build vanilla models from a VisData.
 The CalData export is outside the hot path and not built.
+
+Mutual coupling: `VisCoupling` (:1258-1586) applies Vc = E V E^H, E = I + X o D, between the redundant-visibility and the
+gain stage through ops.coupling_apply, one batched complex product kernel that reads the visibility matrix from the data through
+an index table, builds E on the fly and writes only the baselines of the output.
 """
 import copy
 
@@ -590,6 +594,174 @@ class VisModel(_VisTerm):
             return self._apply(vd, vis, lambda: _sel2index(self.get_bl_idx(vd._blnums), Nmod), Nmod,
                                utils.arr_hash(vd._blnums), undo)
         return self._apply(vd, vis, lambda: np.arange(Nbl), Nmod, None, undo)
+
+
+# ---------------------------------------------------------------------------------------
+# antenna mutual coupling (calibration.py:1258-1586)
+# ---------------------------------------------------------------------------------------
+class VisCoupling(utils.Module, IndexCache):
+    """
+    Mutual coupling of antennas as a linear map of visibilities across the baseline axis (calibration.py:1258-1586): with V
+    the Nant x Nant matrix of all visibilities of one time and channel (lower triangle the conjugate of the upper, baselines
+    missing from the input zero) the coupled visibilities are Vc = E V E^H with E = I + X o D, X the coupling coefficients
+    (params through the response R, shape (1, 1, Nant, Nant, Ntimes | 1, Nfreqs | 1)) and D the delay phasor between the two
+    antennas; `double` adds the double-path term, E = I + Xd + Xd Xd with Xd = X o D.  The matrix order is the order of
+    `antpos`; `bls` are the baselines along the Nbls axis of the input, each with ant2 >= ant1.  setup_coupling() must run
+    before forward().  forward(vd, prior_cache=None, add_I=None, prod=None, double=False) -> VisData: everything runs in
+    ops.coupling_apply -- the matrix is read from vd.data through an index table and only the rows of `bls` are written, so no
+    (Nant^2, Ntimes, Nfreqs) copy exists, E is built on the fly and the output of R is never modified in place; the gradients
+    come from the same kernel in a fixed summation order (bit-identical from run to run).  As in the reference the `double`
+    keyword of forward decides, self.double only when None is passed.  Single polarisation only; no CPU implementation.
+    Not built: RedVisCoupling, CouplingInflate, PartialRedVisInflate, CouplingExpand, configure_coupling_matrix_singlepath,
+    gen_coupling_terms.
+    """
+    def __init__(self, params, freqs, antpos, bls, R=None, parameter=True, p0=None, name=None, atol=1e-5, add_I=True,
+                 prod='both', double=False):
+        utils.Module.__init__(self, name=name)
+        self.params = torch.nn.Parameter(params) if parameter else params
+        self.p0 = p0
+        self.freqs = freqs
+        self.Nfreqs = len(freqs)
+        self.antpos = antpos
+        self.Nants = len(antpos)
+        self.bls = bls
+        self.c = 2.99792458e8
+        self.device = params.device
+        self.Npol = params.shape[0]
+        assert self.Npol == 1, "multi-pol not currently supported"
+        self.add_I, self.prod, self.double = add_I, prod, double
+        self.R = R if R is not None else VisModelResponse()
+        IndexCache.__init__(self, times=getattr(self.R, 'times', None), atol=atol)
+        self.clear_cache()
+
+    def clear_cache(self):
+        """clear all caches, some come from IndexCache"""
+        self.clear_time_cache()
+        self.clear_bl_cache()
+        self.clear_vd_cache()
+
+    def clear_vd_cache(self):
+        self._vd = None
+
+    def __getstate__(self):
+        """pickle and deepcopy leave the cached output behind: after a forward its data is a node of an autograd graph"""
+        state = dict(self.__dict__)
+        state['_vd'] = None
+        return state
+
+    def setup_coupling(self, bls=None, min_dly=None, conj=True):
+        """
+        Delay phasor and matrix indexing of the forward model.  bls: the baselines of the input data (default: those given
+        at construction); min_dly: shortest baseline length [m] used for the coupling delay, dly = max(min_dly, |r_j - r_i|) / c
+        (typically the feed height); conj: the conjugated convention of the delay term.  Sets `dly`
+        (1, 1, Nant, Nant, 1, Nfreqs) = exp(+-2 pi i (f - f_0) / c * length), the int32 matrix table of ops.CouplingPlan, and
+        the reference's index attributes flat_data_idx, flat_conj_idx, flat_unconj_idx, flat_data_null, bls_idx and I.
+        ValueError for a baseline with ant2 < ant1, a duplicate or an antenna that is not in antpos (the reference indexes
+        the wrong rows without a word).
+        """
+        if bls is not None:
+            self.bls = bls
+        ants = [int(a) for a in self.antpos]
+        where = {a: i for i, a in enumerate(ants)}
+        N = self.Nants
+        pairs = [(int(b[0]), int(b[1])) for b in self.bls]
+        rows = {}
+        for r, (a1, a2) in enumerate(pairs):
+            if a1 not in where or a2 not in where:
+                raise ValueError('baseline %s names an antenna that is not in antpos' % ((a1, a2),))
+            if a2 < a1:
+                raise ValueError('baseline %s: VisCoupling needs ant2 >= ant1' % ((a1, a2),))
+            if (a1, a2) in rows:
+                raise ValueError('baseline %s appears twice' % ((a1, a2),))
+            rows[(a1, a2)] = r
+
+        # delay phasor between coupled antennas
+        vecs = np.stack([np.asarray(torch.as_tensor(self.antpos[a]).detach().cpu(), dtype=np.float64) for a in ants])
+        length = np.linalg.norm(vecs[None, :, :] - vecs[:, None, :], axis=-1)
+        if min_dly is not None:
+            length = np.maximum(length, min_dly)
+        fr = np.asarray(torch.as_tensor(self.freqs).detach().cpu(), dtype=np.float64)
+        phase = 2 * np.pi * (1 if conj else -1) * (fr - fr[0])[None, None, :] / self.c * length[:, :, None]
+        self.dly = torch.as_tensor(np.exp(1j * phase)[None, None, :, :, None, :]).to(dtype=utils._cfloat(), device=self.device)
+
+        # matrix entry (i, j): the row of (ant_i, ant_j) when ant_j >= ant_i, else the conjugate of the row of (ant_j, ant_i)
+        table = np.full((N, N), -1, dtype=np.int64)
+        data_idx, null, conj_idx, unconj_idx = [], [], [], []
+        for i, a1 in enumerate(ants):
+            for j, a2 in enumerate(ants):
+                upper = a2 >= a1
+                r = rows.get((a1, a2) if upper else (a2, a1))
+                (unconj_idx if upper else conj_idx).append(i * N + j)
+                data_idx.append(0 if r is None else r)
+                null.append(r is None)
+                if r is not None:
+                    table[i, j] = r if upper else r | ops.COUPLING_CONJ
+        out_rows = np.array([where[a1] * N + where[a2] for a1, a2 in pairs], dtype=np.int64)
+        self.plan = ops.CouplingPlan(table, out_rows, len(pairs))
+        self.flat_data_idx = torch.tensor(data_idx, dtype=torch.int64, device=self.device)
+        self.flat_conj_idx = torch.tensor(conj_idx, dtype=torch.int64, device=self.device)
+        self.flat_unconj_idx = torch.tensor(unconj_idx, dtype=torch.int64, device=self.device)
+        self.flat_data_null = torch.tensor(null, dtype=torch.bool, device=self.device)
+        self.bls_idx = torch.as_tensor(out_rows, device=self.device)
+        self.I = torch.eye(N, dtype=utils._float(), device=self.device)[None, None, :, :, None, None]
+
+    def index_params(self, params, times=None):
+        """overloads IndexCache.index_params: one time bin in params broadcasts"""
+        if times is not None and params.shape[-2] != 1:
+            params = IndexCache.index_params(self, params, times=times)
+        return params
+
+    def forward(self, vd, prior_cache=None, add_I=None, prod=None, double=False, **kwargs):
+        """vd: VisData of shape (1, 1, Nbls, Ntimes, Nfreqs) holding exactly the baselines of setup_coupling, in their order;
+        returns the cached output VisData with the coupled visibilities"""
+        if getattr(self, 'plan', None) is None:
+            raise RuntimeError('VisCoupling: run setup_coupling() before forward()')
+        if not vd.data.is_cuda:
+            raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
+        if tuple(vd.data.shape[:3]) != (1, 1, self.plan.Nbl):
+            raise ValueError('input of shape %s, VisCoupling was set up for (1, 1, %d, Ntimes, Nfreqs)'
+                             % (tuple(vd.data.shape), self.plan.Nbl))
+        if getattr(self, '_vd', None) is None:
+            self._vd = vd.copy(copydata=False)
+        vout = self._vd
+        params = self.params if self.p0 is None else self.params + self.p0
+        coupling = self.R(params)
+        if getattr(self, '_hook_registry', None) is not None and coupling.requires_grad:
+            for r in self._hook_registry:
+                coupling.register_hook(r)
+        self.eval_prior(prior_cache, inp_params=self.params, out_params=coupling)
+        coupling = self.index_params(coupling, times=vd.times)
+        if not coupling.is_complex():
+            coupling = coupling.to(vd.data.dtype)
+        double = double if double is not None else self.double
+        out = ops.coupling_apply(coupling[0, 0], self.dly[0, 0], vd.data[0, 0], self.plan,
+                                 add_I=add_I if add_I is not None else self.add_I,
+                                 prod=prod if prod is not None else self.prod, double=bool(double))
+        vout.data = out[None, None]
+        return vout
+
+    def push(self, device):
+        """push to a new device or dtype"""
+        dtype = isinstance(device, torch.dtype)
+        if not dtype:
+            self.device = device
+            if isinstance(self._times, torch.Tensor):
+                self._times = utils.push(self._times, device)
+            for k in ('flat_data_idx', 'flat_data_null', 'flat_conj_idx', 'flat_unconj_idx', 'bls_idx'):
+                if hasattr(self, k):
+                    setattr(self, k, getattr(self, k).to(device))
+        for k in ('I', 'dly'):
+            if hasattr(self, k):
+                setattr(self, k, utils.push(getattr(self, k), device))
+        self.params = utils.push(self.params, device)
+        self.freqs = utils.push(self.freqs, device)
+        self.R.push(device)
+        if self.p0 is not None:
+            self.p0 = utils.push(self.p0, device)
+        for prs in (self.priors_inp_params, self.priors_out_params):
+            for pr in (prs or []):
+                if pr is not None:
+                    pr.push(device)
 
 
 # ---------------------------------------------------------------------------------------

@@ -2796,3 +2796,222 @@ def rephase_phasor(tau, freqs, dtype=torch.complex64):
                                   _ptr(torch.view_as_real(out)), _ptr(None), _ptr(None), _ptr(None), _stream())
     check(rc, 'rime_vis_timeavg_fwd')
     return out
+
+
+# ---------------------------------------------------------------------------------------
+# antenna mutual coupling: W = E V E^H on one batched complex product kernel (csrc/coupling.hip)
+# ---------------------------------------------------------------------------------------
+COUPLING_CONJ = 1 << 30                          # table word: the row is read conjugated (ftab: no conjugated reader)
+COUPLING_PROD = {'both': 0, 'left': 1, 'right': 2}
+_COUPLING_FWD, _COUPLING_BWD, _COUPLING_EXPAND_BWD = 0, 1, 2
+
+
+class CouplingPlan:
+    """
+    Tables of rime_coupling_fwd / rime_coupling_bwd for one (antenna order, baseline list), built and range-checked with numpy
+    on the host (no GPU needed) and cached per device as int32 tensors.
+      table     (N, N) integers: entry (a, b) of the visibility matrix is data[row] for the word `row`, conj(data[row]) for
+                `row | COUPLING_CONJ`, zero for -1
+      out_rows  (Nout,) flat matrix positions a * N + b of the output rows, in output order
+      Nbl       rows of the data
+    Derived: `otab` (N, N), the output row of every matrix entry or -1, and `ftab` (N, N), at the entry that reads a data row
+    unconjugated the row itself, with COUPLING_CONJ set when no entry reads it conjugated (its gradient is then the single
+    term), -1 elsewhere.  ValueError for a table that is not square, a word outside {-1} U [0, Nbl) (| COUPLING_CONJ), a row
+    read twice in the same sense or only conjugated, a row read conjugated anywhere but at the transpose of the entry that
+    reads it plain (the folded gradient pairs (a, b) with (b, a)), an output position outside the matrix or named twice.
+    """
+    def __init__(self, table, out_rows, Nbl):
+        table = np.asarray(table.cpu() if torch.is_tensor(table) else table)
+        out_rows = np.asarray(out_rows.cpu() if torch.is_tensor(out_rows) else out_rows).reshape(-1)
+        if table.ndim != 2 or table.shape[0] != table.shape[1] or table.shape[0] < 1 or not np.issubdtype(table.dtype, np.integer):
+            raise ValueError('table must be a square integer matrix')
+        if out_rows.size < 1 or not np.issubdtype(out_rows.dtype, np.integer):
+            raise ValueError('out_rows must be a non-empty integer array')
+        table = table.astype(np.int64)
+        self.N, self.Nbl, self.Nout = int(table.shape[0]), int(Nbl), int(out_rows.size)
+        if not 1 <= self.Nbl < COUPLING_CONJ:
+            raise ValueError('Nbl must be in [1, 2^30)')
+        null = table == -1
+        if (table[~null] < 0).any():
+            raise ValueError('a table word is -1 (null) or a row with an optional conjugate bit')
+        row = np.where(null, -1, table & (COUPLING_CONJ - 1))
+        conj = ~null & ((table & COUPLING_CONJ) != 0)
+        if ((table & ~np.int64(2 * COUPLING_CONJ - 1)) != 0)[~null].any() or (row[~null] >= self.Nbl).any():
+            raise ValueError('table row outside [0, %d)' % self.Nbl)
+        plain = ~null & ~conj
+        nplain, nconj = np.bincount(row[plain], minlength=self.Nbl), np.bincount(row[conj], minlength=self.Nbl)
+        if nplain.max(initial=0) > 1 or nconj.max(initial=0) > 1:
+            raise ValueError('a data row is read twice in the same sense')
+        if ((nconj > 0) & (nplain == 0)).any():
+            raise ValueError('a data row is read only conjugated')
+        if (conj & ~((row.T == row) & plain.T)).any():
+            raise ValueError('the conjugated reader of a data row must be the transpose of its plain reader')
+        if out_rows.min() < 0 or out_rows.max() >= self.N * self.N or np.unique(out_rows).size != out_rows.size:
+            raise ValueError('out_rows must be distinct positions in [0, %d)' % (self.N * self.N))
+        self.table = table.astype(np.int32)
+        otab = np.full(self.N * self.N, -1, dtype=np.int32)
+        otab[out_rows] = np.arange(self.Nout, dtype=np.int32)
+        self.otab = otab.reshape(self.N, self.N)
+        self.ftab = np.where(plain, row | np.where(nconj[np.maximum(row, 0)] == 0, COUPLING_CONJ, 0), -1).astype(np.int32)
+        self.out_rows = out_rows.astype(np.int64)
+        self.unread = bool((nplain == 0).any())           # rows of the data outside the matrix: their gradient is zero
+
+    def tables(self, device):
+        """dict of the three int32 tables on `device`, cached"""
+        key = str(torch.device(device))
+        tabs = self.__dict__.setdefault('_tabs', {})
+        if key not in tabs:
+            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous()
+                         for k in ('table', 'otab', 'ftab')}
+        return tabs[key]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tabs', None)
+        return state
+
+
+def _coupling_operands(coupling, dly, dtype, Nf=None):
+    """(x, dly, N, Tm, Fm, Nf) contiguous in `dtype`: coupling (N, N, Tm, Fm), dly (N, N, 1, Nf) or None"""
+    assert coupling.is_complex() and coupling.ndim == 4 and coupling.shape[0] == coupling.shape[1], \
+        'complex coupling of shape (Nant, Nant, Ntimes | 1, Nfreqs | 1)'
+    x = coupling.detach().resolve_conj().to(dtype).contiguous()
+    N, _, Tm, Fm = x.shape
+    d = None
+    if dly is not None:
+        assert dly.is_complex() and dly.ndim == 4 and tuple(dly.shape[:3]) == (N, N, 1), 'complex dly of shape (Nant, Nant, 1, Nfreqs)'
+        d = dly.detach().resolve_conj().to(dtype).contiguous()
+        if Nf is not None and d.shape[3] != Nf:
+            raise ValueError('dly of %d channels, data of %d' % (d.shape[3], Nf))
+        Nf = d.shape[3]
+    elif Nf is None:
+        Nf = Fm
+    return x, d, N, Tm, Fm, Nf
+
+
+def _coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, stage, device):
+    nbytes = lib.rime_coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, stage)
+    return (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None), nbytes
+
+
+def _coupling_fwd_call(coupling, dly, data, plan, add_I, prod, out=None):
+    """W rows (Nout, Nt, Nf) of a contiguous complex data (Nbl, Nt, Nf); `out`: a contiguous tensor to write into"""
+    Nbl, Nt, Nf = data.shape
+    x, d, N, Tm, Fm, _ = _coupling_operands(coupling, dly, data.dtype, Nf)
+    if N != plan.N or Nbl != plan.Nbl:
+        raise ValueError('coupling of %d antennas and data of %d rows, the plan has %d and %d' % (N, Nbl, plan.N, plan.Nbl))
+    if Tm not in (1, Nt) or Fm not in (1, Nf):
+        raise ValueError('coupling of (%d, %d) times and channels against data of (%d, %d)' % (Tm, Fm, Nt, Nf))
+    code, _ = _real_dtype(data)
+    T = plan.tables(data.device)
+    if out is None:
+        out = torch.empty((plan.Nout, Nt, Nf), dtype=data.dtype, device=data.device)
+    assert out.is_contiguous() and tuple(out.shape) == (plan.Nout, Nt, Nf) and out.dtype == data.dtype
+    ws, nbytes = _coupling_workspace(code, N, Nt, Nf, Tm, Fm, COUPLING_PROD[prod], _COUPLING_FWD, data.device)
+    rc = lib.rime_coupling_fwd(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
+                               _ptr(torch.view_as_real(data)), _ptr(T['table']), _ptr(T['otab']), N, Nbl, plan.Nout, Nt, Nf,
+                               Tm, Fm, int(bool(add_I)), COUPLING_PROD[prod], _ptr(torch.view_as_real(out)), _ptr(ws), nbytes,
+                               _stream())
+    check(rc, 'rime_coupling_fwd')
+    return out
+
+
+class _CouplingApply(torch.autograd.Function):
+    """W = E V E^H (or E V, V E^H) with E = [I] + coupling o dly; saves coupling and data only, T = E V is recomputed"""
+    @staticmethod
+    def forward(ctx, coupling, dly, data, plan, add_I, prod):
+        _require_cuda(coupling, dly, data)
+        assert data.is_complex() and data.ndim == 3, 'complex data of shape (Nbls, Ntimes, Nfreqs)'
+        if prod not in COUPLING_PROD:
+            raise ValueError("prod must be 'both', 'left' or 'right'")
+        v = data.detach().resolve_conj().contiguous()
+        out = _coupling_fwd_call(coupling, dly, v, plan, add_I, prod)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(coupling.detach(), dly.detach() if dly is not None else None, v)
+            ctx.plan, ctx.add_I, ctx.prod, ctx.xdtype, ctx.ddtype = plan, bool(add_I), prod, coupling.dtype, data.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        coupling, dly, v = ctx.saved_tensors
+        plan = ctx.plan
+        Nbl, Nt, Nf = v.shape
+        x, d, N, Tm, Fm, _ = _coupling_operands(coupling, dly, v.dtype, Nf)
+        g = gout.detach().resolve_conj().to(v.dtype).contiguous()
+        code, _ = _real_dtype(v)
+        T = plan.tables(v.device)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        gd = None
+        if ctx.needs_input_grad[2]:
+            gd = torch.zeros_like(v) if plan.unread else torch.empty_like(v)
+        prod = COUPLING_PROD[ctx.prod]
+        ws, nbytes = _coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, _COUPLING_BWD, v.device)
+        rc = lib.rime_coupling_bwd(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
+                                   _ptr(torch.view_as_real(v)), _ptr(torch.view_as_real(g)), _ptr(T['table']), _ptr(T['otab']),
+                                   _ptr(T['ftab']), N, Nbl, plan.Nout, Nt, Nf, Tm, Fm, int(ctx.add_I), prod,
+                                   _ptr(torch.view_as_real(gd) if gd is not None else None),
+                                   _ptr(torch.view_as_real(gx) if gx is not None else None), _ptr(ws), nbytes, _stream())
+        check(rc, 'rime_coupling_bwd')
+        if gx is not None and gx.dtype != ctx.xdtype:
+            gx = gx.to(ctx.xdtype)
+        if gd is not None and gd.dtype != ctx.ddtype:
+            gd = gd.to(ctx.ddtype)
+        return gx, None, gd, None, None, None
+
+
+class _CouplingExpand(torch.autograd.Function):
+    """the double-path matrix E = [I] + Xd + Xd Xd, Xd = coupling o dly, as a dense (N, N, Tm, Nf) tensor"""
+    @staticmethod
+    def forward(ctx, coupling, dly, add_I):
+        _require_cuda(coupling, dly)
+        x, d, N, Tm, Fm, Nf = _coupling_operands(coupling, dly, coupling.dtype)
+        code, _ = _real_dtype(x)
+        E = torch.empty((N, N, Tm, Nf), dtype=x.dtype, device=x.device)
+        rc = lib.rime_coupling_expand(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
+                                      N, Tm, Nf, Tm, Fm, int(bool(add_I)), _ptr(torch.view_as_real(E)), _stream())
+        check(rc, 'rime_coupling_expand')
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, d)
+        return E
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gE):
+        x, d = ctx.saved_tensors
+        N, _, Tm, Fm = x.shape
+        Nf = gE.shape[3]
+        g = gE.detach().resolve_conj().to(x.dtype).contiguous()
+        code, _ = _real_dtype(x)
+        gx = torch.empty_like(x)
+        ws, nbytes = _coupling_workspace(code, N, Tm, Nf, Tm, Fm, 0, _COUPLING_EXPAND_BWD, x.device)
+        rc = lib.rime_coupling_expand_bwd(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
+                                          _ptr(torch.view_as_real(g)), N, Tm, Nf, Tm, Fm, _ptr(torch.view_as_real(gx)), _ptr(ws),
+                                          nbytes, _stream())
+        check(rc, 'rime_coupling_expand_bwd')
+        return gx, None, None
+
+
+def coupling_expand(coupling, dly=None, add_I=True):
+    """E = [I] + Xd + Xd Xd with Xd = coupling o dly (double-path coupling) on the product kernel of coupling_apply: coupling
+    (N, N, Tm, Fm) complex, dly (N, N, 1, Nf) or None -> (N, N, Tm, Nf | Fm).  Differentiable once in coupling.  No CPU path."""
+    return _CouplingExpand.apply(coupling, dly, add_I)
+
+
+def coupling_apply(coupling, dly, data, table, out_rows=None, add_I=True, prod='both', double=False):
+    """
+    Mutual coupling of visibilities, W = E V E^H (prod 'both'), E V ('left') or V E^H ('right') per time and channel, with
+    E = [I] + coupling o dly built on the fly, V read from `data` through the matrix table and only the output rows written
+    (rime_coupling_fwd; nothing of size (N^2, Nt, Nf) is gathered or saved).
+      coupling (N, N, Tm, Fm) complex, Tm in {1, Nt}, Fm in {1, Nf};  dly (N, N, 1, Nf) complex or None
+      data     (Nbl, Nt, Nf) complex64 / complex128
+      table    a CouplingPlan, or the (N, N) integer table with `out_rows`, the flat matrix positions of the output rows
+      double   E = [I] + Xd + Xd Xd, Xd = coupling o dly, formed first as a dense tensor (coupling_expand)
+    Differentiable once in coupling and data: gdata = fold(E^H G E), gcoupling = (G E V^H + G^H E V) o conj(dly) summed over
+    the broadcast axes, every sum by one thread in a fixed order (bit-identical from run to run).  No CPU path.
+    """
+    plan = table if isinstance(table, CouplingPlan) else CouplingPlan(table, out_rows, data.shape[0])
+    if double:
+        E = _CouplingExpand.apply(coupling.to(data.dtype), dly, add_I)
+        return _CouplingApply.apply(E, None, data, plan, False, prod)
+    return _CouplingApply.apply(coupling, dly, data, plan, add_I, prod)

@@ -678,6 +678,52 @@ int rime_vis_timeavg_bwd(int dtype, const void* gavg, const void* wgts, const vo
                          int Nf, int Nbin, int Nmem, void* gdata, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Antenna mutual coupling of visibilities (calibration.VisCoupling; reference calibration.py:1258-1586), single polarisation:
+ *     W = E V E^H (prod = BOTH),  E V (LEFT),  V E^H (RIGHT)         E = [I] + X o D   per (t, f), N x N complex
+ * on one batched complex product kernel (csrc/coupling.hip) whose operands are read, and whose results are written, in place:
+ *   x        complex T [N][N][Tm][Fm], Tm in {1, Nt}, Fm in {1, Nf} (1 broadcasts);  dly complex T [N][N][Nf] or NULL (ones)
+ *   data     complex T [Nbl][Nt][Nf];  out, gout complex T [Nout][Nt][Nf];  gdata as data;  gx as x
+ *   tab      int32 [N][N] (device): V[a][b] = data[row] for the word `row`, conj(data[row]) for `row | 1 << 30`, 0 for -1
+ *   otab     int32 [N][N] (device): W[a][b] is output row `row`, -1: not an output.  Every output row names one entry.
+ *   ftab     int32 [N][N] (device), backward: entry (a, b) holds the data row read unconjugated there, with 1 << 30 set when no
+ *            entry reads that row conjugated (an auto-correlation), -1 elsewhere; needed with gdata
+ * No (N^2, Nt, Nf) copy of the data is made and E is never materialised; the intermediate of a two-sided product lives in the
+ * caller's workspace: rime_coupling_workspace(dtype, N, Nt, Nf, Tm, Fm, prod, stage) bytes, stage RIME_COUPLING_FWD (T = E V
+ * for BOTH, else 0), RIME_COUPLING_BWD (T and P = G E for BOTH, plus one matrix when Tm != Nt or Fm != Nf) or
+ * RIME_COUPLING_EXPAND_BWD (one matrix when Tm != Nt or Fm != Nf); 0 for arguments the calls below reject.
+ * rime_coupling_bwd, with G the matrix that holds gout at the output entries and 0 elsewhere:
+ *     gV = E^H G E,  gdata[row(a, b)] = gV[a][b] + conj(gV[b][a]) (the first term alone when the word carries 1 << 30),
+ *     gE = G E V^H + G^H E V (LEFT: G V^H;  RIGHT: G^H V),  gx = gE o conj(dly), summed over t when Tm = 1 and over f when Fm = 1.
+ *   gdata or gx may be NULL (not computed).  Rows of gdata that ftab does not name are not written.
+ * rime_coupling_expand: the double-path matrix e [N][N][Nt][Nf] = [I] + Xd + Xd Xd, Xd = X o D, as a dense tensor to be passed
+ *   as x (with dly NULL, addI 0) to the calls above;  rime_coupling_expand_bwd: gx = (ge + ge Xd^H + Xd^H ge) o conj(dly),
+ *   summed over the broadcast axes.
+ * Every output element is summed over k in ascending order by one thread (two products of a sum one after the other), the
+ * broadcast sums t outer, f inner, ascending: no atomics, bit-reproducible.  float32 accumulates in float32, float64 in float64.
+ * Checked before any HIP call: RIME_EINVAL for a null pointer (dly may be null; gdata or gx, not both), an unknown dtype, prod
+ * or stage, N, Nt, Nf, Nbl or Nout < 1, Tm outside {1, Nt}, Fm outside {1, Nf}, addI outside {0, 1}; RIME_EWORKSPACE for a null
+ * or short workspace where one is needed.  The tables live on the device and are checked by the caller where they are built;
+ * the kernel treats a row outside [0, Nbl) / [0, Nout) as -1 and never reads or writes outside the tensors.
+ * ------------------------------------------------------------------------------------- */
+#define RIME_COUPLING_BOTH 0
+#define RIME_COUPLING_LEFT 1
+#define RIME_COUPLING_RIGHT 2
+#define RIME_COUPLING_FWD 0
+#define RIME_COUPLING_BWD 1
+#define RIME_COUPLING_EXPAND_BWD 2
+size_t rime_coupling_workspace(int dtype, int N, int Nt, int Nf, int Tm, int Fm, int prod, int stage);
+int rime_coupling_fwd(int dtype, const void* x, const void* dly, const void* data, const int* tab, const int* otab,
+                      int N, int Nbl, int Nout, int Nt, int Nf, int Tm, int Fm, int addI, int prod, void* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int rime_coupling_bwd(int dtype, const void* x, const void* dly, const void* data, const void* gout, const int* tab,
+                      const int* otab, const int* ftab, int N, int Nbl, int Nout, int Nt, int Nf, int Tm, int Fm,
+                      int addI, int prod, void* gdata, void* gx, void* workspace, size_t workspace_bytes, void* stream);
+int rime_coupling_expand(int dtype, const void* x, const void* dly, int N, int Nt, int Nf, int Tm, int Fm, int addI,
+                         void* e, void* stream);
+int rime_coupling_expand_bwd(int dtype, const void* x, const void* dly, const void* ge, int N, int Nt, int Nf, int Tm,
+                             int Fm, void* gx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
