@@ -106,6 +106,10 @@ SIGNATURES = {
     'rime_coupling_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'rime_coupling_expand': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rime_coupling_expand_bwd': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'rime_redcoupling_workspace': (_sz, [_i] * 4),
+    'rime_redcoupling_fwd': (_i, [_i] + [_vp] * 5 + [_i] * 8 + [_vp, _vp]),
+    'rime_redcoupling_bwd_data': (_i, [_i] + [_vp] * 6 + [_i] * 8 + [_vp, _vp]),
+    'rime_redcoupling_bwd_coupling': (_i, [_i] + [_vp] * 10 + [_i] * 11 + [_vp, _vp, _sz, _vp]),
 }
 
 

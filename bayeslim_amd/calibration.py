@@ -26,7 +26,11 @@ The CalData export is outside the hot path and not built.
 
 Mutual coupling: `VisCoupling` (:1258-1586) applies Vc = E V E^H, E = I + X o D, between the redundant-visibility and the
 gain stage through ops.coupling_apply, one batched complex product kernel that reads the visibility matrix from the data through
-an index table, builds E on the fly and writes only the baselines of the output.
+an index table, builds E on the fly and writes only the baselines of the output.  `RedVisCoupling` (:1588-2115) is the form
+fitted on a redundant array, Vc = A(eps) Vr + B(eps) conj(Vr) with one coefficient per coupling vector: ops.redcoupling_apply
+sums the non-zero first- and second-order terms from a flat entry list instead of the reference's two dense
+(Nbls_out, Nbls_in, Ntimes, Nfreqs) matrices; `gen_coupling_terms`, `configure_coupling_matrix_singlepath`, `cut_bl` and
+`CouplingInflate` (:2118-2175, 3047-3400) are its host side.
 """
 import copy
 
@@ -612,8 +616,8 @@ class VisCoupling(utils.Module, IndexCache):
     (Nant^2, Ntimes, Nfreqs) copy exists, E is built on the fly and the output of R is never modified in place; the gradients
     come from the same kernel in a fixed summation order (bit-identical from run to run).  As in the reference the `double`
     keyword of forward decides, self.double only when None is passed.  Single polarisation only; no CPU implementation.
-    Not built: RedVisCoupling, CouplingInflate, PartialRedVisInflate, CouplingExpand, configure_coupling_matrix_singlepath,
-    gen_coupling_terms.
+    The form fitted on a redundant array, with one coefficient per coupling vector (gen_coupling_terms), is RedVisCoupling;
+    CouplingInflate turns its parameters into the matrix used here.  Not built: PartialRedVisInflate, CouplingExpand.
     """
     def __init__(self, params, freqs, antpos, bls, R=None, parameter=True, p0=None, name=None, atol=1e-5, add_I=True,
                  prod='both', double=False):
@@ -762,6 +766,443 @@ class VisCoupling(utils.Module, IndexCache):
             for pr in (prs or []):
                 if pr is not None:
                     pr.push(device)
+
+
+# ---------------------------------------------------------------------------------------
+# mutual coupling of a redundant model (calibration.py:1588-2175, 3047-3400)
+# ---------------------------------------------------------------------------------------
+def _antvecs(antpos):
+    """(antenna keys, (Nant, 3) numpy positions in the dtype antpos holds) in the order of antpos"""
+    ants = list(antpos.keys())
+    return ants, np.stack([np.asarray(torch.as_tensor(antpos[a]).detach().cpu()) for a in ants])
+
+
+def _cut_matrix(vecs, min_len=None, max_len=None, min_EW=None, max_EW=None, min_NS=None, max_NS=None):
+    """cut_bl for every ordered antenna pair at once: cut[p, q] for the vector r_q - r_p"""
+    d = vecs[None, :, :] - vecs[:, None, :]
+    length, ew = np.linalg.norm(d, axis=-1), np.abs(d[..., 0])
+    cut = np.zeros(length.shape, dtype=bool)
+    if min_len is not None:
+        cut |= length < min_len
+    if max_len is not None:
+        cut |= length > max_len
+    if min_EW is not None:
+        cut |= ew < min_EW
+    if max_EW is not None:
+        cut |= ew > max_EW
+    if min_NS is not None:                               # the reference tests the East-West component here too (:3395-3398)
+        cut |= ew < min_NS
+    if max_NS is not None:
+        cut |= ew > max_NS
+    return cut
+
+
+def cut_bl(bl, antpos, bl_vecs=None, min_len=None, max_len=None, min_EW=None, max_EW=None, min_NS=None, max_NS=None):
+    """
+    True if the antenna pair `bl` is cut by its vector r_bl[1] - r_bl[0] (calibration.py:3342-3400): shorter than min_len,
+    longer than max_len, East-West extent below min_EW or above max_EW.  As in the reference the North-South limits are
+    compared with the East-West component as well.  bl_vecs: optional cache {bl: (vector, length)}.
+    """
+    if all(x is None for x in (min_len, max_len, min_EW, max_EW, min_NS, max_NS)):
+        return False
+    if bl_vecs is not None and bl in bl_vecs:
+        vec, vec_len = bl_vecs[bl]
+    else:
+        vec = antpos[bl[1]] - antpos[bl[0]]
+        vec_len = torch.linalg.norm(vec)
+        if bl_vecs is not None:
+            bl_vecs[bl] = vec, vec_len
+    ew = abs(vec[0])
+    return bool((min_len is not None and vec_len < min_len) or (max_len is not None and vec_len > max_len)
+                or (min_EW is not None and ew < min_EW) or (max_EW is not None and ew > max_EW)
+                or (min_NS is not None and ew < min_NS) or (max_NS is not None and ew > max_NS))
+
+
+def gen_coupling_terms(antpos, min_len=None, max_len=None, max_EW=None, max_NS=None, ants=None, no_auto_coupling=False,
+                       compress_to_red=False, redtol=1.0):
+    """
+    Coupling terms (ant_i, ant_j) to model and the index of every term along the Ncoupling axis of the parameters
+    (calibration.py:3246-3339): all ordered pairs of antpos whose vector r_j - r_i passes the cuts (length, |East-West|,
+    |North-South|), with ant_j in `ants` when given, without the autos under no_auto_coupling.  compress_to_red: one term
+    per unique vector within redtol (a pair and its reverse are different vectors); coupling_idx then maps every pair to the
+    term of its vector.  Returns (coupling_terms, coupling_idx).
+    """
+    assert isinstance(antpos, dict) or hasattr(antpos, 'keys')
+    keys, vecs = _antvecs(antpos)
+    d = vecs[None, :, :] - vecs[:, None, :]                          # d[i, j] = r_j - r_i
+    length = np.linalg.norm(d, axis=-1)
+    keep = np.ones(length.shape, dtype=bool)
+    if no_auto_coupling:
+        keep &= ~np.eye(len(keys), dtype=bool)
+    if ants is not None:
+        keep &= np.array([k in ants for k in keys], dtype=bool)[None, :]
+    if min_len is not None:
+        keep &= ~(length < min_len)
+    if max_len is not None:
+        keep &= ~(length > max_len)
+    if max_EW is not None:
+        keep &= ~(np.abs(d[..., 0]) > max_EW)
+    if max_NS is not None:
+        keep &= ~(np.abs(d[..., 1]) > max_NS)
+    ii, jj = np.nonzero(keep)                                        # row-major: the reference's loop order
+    coupling_terms = [(keys[i], keys[j]) for i, j in zip(ii, jj)]
+    coupling_idx = {c: i for i, c in enumerate(coupling_terms)}
+    if compress_to_red:
+        cvec = d[ii, jj]
+        red_vecs, first, red_idx = np.zeros((0, 3), dtype=cvec.dtype), [], []
+        for n, v in enumerate(cvec):                                 # first group within redtol, else a new one
+            match = np.nonzero(np.linalg.norm(red_vecs - v, axis=1) < redtol)[0]
+            if match.size:
+                red_idx.append(int(match[0]))
+            else:
+                red_idx.append(len(first))
+                red_vecs = np.concatenate([red_vecs, v[None]])
+                first.append(n)
+        coupling_idx = {c: red_idx[i] for i, c in enumerate(coupling_terms)}
+        coupling_terms = [coupling_terms[n] for n in first]
+    return coupling_terms, coupling_idx
+
+
+def configure_coupling_matrix_singlepath(antpos, bls, bl2red=None, no_auto_coupling=False, include_second_order=True,
+                                         min_len=None, max_len=None, max_EW=None, max_NS=None, second_max_len=None,
+                                         second_max_EW=None, second_max_NS=None, Nproc=None, Ntask=5, use_pathos=True):
+    """
+    Rows of the baseline-to-baseline matrix of single-path mutual coupling, Vc = E V E^H with E = I + X
+    (calibration.py:3052-3243).  For the output baseline (j, k) antenna i contributes the first-order terms eps_j_i V_ik and
+    conj(eps_k_i) V_ji and, with include_second_order, eps_j_i conj(eps_k_i') V_ii' for every i'.  Returns
+    Arows: {output baseline: {input baseline: ['eps_j_i', 'eps_k_i_conj', 'eps_j_i,eps_k_i2_conj', ...]}} with the
+    reference's keys, names and list order.  bl2red: physical baseline (both orientations) -> the redundant baseline that
+    stands for it; a visibility that it does not hold is dropped.  A term whose vector is cut (min_len, max_len, max_EW,
+    max_NS for the first order; min_len and second_max_* for both factors of the second) is left out, and so are the auto
+    terms under no_auto_coupling (of a second-order product only its conjugated factor is tested, as in the reference).
+    The cuts are evaluated for all antenna pairs at once with numpy; Nproc, Ntask and use_pathos are accepted and ignored.
+    """
+    keys, vecs = _antvecs(antpos)
+    where = {a: i for i, a in enumerate(keys)}
+    N = len(keys)
+    keep1 = ~_cut_matrix(vecs, min_len=min_len, max_len=max_len, max_EW=max_EW, max_NS=max_NS)
+    keep2 = ~_cut_matrix(vecs, min_len=min_len, max_len=second_max_len, max_EW=second_max_EW, max_NS=second_max_NS)
+    auto = np.eye(N, dtype=bool)
+    if no_auto_coupling:
+        keep1 &= ~auto
+    look = (lambda bl: bl2red.get(bl)) if bl2red else (lambda bl: bl)
+    Arows = {}
+    for bl in bls:
+        p0, p1 = where[bl[0]], where[bl[1]]
+        first0, first1 = keep1[p0], keep1[p1]
+        row = {}
+        if include_second_order:
+            sec0 = keep2[p0]
+            sec1 = np.nonzero(keep2[p1] & ~auto[p1] if no_auto_coupling else keep2[p1])[0]
+        for k in range(N):
+            ant = keys[k]
+            if first0[k]:
+                vis = look((ant, bl[1]))
+                if vis is not None:
+                    row.setdefault(vis, []).append('eps_{}_{}'.format(bl[0], ant))
+            if first1[k]:
+                vis = look((bl[0], ant))
+                if vis is not None:
+                    row.setdefault(vis, []).append('eps_{}_{}_conj'.format(bl[1], ant))
+            if include_second_order and sec0[k]:
+                for k2 in sec1:
+                    vis = look((ant, keys[k2]))
+                    if vis is not None:
+                        row.setdefault(vis, []).append('eps_{}_{},eps_{}_{}_conj'.format(bl[0], ant, bl[1], keys[k2]))
+        Arows[bl] = row
+    return Arows
+
+
+class CouplingInflate:
+    """
+    Inflates the parameters of a RedVisCoupling (one per coupling vector) to the Nants x Nants coupling matrix of a
+    VisCoupling, in the order of antpos (calibration.py:2118-2175): entry (i, j) takes the term whose vector matches
+    r_i - r_j within redtol, zero where none does.  vecs (Nterms, 3) ENU [m].  __call__(params (Npol, Npol, Nterms, Ntimes,
+    Nfreqs)) -> (Npol, Npol, Nants, Nants, Ntimes, Nfreqs) by one gather and a fill, without writing into its input.
+    """
+    def __init__(self, vecs, antpos, redtol=1.0):
+        self.vecs, self.antpos, self.redtol = vecs, antpos, redtol
+        self.ants, pos = _antvecs(antpos)
+        Nants = len(self.ants)
+        self.shape = (Nants, Nants)
+        v = np.asarray(torch.as_tensor(vecs).detach().cpu())
+        d = pos[:, None, :] - pos[None, :, :]                         # d[i, j] = r_i - r_j
+        match = np.linalg.norm(v[None, None, :, :] - d[:, :, None, :], axis=-1) <= redtol
+        self.idx = torch.as_tensor(np.where(match.any(axis=-1), match.argmax(axis=-1), 0).ravel(), dtype=torch.int64)
+        self.zeros = torch.as_tensor(~match.any(axis=-1).ravel())
+
+    def __call__(self, params):
+        shape = params.shape[:2] + self.shape + params.shape[-2:]
+        out = params.index_select(2, self.idx.to(params.device))
+        return out.masked_fill(self.zeros.to(params.device)[None, None, :, None, None], 0.0).reshape(shape)
+
+    def push(self, device):
+        self.idx = utils.push(self.idx, device)
+        self.zeros = utils.push(self.zeros, device)
+
+
+_RVC_TUPLES = ('unconj_param_unconj_vis', 'unconj_param_conj_vis', 'conj_param_unconj_vis', 'conj_param_conj_vis',
+               'sq_param_unconj_vis', 'sq_param_conj_vis')
+
+
+class RedVisCoupling(utils.Module, IndexCache):
+    """
+    Mutual coupling with a redundant visibility model as input and all physical baselines as output
+    (calibration.py:1588-2115):  Vc = A @ Vr + B @ conj(Vr),  A and B (Nbls_out, Nbls_in) matrices of the first-order terms
+    eps, conj(eps) and the second-order single-path terms eps conj(eps'), eps = R(params) o dly.  params has shape (1, 1,
+    Ncoupling, Ntimes | 1, Nfreqs | 1[, 2]) with one row per entry of coupling_terms ((i, j): eps_i_j, v_i <- v_i + eps_i_j v_j);
+    coupling_idx maps antenna pairs to rows (pass the one of gen_coupling_terms(..., compress_to_red=True) for one term per
+    unique vector).  bls_in: the baselines of the input (with use_reds the redundant baselines), bls_out those of the output,
+    each with ant2 >= ant1.  setup_coupling() must run before forward().
+
+    Where the reference fills two dense (Nbls_out, Nbls_in, Ntimes, Nfreqs) matrices and contracts them with einsum, forward
+    runs ops.redcoupling_apply on a flat list of the non-zero terms (ops.RedCouplingPlan): the zeroth-order term -- with
+    use_reds the inflation by redundancy -- is one more entry per output row, no matrix and no inflated copy exists, and the
+    gradients are summed in an order fixed by the plan (bit-identical from run to run).  The reference's indexed `+=` keeps
+    one of two terms of one kind that fall on the same matrix element; here they add.  With neither kind of first-order
+    term on a visibility (plain / conjugated) the reference skips its second-order terms too, and so does the plan.
+    Single polarisation; no CPU implementation.
+    """
+    def __init__(self, params, freqs, antpos, coupling_terms, bls_in, bls_out, coupling_idx=None, R=None, parameter=True,
+                 p0=None, name=None, atol=1e-5):
+        utils.Module.__init__(self, name=name)
+        self.params = torch.nn.Parameter(params) if parameter else params
+        self.p0 = p0
+        self.freqs = freqs
+        self.Nfreqs = len(freqs)
+        self.antpos = antpos
+        self.Nants = len(antpos)
+        self.c = 2.99792458e8
+        self.device = params.device
+        self.Npol = params.shape[0]
+        assert self.Npol == 1, "multi-pol not currently supported"
+        self.R = R if R is not None else VisModelResponse()
+        IndexCache.__init__(self, times=getattr(self.R, 'times', None), atol=atol)
+        self.clear_cache()
+        self.coupling_terms = coupling_terms
+        self.coupling_idx = coupling_idx if coupling_idx is not None else {c: i for i, c in enumerate(coupling_terms)}
+        self.Nterms = len(coupling_terms)
+        self.bls_in, self.bls_out = bls_in, bls_out
+        self.plan = None
+
+    def clear_cache(self):
+        """clear all caches, some come from IndexCache"""
+        self.clear_time_cache()
+        self.clear_bl_cache()
+        self.clear_vd_cache()
+
+    def clear_vd_cache(self):
+        self._vd = None
+
+    def __getstate__(self):
+        """pickle and deepcopy leave the cached output behind: after a forward its data is a node of an autograd graph"""
+        state = dict(self.__dict__)
+        state['_vd'] = None
+        return state
+
+    def setup_coupling(self, use_reds=True, copydata=False, redtol=1.0, include_second_order=True, min_len=None,
+                       max_len=None, max_EW=None, max_NS=None, second_max_len=None, second_max_EW=None, second_max_NS=None,
+                       min_dly=None, Nproc=None, Ntask=5, use_pathos=True):
+        """
+        Delay phasor and indexing of the forward model.  use_reds: bls_in are redundant baselines (else the physical ones,
+        bls_in == bls_out); copydata: kept for the reference's signature, the input is never modified; redtol [m] for the
+        redundancy; include_second_order, min_len, max_len, max_EW, max_NS, second_max_*: the terms to include, see
+        configure_coupling_matrix_singlepath; min_dly: shortest length [m] used for the coupling delay.  Sets `dly`
+        (1, 1, Nterms, 1, Nfreqs) = exp(2 pi i (f - f_0) / c * max(min_dly, |r_j - r_i|)), the reference's index tuples
+        unconj_param_unconj_vis, unconj_param_conj_vis, conj_param_unconj_vis, conj_param_conj_vis ((rows, columns, terms))
+        and sq_param_unconj_vis, sq_param_conj_vis ((rows, columns, element of every product, first and conjugated term)),
+        with use_reds `red_bl_inds`, and `plan`, the ops.RedCouplingPlan of all of them.  ValueError for an output baseline
+        with ant2 < ant1, a duplicate, or an antenna that is not in antpos.  Nproc, Ntask, use_pathos: ignored.
+        """
+        seen, known = set(), set(self.antpos.keys())
+        for bl in self.bls_out:
+            bl = tuple(bl)
+            if bl[0] not in known or bl[1] not in known:
+                raise ValueError('baseline %s names an antenna that is not in antpos' % (bl,))
+            if bl[1] < bl[0]:
+                raise ValueError('baseline %s: RedVisCoupling needs ant2 >= ant1' % (bl,))
+            if bl in seen:
+                raise ValueError('baseline %s appears twice' % (bl,))
+            seen.add(bl)
+        for ct in self.coupling_terms:
+            if ct[0] not in known or ct[1] not in known:
+                raise ValueError('coupling term %s names an antenna that is not in antpos' % (tuple(ct),))
+        self.use_reds, self.copydata = use_reds, copydata
+        bl2red = None
+        if use_reds:
+            reds, _, bl2red_idx, _, _, _, _ = telescope_model.build_reds(self.antpos, bls=self.bls_out, red_bls=self.bls_in,
+                                                                        redtol=redtol)
+            bl2red = {}
+            for k in bl2red_idx:
+                bl2red[k] = reds[bl2red_idx[k]][0]
+                bl2red[k[::-1]] = reds[bl2red_idx[k]][0][::-1]
+
+        # delay phasor between coupled antennas
+        keys, vecs = _antvecs(self.antpos)
+        where = {a: i for i, a in enumerate(keys)}
+        vecs = vecs.astype(np.float64)
+        length = np.array([np.linalg.norm(vecs[where[a2]] - vecs[where[a1]]) for a1, a2 in self.coupling_terms])
+        if min_dly is not None:
+            length = np.maximum(length, min_dly)
+        fr = np.asarray(torch.as_tensor(self.freqs).detach().cpu(), dtype=np.float64)
+        phase = 2 * np.pi * (fr - fr[0])[None, :] / self.c * length[:, None]
+        self.dly = torch.as_tensor(np.exp(1j * phase)[None, None, :, None, :]).to(dtype=utils._cfloat(), device=self.device)
+
+        Arows = configure_coupling_matrix_singlepath(self.antpos, bls=self.bls_out, bl2red=bl2red,
+                                                     include_second_order=include_second_order, min_len=min_len,
+                                                     max_len=max_len, max_EW=max_EW, max_NS=max_NS,
+                                                     second_max_len=second_max_len, second_max_EW=second_max_EW,
+                                                     second_max_NS=second_max_NS)
+        if use_reds:
+            for bl in self.bls_out:
+                if bl not in bl2red_idx:
+                    raise ValueError('output baseline %s is redundant with none of bls_in' % (tuple(bl),))
+            self.red_bl_inds = [bl2red_idx[bl] for bl in self.bls_out]
+        elif len(self.bls_in) != len(self.bls_out):
+            raise ValueError('without use_reds the input baselines are the output baselines')
+
+        # the index lists of the reference (:1788-1928), visiting only the columns a row names
+        first = {k: ([], [], []) for k in _RVC_TUPLES[:4]}
+        sq = {0: ([], [], [], [], []), 1: ([], [], [], [], [])}
+        counter = [0, 0]
+        cols = {}
+        for j, bli in enumerate(self.bls_in):
+            cols.setdefault(tuple(bli), []).append(j)
+        cidx = self.coupling_idx
+
+        def pair(name):
+            return tuple(int(a) for a in name.split('_')[1:3])
+
+        for i, blo in enumerate(self.bls_out):
+            Arow = Arows[blo]
+            js = set()
+            for key in Arow:
+                js.update(cols.get(key, ()))
+                js.update(cols.get(key[::-1], ()))
+            for j in sorted(js):
+                bli = tuple(self.bls_in[j])
+                for cv, key in ((0, bli), (1, bli[::-1])):
+                    if key not in Arow or (cv == 1 and bli[0] == bli[1]):
+                        continue
+                    appended = False
+                    for eps in Arow[key]:
+                        if ',' in eps:
+                            t1, t2 = eps.split(',')
+                            c1, c2 = pair(t1), pair(t2)
+                            if c1 not in cidx or c2 not in cidx:
+                                continue
+                            if not appended:
+                                sq[cv][0].append(i)
+                                sq[cv][1].append(j)
+                            sq[cv][2].append(counter[cv])
+                            sq[cv][3].append(cidx[c1])
+                            sq[cv][4].append(cidx[c2])
+                            appended = True
+                        else:
+                            c = pair(eps)
+                            if c not in cidx:
+                                continue
+                            lst = first[('conj_param_' if 'conj' in eps else 'unconj_param_') + ('conj_vis' if cv else 'unconj_vis')]
+                            lst[0].append(i)
+                            lst[1].append(j)
+                            lst[2].append(cidx[c])
+                    counter[cv] += appended
+        for k in _RVC_TUPLES[:4]:
+            setattr(self, k, tuple(torch.as_tensor(x, dtype=torch.int64) for x in first[k]))
+        self.sq_param_unconj_vis = tuple(torch.as_tensor(x, dtype=torch.int64) for x in sq[0])
+        self.sq_param_conj_vis = tuple(torch.as_tensor(x, dtype=torch.int64) for x in sq[1])
+        self.plan = self._build_plan()
+        self.clear_vd_cache()
+
+    def _build_plan(self):
+        """every term forward adds up, as one entry list: zeroth order, then per kind of visibility the first-order terms
+        and the second-order products (only where the reference builds that matrix at all)"""
+        Nout, Nin = len(self.bls_out), len(self.bls_in)
+        zero = np.asarray(self.red_bl_inds if self.use_reds else np.arange(Nout), dtype=np.int64)
+        row, col, cj = [np.arange(Nout)], [zero], [np.zeros(Nout, dtype=np.int64)]
+        a, b = [np.full(Nout, -1)], [np.full(Nout, -1)]
+        for cv, (un, co, sq) in enumerate((('unconj_param_unconj_vis', 'conj_param_unconj_vis', 'sq_param_unconj_vis'),
+                                           ('unconj_param_conj_vis', 'conj_param_conj_vis', 'sq_param_conj_vis'))):
+            un, co, sq = (tuple(np.asarray(x.cpu(), dtype=np.int64) for x in getattr(self, k)) for k in (un, co, sq))
+            if len(un[0]) == 0 and len(co[0]) == 0:
+                continue
+            none = np.full(len(un[0]), -1), np.full(len(co[0]), -1)
+            row += [un[0], co[0], sq[0][sq[2]]]
+            col += [un[1], co[1], sq[1][sq[2]]]
+            a += [un[2], none[1], sq[3]]
+            b += [none[0], co[2], sq[4]]
+            cj += [np.full(len(un[0]) + len(co[0]) + len(sq[2]), cv, dtype=np.int64)]
+        cat = lambda x: np.concatenate([np.asarray(y, dtype=np.int64) for y in x])
+        return ops.RedCouplingPlan(cat(row), cat(col), cat(cj), cat(a), cat(b), Nout, Nin, self.Nterms)
+
+    def index_params(self, params, times=None):
+        """overloads IndexCache.index_params: one time bin in params broadcasts"""
+        if times is not None and params.shape[-2] != 1:
+            params = IndexCache.index_params(self, params, times=times)
+        return params
+
+    def forward(self, vd, prior_cache=None, **kwargs):
+        """vd: VisData of shape (1, 1, Nbls_in, Ntimes, Nfreqs) holding bls_in in their order; returns a VisData of the
+        baselines bls_out with the coupled visibilities (cached between calls, with new data)"""
+        if getattr(self, 'plan', None) is None:
+            raise RuntimeError('RedVisCoupling: run setup_coupling() before forward()')
+        if not vd.data.is_cuda:
+            raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
+        if tuple(vd.data.shape[:3]) != (1, 1, self.plan.Nin):
+            raise ValueError('input of shape %s, RedVisCoupling was set up for (1, 1, %d, Ntimes, Nfreqs)'
+                             % (tuple(vd.data.shape), self.plan.Nin))
+        if getattr(self, '_vd', None) is None:
+            if self.use_reds:
+                take = lambda x: None if x is None else x.index_select(2, torch.as_tensor(self.red_bl_inds, device=x.device))
+                by_bl = vd.cov_axis in (None, 'bl')
+                self._vd = dataset.VisData()
+                self._vd.setup_meta(telescope=vd.telescope, antpos=vd.antpos)
+                self._vd.setup_data(self.bls_out, vd.times, vd.freqs, pol=vd.pol, data=None, flags=take(vd.flags),
+                                    cov=take(vd.cov) if by_bl else vd.cov, cov_axis=vd.cov_axis,
+                                    icov=take(vd.icov) if by_bl else vd.icov, history=vd.history)
+            else:
+                self._vd = vd.copy(copydata=False)
+        vout = self._vd
+        params = self.params if self.p0 is None else self.params + self.p0
+        coupling = self.R(params)
+        if getattr(self, '_hook_registry', None) is not None and coupling.requires_grad:
+            for r in self._hook_registry:
+                coupling.register_hook(r)
+        self.eval_prior(prior_cache, inp_params=self.params, out_params=coupling)
+        coupling = self.index_params(coupling, times=vd.times)
+        if not coupling.is_complex():
+            coupling = coupling.to(vd.data.dtype)
+        out = ops.redcoupling_apply(coupling[0, 0], self.dly[0, 0, :, 0], vd.data[0, 0], self.plan)
+        vout.data = out[None, None]
+        return vout
+
+    def push(self, device):
+        """push to a new device or dtype"""
+        if not isinstance(device, torch.dtype):
+            self.device = device
+            self.clear_vd_cache()
+            if isinstance(self._times, torch.Tensor):
+                self._times = utils.push(self._times, device)
+            for k in _RVC_TUPLES:
+                if hasattr(self, k):
+                    setattr(self, k, tuple(a.to(device) for a in getattr(self, k)))
+        if hasattr(self, 'dly'):
+            self.dly = utils.push(self.dly, device)
+        self.params = utils.push(self.params, device)
+        self.R.push(device)
+        if self.p0 is not None:
+            self.p0 = utils.push(self.p0, device)
+        for prs in (self.priors_inp_params, self.priors_out_params):
+            for pr in (prs or []):
+                if pr is not None:
+                    pr.push(device)
+
+    def get_coupling_hits(self):
+        """{coupling term: how often the index tuples name its row}, counted as the reference counts (calibration.py:2092-2115:
+        the second list of every first-order tuple and the second and third of the second-order ones)"""
+        lists = [np.asarray(getattr(self, k)[1].cpu()) for k in _RVC_TUPLES] + \
+                [np.asarray(getattr(self, k)[2].cpu()) for k in _RVC_TUPLES[4:]]
+        return {ct: int(sum((x == i).sum() for x in lists)) for i, ct in enumerate(self.coupling_terms)}
 
 
 # ---------------------------------------------------------------------------------------

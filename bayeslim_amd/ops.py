@@ -3015,3 +3015,173 @@ def coupling_apply(coupling, dly, data, table, out_rows=None, add_I=True, prod='
         E = _CouplingExpand.apply(coupling.to(data.dtype), dly, add_I)
         return _CouplingApply.apply(E, None, data, plan, False, prod)
     return _CouplingApply.apply(coupling, dly, data, plan, add_I, prod)
+
+
+# ---------------------------------------------------------------------------------------
+# mutual coupling of redundant visibilities: Vc = A(eps) Vr + B(eps) conj(Vr) on a sparse entry list (csrc/redcoupling.hip)
+# ---------------------------------------------------------------------------------------
+REDCOUPLING_SEG = 64                             # words of a segment of a term's list in the gradient of the coefficients
+REDCOUPLING_FLAG = 1 << 30                       # column word: the visibility is read conjugated; term word: role b
+
+
+class RedCouplingPlan:
+    """
+    Tables of rime_redcoupling_fwd / _bwd_data / _bwd_coupling, built and range-checked with numpy on the host (no GPU
+    needed) and cached per device as int32 tensors.  Entry e = (row[e], col[e], conj[e], a[e], b[e]) adds
+        (a >= 0 ? C[a] : 1) (b >= 0 ? conj(C[b]) : 1) (conj ? conj(data[col]) : data[col])        C = coupling o dly
+    to output row[e]; -1 for a or b means no factor.  The entries are kept sorted by row (stable), and three CSR orderings of
+    them, each ascending: `roff` [Nout + 1] by output row; `coff` [Nin + 1] / `cmem` [Nent] by input column; `toff`
+    [Nterms + 1] / `tmem` by coupling term, the words `e` (the term is a[e]) and `e | REDCOUPLING_FLAG` (it is b[e]), an entry
+    with a == b under both.  Every term's list is cut into segments of `seg` words: `segterm`, `segstart` [Nseg] and `tsoff`
+    [Nterms + 1], the segments of every term.  ValueError for arrays of different lengths, no entry, a row outside [0, Nout),
+    a column outside [0, Nin), a or b outside [-1, Nterms), a conj outside {0, 1}, 2^30 entries or more.
+    """
+    def __init__(self, row, col, conj, a, b, Nout, Nin, Nterms, seg=REDCOUPLING_SEG):
+        arrs = []
+        for name, x in (('row', row), ('col', col), ('conj', conj), ('a', a), ('b', b)):
+            x = np.asarray(x.cpu() if torch.is_tensor(x) else x).reshape(-1)
+            if x.dtype == bool:
+                x = x.astype(np.int64)
+            if x.size and not np.issubdtype(x.dtype, np.integer):
+                raise ValueError('%s must be an integer array' % name)
+            arrs.append(x.astype(np.int64))
+        row, col, conj, a, b = arrs
+        self.Nout, self.Nin, self.Nterms, self.seg = int(Nout), int(Nin), int(Nterms), int(seg)
+        self.Nent = int(row.size)
+        if any(x.size != self.Nent for x in arrs):
+            raise ValueError('row, col, conj, a and b must have one length')
+        if not 1 <= self.Nent < REDCOUPLING_FLAG:
+            raise ValueError('the plan needs between 1 and 2^30 - 1 entries')
+        if min(self.Nout, self.Nin, self.Nterms) < 1 or max(self.Nout, self.Nin) >= REDCOUPLING_FLAG or not 1 <= self.seg <= 1 << 20:
+            raise ValueError('Nout, Nin, Nterms must be positive and seg in [1, 2^20]')
+        if row.min() < 0 or row.max() >= self.Nout:
+            raise ValueError('entry row outside [0, %d)' % self.Nout)
+        if col.min() < 0 or col.max() >= self.Nin:
+            raise ValueError('entry column outside [0, %d)' % self.Nin)
+        if min(a.min(), b.min()) < -1 or max(a.max(), b.max()) >= self.Nterms:
+            raise ValueError('coupling term outside [-1, %d)' % self.Nterms)
+        if conj.min() < 0 or conj.max() > 1:
+            raise ValueError('conj must be 0 or 1')
+        order = np.argsort(row, kind='stable')
+        row, col, conj, a, b = (x[order] for x in (row, col, conj, a, b))
+        self.row, self.col, self.conj, self.a, self.b = row, col, conj, a, b
+        self.ent = np.stack([row, col | (conj * REDCOUPLING_FLAG), a, b], axis=1).astype(np.int32)
+        self.roff = _csr(row, self.Nout)[0]
+        self.coff, self.cmem = _csr(col, self.Nin)
+        term = np.stack([a, b], axis=1).reshape(-1)                         # (entry, role) in ascending order
+        word = np.stack([np.arange(self.Nent), np.arange(self.Nent) | REDCOUPLING_FLAG], axis=1).reshape(-1)
+        used = term >= 0
+        term, word = term[used], word[used]
+        self.toff, pos = _csr(term, self.Nterms)
+        self.tmem = word[pos].astype(np.int32)
+        self.Nmem = int(self.tmem.size)
+        count = np.diff(self.toff.astype(np.int64))
+        nseg = (count + self.seg - 1) // self.seg
+        tsoff = np.zeros(self.Nterms + 1, dtype=np.int64)
+        np.cumsum(nseg, out=tsoff[1:])
+        self.tsoff, self.Nseg = tsoff.astype(np.int32), int(tsoff[-1])
+        self.segterm = np.repeat(np.arange(self.Nterms), nseg).astype(np.int32)
+        self.segstart = (self.toff[self.segterm] + (np.arange(self.Nseg) - tsoff[self.segterm]) * self.seg).astype(np.int32)
+        self.term_counts = count
+
+    _TABLES = ('ent', 'roff', 'coff', 'cmem', 'toff', 'tmem', 'segterm', 'segstart', 'tsoff')
+
+    def tables(self, device):
+        """dict of the int32 tables on `device`, cached"""
+        key = str(torch.device(device))
+        tabs = self.__dict__.setdefault('_tabs', {})
+        if key not in tabs:
+            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous() for k in self._TABLES}
+        return tabs[key]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tabs', None)
+        return state
+
+
+def _redcoupling_operands(coupling, dly, data, plan):
+    """(x, d, v, Tm, Fm) contiguous in the dtype of the data"""
+    assert data.is_complex() and data.ndim == 3, 'complex data of shape (Nin, Ntimes, Nfreqs)'
+    assert coupling.is_complex() and coupling.ndim == 3, 'complex coupling of shape (Nterms, Ntimes | 1, Nfreqs | 1)'
+    v = data.detach().resolve_conj().contiguous()
+    Nin, Nt, Nf = v.shape
+    x = coupling.detach().resolve_conj().to(v.dtype).contiguous()
+    Nterms, Tm, Fm = x.shape
+    if Nin != plan.Nin or Nterms != plan.Nterms:
+        raise ValueError('data of %d rows and coupling of %d terms, the plan has %d and %d' % (Nin, Nterms, plan.Nin, plan.Nterms))
+    if Tm not in (1, Nt) or Fm not in (1, Nf):
+        raise ValueError('coupling of (%d, %d) times and channels against data of (%d, %d)' % (Tm, Fm, Nt, Nf))
+    d = None
+    if dly is not None:
+        assert dly.is_complex() and tuple(dly.shape) == (Nterms, Nf), 'complex dly of shape (Nterms, Nfreqs)'
+        d = dly.detach().resolve_conj().to(v.dtype).contiguous()
+    return x, d, v, Tm, Fm
+
+
+def _cptr(t):
+    return _ptr(torch.view_as_real(t)) if t is not None else _ptr(None)
+
+
+class _RedCouplingApply(torch.autograd.Function):
+    """out = sum of the plan's entries; saves coupling, dly and data, the coefficients are rebuilt in the backward kernels"""
+    @staticmethod
+    def forward(ctx, coupling, dly, data, plan):
+        _require_cuda(coupling, dly, data)
+        x, d, v, Tm, Fm = _redcoupling_operands(coupling, dly, data, plan)
+        _, Nt, Nf = v.shape
+        code, _ = _real_dtype(v)
+        T = plan.tables(v.device)
+        out = torch.empty((plan.Nout, Nt, Nf), dtype=v.dtype, device=v.device)
+        rc = lib.rime_redcoupling_fwd(code, _cptr(x), _cptr(d), _cptr(v), _ptr(T['ent']), _ptr(T['roff']), plan.Nout, plan.Nin,
+                                      plan.Nterms, plan.Nent, Nt, Nf, Tm, Fm, _cptr(out), _stream())
+        check(rc, 'rime_redcoupling_fwd')
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(x, d, v)
+            ctx.plan, ctx.xdtype, ctx.ddtype = plan, coupling.dtype, data.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, d, v = ctx.saved_tensors
+        plan = ctx.plan
+        _, Nt, Nf = v.shape
+        _, Tm, Fm = x.shape
+        g = gout.detach().resolve_conj().to(v.dtype).contiguous()
+        code, _ = _real_dtype(v)
+        T = plan.tables(v.device)
+        dims = (plan.Nout, plan.Nin, plan.Nterms, plan.Nent)
+        gx = gd = None
+        if ctx.needs_input_grad[2]:
+            gd = torch.empty_like(v)
+            rc = lib.rime_redcoupling_bwd_data(code, _cptr(x), _cptr(d), _cptr(g), _ptr(T['ent']), _ptr(T['coff']), _ptr(T['cmem']),
+                                               *dims, Nt, Nf, Tm, Fm, _cptr(gd), _stream())
+            check(rc, 'rime_redcoupling_bwd_data')
+            if gd.dtype != ctx.ddtype:
+                gd = gd.to(ctx.ddtype)
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            nbytes = lib.rime_redcoupling_workspace(code, plan.Nseg, Nt, Nf)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=v.device) if nbytes else None
+            seg = [_ptr(T[k]) if plan.Nseg else _ptr(None) for k in ('tmem', 'segterm', 'segstart')]
+            rc = lib.rime_redcoupling_bwd_coupling(code, _cptr(x), _cptr(d), _cptr(v), _cptr(g), _ptr(T['ent']), _ptr(T['toff']),
+                                                   seg[0], seg[1], seg[2], _ptr(T['tsoff']), *dims, plan.Nmem, plan.Nseg,
+                                                   plan.seg, Nt, Nf, Tm, Fm, _cptr(gx), _ptr(ws), nbytes, _stream())
+            check(rc, 'rime_redcoupling_bwd_coupling')
+            if gx.dtype != ctx.xdtype:
+                gx = gx.to(ctx.xdtype)
+        return gx, None, gd, None
+
+
+def redcoupling_apply(coupling, dly, data, plan):
+    """
+    Coupled visibilities of a redundant model, out[i] = sum over the entries (i, j, conj, a, b) of the RedCouplingPlan of
+    (a >= 0 ? C[a] : 1) (b >= 0 ? conj(C[b]) : 1) (conj ? conj(data[j]) : data[j]) with C = coupling o dly built on the fly
+    (rime_redcoupling_fwd): no (Nout, Nin, Nt, Nf) matrix is formed.
+      coupling (Nterms, Tm, Fm) complex, Tm in {1, Nt}, Fm in {1, Nf};  dly (Nterms, Nf) complex or None
+      data     (Nin, Nt, Nf) complex64 / complex128  ->  (Nout, Nt, Nf)
+    Differentiable once in coupling and data; every gradient sum runs in an order fixed by the plan, without atomics
+    (bit-identical from run to run); columns that nothing reads and terms without an entry get zeros.  No CPU path.
+    """
+    return _RedCouplingApply.apply(coupling, dly, data, plan)

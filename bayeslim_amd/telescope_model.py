@@ -336,11 +336,13 @@ class ArrayModel(utils.Module, utils.AntposDict):
         return utils.AntposDict(self.ants, self.antvecs)
 
 
-def build_reds(antpos, bls=None, redtol=1.0, min_len=None, max_len=None, skip_reds=False, **kw):
+def build_reds(antpos, bls=None, redtol=1.0, min_len=None, max_len=None, skip_reds=False, red_bls=None, **kw):
     """
     Group baselines (autos + all i<j pairs unless `bls` is given) into redundant sets by
     baseline vector within `redtol` metres; groups sorted by length + angle*redtol/180 and
     baselines sorted inside a group, as the reference does (telescope_model.py:693-942).
+    red_bls: the groups are instead put in the order of these redundant baselines (each names the group that holds it or
+    its conjugate; one that names no group is passed over, a group that none names is dropped; :910-919).
     Returns (reds, redvecs, bl2red, bls, redlens, redangs, redtags).
     """
     ants = list(antpos.keys())
@@ -389,7 +391,19 @@ def build_reds(antpos, bls=None, redtol=1.0, min_len=None, max_len=None, skip_re
         if abs(v[1]) < redtol:
             ang = 0.0
         ra.append(ang)
-    order = np.argsort(np.array(rl) + np.array(ra) * redtol / 180.0, kind='stable') if len(rl) else []
+    if red_bls is not None:
+        member = {}
+        for i, r in enumerate(reds):
+            for bl in r:
+                member.setdefault(bl, i)
+        order = []
+        for rbl in red_bls:
+            rbl = tuple(rbl)
+            i = [member[b] for b in (rbl, utils.conjbl(rbl)) if b in member]
+            if i:
+                order.append(min(i))
+    else:
+        order = np.argsort(np.array(rl) + np.array(ra) * redtol / 180.0, kind='stable') if len(rl) else []
     reds = [sorted(reds[i]) for i in order]
     redvecs = [torch.as_tensor(rvecs[i]) for i in order]
     redlens = [rl[i] for i in order]

@@ -724,6 +724,45 @@ int rime_coupling_expand_bwd(int dtype, const void* x, const void* dly, const vo
                              int Fm, void* gx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Mutual coupling of redundant visibilities (calibration.RedVisCoupling; reference calibration.py:1588-2115), single
+ * polarisation:  Vc = A(eps) Vr + B(eps) conj(Vr)  without the two dense (Nout, Nin, Nt, Nf) matrices (csrc/redcoupling.hip).
+ * What the forward adds up is one list of entries, int32 ent [Nent][4] (device) = (i, j | flag << 30, a, b), sorted by i:
+ *     out[i][t][f] = sum over the entries of row i, ascending, of  coef (flag ? conj(data[j][t][f]) : data[j][t][f])
+ *     coef = (a >= 0 ? C[a] : 1) (b >= 0 ? conj(C[b]) : 1),   C[c][t][f] = x[c][tm][fm] dly[c][f]
+ *   x      complex T [Nterms][Tm][Fm], Tm in {1, Nt}, Fm in {1, Nf} (1 broadcasts);  dly complex T [Nterms][Nf] or NULL (ones)
+ *   data   complex T [Nin][Nt][Nf];  out, gout complex T [Nout][Nt][Nf];  gdata as data;  gx as x
+ *   roff   int32 [Nout + 1]: the entries of every row (ent is in row order)
+ *   coff   int32 [Nin + 1], cmem int32 [Nent]: the entries that read every column, ascending
+ *   toff   int32 [Nterms + 1], tmem int32 [Nmem]: per term the words `entry` (the term is a of the entry) and
+ *          `entry | 1 << 30` (it is b), ascending in (entry, role); an entry with a == b is listed under both
+ *   segterm, segstart int32 [Nseg], tsoff int32 [Nterms + 1]: every term's list cut into segments of `seg` words: the term and
+ *          the first position in tmem of every segment, and the segments of every term
+ * rime_redcoupling_bwd_data:      gdata[j] = sum over the readers of j of  conj(coef) gout[i]  (flag 0),  coef conj(gout[i])  (1);
+ *   every element of gdata is written.
+ * rime_redcoupling_bwd_coupling:  gx[c] = conj(dly[c]) sum over the words of term c of  conj(w) gout[i],  w = conj(C[b]) v  (role a)
+ *   or  w' conj(gout[i]),  w' = C[a] v  (role b), v the visibility as the entry reads it; summed over t when Tm = 1 and over f
+ *   when Fm = 1.  One wave adds the words of a segment in ascending order into the workspace (rime_redcoupling_workspace bytes:
+ *   Nseg Nt Nf complex), then per (term, tm, fm) wave w of a block adds the segments w, w + 4, ... in ascending order (t outer
+ *   of f), the lanes by a butterfly when Fm = 1, and wave 0 the four wave sums.  Terms without a word get zeros.
+ * No atomics; every sum has an order fixed by the tables: bit-reproducible.  float32 accumulates in float32, float64 in float64.
+ * Checked before any launch: RIME_EINVAL for a null pointer (dly may be null; tmem, segterm, segstart when Nmem = Nseg = 0), an
+ * unknown dtype, Nout, Nin, Nterms, Nent, Nt or Nf < 1, Nout, Nin or Nent >= 2^30, Tm outside {1, Nt}, Fm outside {1, Nf}, Nmem or
+ * Nseg < 0, Nseg > Nmem, one of Nmem and Nseg zero alone, seg outside [1, 2^20]; RIME_EWORKSPACE for a null or short workspace
+ * where one is needed.  The tables live on the device and are checked by the caller where they are built; the kernels skip every
+ * word that points outside and never read or write outside the tensors.
+ * ------------------------------------------------------------------------------------- */
+size_t rime_redcoupling_workspace(int dtype, int Nseg, int Nt, int Nf);
+int rime_redcoupling_fwd(int dtype, const void* x, const void* dly, const void* data, const int* ent, const int* roff,
+                         int Nout, int Nin, int Nterms, int Nent, int Nt, int Nf, int Tm, int Fm, void* out, void* stream);
+int rime_redcoupling_bwd_data(int dtype, const void* x, const void* dly, const void* gout, const int* ent, const int* coff,
+                              const int* cmem, int Nout, int Nin, int Nterms, int Nent, int Nt, int Nf, int Tm, int Fm,
+                              void* gdata, void* stream);
+int rime_redcoupling_bwd_coupling(int dtype, const void* x, const void* dly, const void* data, const void* gout, const int* ent,
+                                  const int* toff, const int* tmem, const int* segterm, const int* segstart, const int* tsoff,
+                                  int Nout, int Nin, int Nterms, int Nent, int Nmem, int Nseg, int seg, int Nt, int Nf, int Tm,
+                                  int Fm, void* gx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
