@@ -9,6 +9,7 @@ tensors and raises otherwise -- there is no CPU path in the product.
   interp_gather: out[..., p] = sum_k w[p,k] m[..., inds[p,k]]    utils.py:815-861
   alm2pix      : out = Re(alm @ Ylm)                             sph_harm.py:1342-1372
 """
+import contextlib
 import ctypes
 import os
 
@@ -40,12 +41,88 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _cptr(t):
+    """a complex tensor as the (re, im) pairs the library reads; None: the null pointer"""
+    return _ptr(torch.view_as_real(t) if t is not None else None)
+
+
+def _dtype_code(dtype):
+    if dtype in (torch.float32, torch.complex64):
+        return RIME_F32
+    if dtype in (torch.float64, torch.complex128):
+        return RIME_F64
+    raise TypeError('unsupported dtype %s' % dtype)
+
+
 def _real_dtype(t):
-    if t.dtype in (torch.float32, torch.complex64):
-        return RIME_F32, torch.float32
-    if t.dtype in (torch.float64, torch.complex128):
-        return RIME_F64, torch.float64
-    raise TypeError('unsupported dtype %s' % t.dtype)
+    code = _dtype_code(t.dtype)
+    return code, (torch.float32 if code == RIME_F32 else torch.float64)
+
+
+def _dense(t, dtype=None):
+    """t detached, its conjugation resolved, in `dtype` (None: its own) and contiguous: an operand read through one pointer"""
+    t = t.detach().resolve_conj()
+    return (t if dtype is None else t.to(dtype)).contiguous()
+
+
+def _host_array(x, flat=False, integer=None):
+    """x (a tensor on any device, an array or a sequence) as a numpy array on the host; flat: as one axis; integer: the
+    ValueError message for a non-empty array of another kind (an empty sequence arrives as float64 and passes)"""
+    a = np.asarray(x.detach().cpu() if torch.is_tensor(x) else x)
+    if flat:
+        a = a.reshape(-1)
+    if integer is not None and a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(integer)
+    return a
+
+
+def _workspace(nbytes, device, floor=0):
+    """(buffer, its size) for a rime_*_workspace() answer.  floor=16: the callers whose kernels always get a pointer; floor=0:
+    those that pass the null pointer with zero bytes (_ptr(None)).  Which one a call takes is part of its C contract."""
+    n = max(int(nbytes), floor)
+    return (torch.empty(n, dtype=torch.uint8, device=device) if n else None), n
+
+
+def _timed(name, *fields):
+    """context that appends (name, start event, end event) + fields + what the body puts into the list it is given to
+    PROFILE, read once on entry.  PROFILE None: no event, the body is given None.  A body that raises records nothing."""
+    prof = PROFILE
+    return _NOT_TIMED if prof is None else _record(prof, name, fields)
+
+
+_NOT_TIMED = contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def _record(prof, name, fields):
+    e0, e1, late = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), []
+    e0.record()
+    yield late
+    e1.record()
+    prof.append((name, e0, e1) + fields + tuple(late))
+
+
+class _IndexPlan:
+    """
+    Base of the plans built with numpy on the host: the attributes named in `_TABLES` as int32 tensors, made on first use per
+    device, kept in self.__dict__['_tabs'] (LMPlan keeps its keyed tables there too) and dropped on pickling and copies.
+    """
+    _TABLES = ()
+
+    def _cache(self):
+        return self.__dict__.setdefault('_tabs', {})
+
+    def tables(self, device):
+        """dict of the int32 tables on `device`, cached"""
+        key, tabs = str(torch.device(device)), self._cache()
+        if key not in tabs:
+            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous() for k in self._TABLES}
+        return tabs[key]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_tabs', None)
+        return state
 
 
 def pad_to_tile(n):
@@ -794,8 +871,7 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
             amax = torch.maximum(hi, -lo)
             rowmin = [lo.permute(1, 2, 0, 3).contiguous()]
             scale = _pow2_scale(amax.permute(1, 2, 0, 3)).contiguous()             # (Nmp, Npp, Nt, Nf)
-        nbytes = lib.rime_fringe_ant_workspace(Nbl, Nt, Nf, geom.Pstride)
-        ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        ws, _ = _workspace(lib.rime_fringe_ant_workspace(Nbl, Nt, Nf, geom.Pstride), dev, 16)
         two_pass = [blk for blk in blocks if cplx and blk['fwd_cpass'] == 0]
         tmp = torch.empty((Nbl, Nt, Nf, 2), dtype=torch.float32, device=dev) if two_pass else None
 
@@ -824,8 +900,7 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
                 out[pp][..., 1] += tmp[..., 0]
     else:
         # inp: gvis as real (Npp, Nbl, Nt, Nf, 2); out: gpsky float32 view with psky's strides
-        nbytes = lib.rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)
-        ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        ws, _ = _workspace(lib.rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf), dev, 16)
         gvt = ws[:Nt * Nf * 2 * Nbl * 4].view(torch.float32).view(Nt * Nf, 2 * Nbl)    # what bwd_prepare writes
         two_pass = [blk for blk in blocks if cplx and blk['cpass'] == 0]
         for pp in range(Npp):
@@ -998,37 +1073,26 @@ def _fringe_algorithmic_bytes(geom, a, b):
 
 def _fringe_call(geom, backward, inp, out, Npp, cplx, strides=None):
     if geom.ant is not None and inp.dtype == torch.float32 and strides is not None:
-        prof = PROFILE
-        if prof is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        flops = _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx)
-        if prof is not None:
-            e1.record()
-            prof.append(('fringe_ant_bwd_kernel' if backward else 'fringe_ant_fwd_kernel', e0, e1, geom.elements, flops,
-                         _fringe_algorithmic_bytes(geom, inp, out)))
+        with _timed('fringe_ant_bwd_kernel' if backward else 'fringe_ant_fwd_kernel', geom.elements) as late:
+            flops = _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx)
+            if late is not None:
+                late += (flops, _fringe_algorithmic_bytes(geom, inp, out))
         return
     code, rdt = _real_dtype(inp)
     fn = lib.rime_fringe_sum_bwd if backward else lib.rime_fringe_sum_fwd
-    nbytes = lib.rime_fringe_sum_workspace(code, geom.Nbl, geom.Nt, geom.Nf, geom.Pstride,
-                                           geom.Nmp, Npp, int(cplx), int(backward))
-    ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=inp.device)
+    ws, nbytes = _workspace(lib.rime_fringe_sum_workspace(code, geom.Nbl, geom.Nt, geom.Nf, geom.Pstride,
+                                                          geom.Nmp, Npp, int(cplx), int(backward)), inp.device, 16)
     uniform = int(geom.uniform)
     if uniform == 2 and code == RIME_F64 and geom.nu_phi >= NU_F64_PHI:
         uniform = 0
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = fn(code, _ptr(geom.blvecs), _ptr(geom.sdir), _ptr(geom.freqs), _ptr(inp),
-            geom.mp_offsets, _ptr(geom.bl_order), geom.Nbl, geom.Nt, geom.Nf, geom.Pstride,
-            geom.Nmp, Npp, int(cplx), geom.sign, uniform, geom.f0, geom.df,
-            geom.max_blen, strides, _ptr(out), _ptr(ws), ws.numel(), _stream())
-    check(rc, 'rime_fringe_sum_bwd' if backward else 'rime_fringe_sum_fwd')
-    if prof is not None:
-        e1.record()
-        prof.append(('fringe_bwd_kernel' if backward else 'fringe_fwd_kernel', e0, e1, geom.elements, 0,
-                     _fringe_algorithmic_bytes(geom, inp, out)))
+    with _timed('fringe_bwd_kernel' if backward else 'fringe_fwd_kernel', geom.elements, 0) as late:
+        rc = fn(code, _ptr(geom.blvecs), _ptr(geom.sdir), _ptr(geom.freqs), _ptr(inp),
+                geom.mp_offsets, _ptr(geom.bl_order), geom.Nbl, geom.Nt, geom.Nf, geom.Pstride,
+                geom.Nmp, Npp, int(cplx), geom.sign, uniform, geom.f0, geom.df,
+                geom.max_blen, strides, _ptr(out), _ptr(ws), nbytes, _stream())
+        check(rc, 'rime_fringe_sum_bwd' if backward else 'rime_fringe_sum_fwd')
+        if late is not None:
+            late.append(_fringe_algorithmic_bytes(geom, inp, out))
 
 
 def _npp_chunks(Npp, cplx):
@@ -1441,11 +1505,9 @@ class _BeamSkyProduct(torch.autograd.Function):
         g = g.contiguous()
         T1 = torch.empty((Q, R), dtype=b.dtype, device=b.device)
         gsky = torch.empty((R, Npix), dtype=b.dtype, device=b.device)
-        nws = int(lib.rime_beam_sky_bwd_workspace(code, R, Npix, Nt))
-        ws = torch.empty(nws, dtype=torch.uint8, device=b.device) if nws else None
+        ws, nws = _workspace(lib.rime_beam_sky_bwd_workspace(code, R, Npix, Nt), b.device)
         rc = lib.rime_beam_sky_bwd(code, _ptr(g), _ptr(b), _ptr(k), _ptr(st.inds), _ptr(st.weights(rdt)), _ptr(cut),
-                                   _ptr(pos), R, Npb, Npix, Nt, Ps, st.Nnn, _ptr(T1), _ptr(gsky),
-                                   _ptr(ws) if ws is not None else None, nws, _stream())
+                                   _ptr(pos), R, Npb, Npix, Nt, Ps, st.Nnn, _ptr(T1), _ptr(gsky), _ptr(ws), nws, _stream())
         check(rc, 'rime_beam_sky_bwd')
         gmT = torch.empty((Npb, R), dtype=b.dtype, device=b.device)
         rc = lib.rime_interp_scatter_bwd(code, 0, _ptr(T1), _ptr(st.csr_ptr), _ptr(st.csr_src), _ptr(st.weights(rdt)),
@@ -1477,9 +1539,8 @@ class _Chisq(torch.autograd.Function):
         d = None if data is None else data.detach().to(p.dtype).expand_as(p).contiguous()
         w = None if icov is None else icov.detach().to(rdt).expand_as(p).contiguous()
         out = torch.empty((), dtype=rdt, device=p.device)
-        ws = torch.empty(int(lib.rime_chisq_workspace()), dtype=torch.uint8, device=p.device)
-        rc = lib.rime_chisq_fwd(code, _ptr(torch.view_as_real(p)), _ptr(torch.view_as_real(d)) if d is not None else None,
-                                _ptr(w) if w is not None else None, p.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream())
+        ws, nws = _workspace(lib.rime_chisq_workspace(), p.device)
+        rc = lib.rime_chisq_fwd(code, _cptr(p), _cptr(d), _ptr(w), p.numel(), _ptr(out), _ptr(ws), nws, _stream())
         check(rc, 'rime_chisq_fwd')
         ctx.saved = (p, d, w)
         return out
@@ -1490,9 +1551,7 @@ class _Chisq(torch.autograd.Function):
         code, rdt = _real_dtype(p)
         gp = torch.empty_like(p)
         gg = g.detach().to(rdt).reshape(1).contiguous()
-        rc = lib.rime_chisq_bwd(code, _ptr(torch.view_as_real(p)), _ptr(torch.view_as_real(d)) if d is not None else None,
-                                _ptr(w) if w is not None else None, _ptr(gg), p.numel(),
-                                _ptr(torch.view_as_real(gp)), _stream())
+        rc = lib.rime_chisq_bwd(code, _cptr(p), _cptr(d), _ptr(w), _ptr(gg), p.numel(), _cptr(gp), _stream())
         check(rc, 'rime_chisq_bwd')
         return gp, None, None
 
@@ -1697,16 +1756,15 @@ class _Alm2Pix(torch.autograd.Function):
         R = int(np.prod(lead)) if len(lead) else 1
         out = torch.empty(lead + (Npix,), dtype=rdt, device=a.device)
         ys = _ylm_scale(Ylm) if (rdt == torch.float32 and ALM_SPLIT_F16) else 0.0
-        nbytes = lib.rime_alm2pix_fwd_workspace(code, R, Nc, Npix) if ys > 0 else 0
-        ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=a.device)
+        ws, nws = _workspace(lib.rime_alm2pix_fwd_workspace(code, R, Nc, Npix) if ys > 0 else 0, a.device, 16)
         packed = _ylm_packed(Ylm, Y, ys, 0) if ys > 0 else None
         if packed is not None:
             rc = lib.rime_alm2pix_fwd_packed(_ptr(torch.view_as_real(a)), _ptr(packed), ys, R, Nc, Npix, _ptr(out),
-                                             _ptr(ws), ws.numel(), _stream())
+                                             _ptr(ws), nws, _stream())
             check(rc, 'rime_alm2pix_fwd_packed')
         else:
             rc = lib.rime_alm2pix_fwd(code, _ptr(torch.view_as_real(a)), _ptr(torch.view_as_real(Y)), ys,
-                                      R, Nc, Npix, _ptr(out), _ptr(ws), ws.numel(), _stream())
+                                      R, Nc, Npix, _ptr(out), _ptr(ws), nws, _stream())
             check(rc, 'rime_alm2pix_fwd')
         # the packed-copy cache lives on the CALLER's tensor object: a weak reference finds it again in the backward without
         # keeping that object (and its two packed buffers) alive through the graph
@@ -1722,17 +1780,16 @@ class _Alm2Pix(torch.autograd.Function):
         Nc, Npix = Y.shape
         ga = torch.empty(ctx.shape, dtype=ctx.dtype, device=g.device)
         R = int(np.prod(ctx.shape[:-1])) if len(ctx.shape) > 1 else 1
-        nbytes = lib.rime_alm2pix_bwd_workspace(code, R, Nc, Npix)
-        ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=g.device)
+        ws, nws = _workspace(lib.rime_alm2pix_bwd_workspace(code, R, Nc, Npix), g.device, 16)
         owner = ctx.Ylm()
         packed = _ylm_packed(owner, Y, ctx.ys, 1) if (ctx.ys > 0 and owner is not None) else None
         if packed is not None:
             rc = lib.rime_alm2pix_bwd_packed(_ptr(g), _ptr(packed), ctx.ys, R, Nc, Npix,
-                                             _ptr(torch.view_as_real(ga)), _ptr(ws), ws.numel(), _stream())
+                                             _ptr(torch.view_as_real(ga)), _ptr(ws), nws, _stream())
             check(rc, 'rime_alm2pix_bwd_packed')
         else:
             rc = lib.rime_alm2pix_bwd(code, _ptr(g), _ptr(torch.view_as_real(Y)), ctx.ys, R, Nc, Npix,
-                                      _ptr(torch.view_as_real(ga)), _ptr(ws), ws.numel(), _stream())
+                                      _ptr(torch.view_as_real(ga)), _ptr(ws), nws, _stream())
             check(rc, 'rime_alm2pix_bwd')
         return ga, None
 
@@ -1796,17 +1853,10 @@ class SFBPlan:
 
 
 def _sfb_call(fn, name, inp, plan, tiles, cplx, B, res):
-    code = RIME_F32 if plan.dtype == torch.float32 else RIME_F64
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = fn(code, int(cplx), _ptr(inp), _ptr(plan.g), _ptr(plan.blocks), _ptr(plan.cols), _ptr(tiles), plan.Nblk,
-            tiles.shape[0], B, plan.Nlmn, plan.Nr, plan.Nlm, _ptr(res), _stream())
-    check(rc, name)
-    if prof is not None:
-        e1.record()
-        prof.append((name.replace('rime_', '') + '_kernel', e0, e1, 2 * int(cplx + 1) * B * plan.Nr * plan.Nlmn))
+    with _timed(name.replace('rime_', '') + '_kernel', 2 * int(cplx + 1) * B * plan.Nr * plan.Nlmn):
+        rc = fn(_dtype_code(plan.dtype), int(cplx), _ptr(inp), _ptr(plan.g), _ptr(plan.blocks), _ptr(plan.cols), _ptr(tiles),
+                plan.Nblk, tiles.shape[0], B, plan.Nlmn, plan.Nr, plan.Nlm, _ptr(res), _stream())
+        check(rc, name)
 
 
 class _SFBRadial(torch.autograd.Function):
@@ -1875,7 +1925,7 @@ def filt_tables(M, K, residual=False, input_idx=None):
     M, K = int(M), int(K)
     idx = None
     if input_idx is not None:
-        idx = np.asarray(input_idx.detach().cpu() if isinstance(input_idx, torch.Tensor) else input_idx)
+        idx = _host_array(input_idx)
         if idx.dtype == bool:
             if idx.shape != (K,):
                 raise ValueError('boolean input_idx of shape %s, the filtered axis has %d samples' % (idx.shape, K))
@@ -1982,17 +2032,11 @@ def _filt_call(plan, direction, x, y, tiles, npass):
     M, K = (plan.M, plan.K) if direction == 'fwd' else (plan.K, plan.M)
     Nx, Ny = x.shape[-1], y.shape[-1]
     nlines = x.numel() // Nx
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib.rime_filt_apply(RIME_F32 if plan.dtype == torch.float32 else RIME_F64, int(plan.cplx), _ptr(x), _ptr(plan.W[direction]),
-                             _ptr(ic), _ptr(oc), _ptr(base), _ptr(tiles), tiles.shape[0], npass, plan.Nfilt, M, K, Nx, Ny,
-                             nlines, s, _ptr(y), _stream())
-    check(rc, 'rime_filt_apply')
-    if prof is not None:
-        e1.record()
-        prof.append(('filt_kernel', e0, e1, 2 * (4 if plan.cplx else 2) * nlines * M * K))
+    with _timed('filt_kernel', 2 * (4 if plan.cplx else 2) * nlines * M * K):
+        rc = lib.rime_filt_apply(_dtype_code(plan.dtype), int(plan.cplx), _ptr(x), _ptr(plan.W[direction]),
+                                 _ptr(ic), _ptr(oc), _ptr(base), _ptr(tiles), tiles.shape[0], npass, plan.Nfilt, M, K, Nx, Ny,
+                                 nlines, s, _ptr(y), _stream())
+        check(rc, 'rime_filt_apply')
 
 
 class _FiltApply(torch.autograd.Function):
@@ -2187,17 +2231,11 @@ def _fft_call(plan, x, inverse, sh_in, sh_out, window, win_store, scale, mask, s
         y = torch.empty(batch + (N,), dtype=x.dtype, device=x.device)
     if nlines == 0:
         return y
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib.rime_fft_apply(RIME_F32 if rdt == torch.float32 else RIME_F64, _ptr(x), _ptr(plan.table(inverse, x.device)), _ptr(window),
-                            int(win_store), plan._radix_c, len(plan.radix), N, nlines, int(bool(inverse)), int(sh_in), int(sh_out),
-                            float(scale), int(mask), float(start), float(df), _ptr(y), _stream())
-    check(rc, 'rime_fft_apply')
-    if prof is not None:
-        e1.record()
-        prof.append(('fft_kernel', e0, e1, nlines * N))
+    with _timed('fft_kernel', nlines * N):
+        rc = lib.rime_fft_apply(_dtype_code(rdt), _ptr(x), _ptr(plan.table(inverse, x.device)), _ptr(window),
+                                int(win_store), plan._radix_c, len(plan.radix), N, nlines, int(bool(inverse)), int(sh_in), int(sh_out),
+                                float(scale), int(mask), float(start), float(df), _ptr(y), _stream())
+        check(rc, 'rime_fft_apply')
     return y
 
 
@@ -2297,7 +2335,7 @@ def lm_layout(R, K, I):
     return 'rk' if (I > 1 and K <= LM_REG) else 'kr'
 
 
-class LMPlan:
+class LMPlan(_IndexPlan):
     """
     Device-side state of one linear model y = A x (rime_lm_apply): the design matrix A (Nsamples, Nfeatures), real or complex,
     the gather table idx along the contracted axis and the vector coeff of the un-gathered axis (or None).  The tables the
@@ -2335,9 +2373,6 @@ class LMPlan:
                 raise IndexError('idx outside the indexed axis')
         elif self.K_in is not None and self.K_in != self.K:
             raise ValueError('coeff of %d entries, A takes %d features' % (self.K_in, self.K))
-
-    def _cache(self):
-        return self.__dict__.setdefault('_tabs', {})
 
     def table(self, direction, real_part, layout, dtype, device):
         """(buffer, m_rs, m_ks, R, K, complex) of M = A ('fwd') or A^H ('bwd'), or of Re(M), stored in `layout`"""
@@ -2386,11 +2421,6 @@ class LMPlan:
             tabs[key] = c.contiguous()
         return tabs[key]
 
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_tabs', None)
-        return state
-
     def __deepcopy__(self, memo):
         new = type(self).__new__(type(self))
         import copy
@@ -2404,7 +2434,7 @@ def _lm_call(plan, direction, x3, real_out, with_idx=True):
     'bwd' applies A^H and scales the compact result [O, K, I] by pre.  real_out: Re(.) only.
     """
     O, K_in, I = (int(n) for n in x3.shape)
-    _, rdt = _real_dtype(x3)
+    code, rdt = _real_dtype(x3)
     xc = x3.is_complex()
     real_part = bool(real_out and not xc)                     # Re(M x) of a real x: Re(M) x
     R, K = (plan.R, plan.K) if direction == 'fwd' else (plan.K, plan.R)
@@ -2428,16 +2458,10 @@ def _lm_call(plan, direction, x3, real_out, with_idx=True):
     y = torch.empty((O, R, I), dtype=_lib_cdtype(rdt) if ycplx else rdt, device=x3.device)
     if y.numel() == 0:
         return y
-    prof = PROFILE
-    if prof is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    rc = lib.rime_lm_apply(RIME_F32 if rdt == torch.float32 else RIME_F64, int(xc), int(mc), int(out_real), _ptr(x3), _ptr(buf),
-                           rs, ks, _ptr(idx), _ptr(pre), _ptr(post), O, K, K_in, R, I, _ptr(y), _stream())
-    check(rc, 'rime_lm_apply')
-    if prof is not None:
-        e1.record()
-        prof.append(('lm_kernel', e0, e1, O * R * I * K))
+    with _timed('lm_kernel', O * R * I * K):
+        rc = lib.rime_lm_apply(code, int(xc), int(mc), int(out_real), _ptr(x3), _ptr(buf),
+                               rs, ks, _ptr(idx), _ptr(pre), _ptr(post), O, K, K_in, R, I, _ptr(y), _stream())
+        check(rc, 'rime_lm_apply')
     return y
 
 
@@ -2514,7 +2538,7 @@ def _csr(index, N):
     return off.astype(np.int32), np.argsort(index, kind='stable').astype(np.int32)
 
 
-class RedVisPlan:
+class RedVisPlan(_IndexPlan):
     """
     Index tables of one (baseline set, time set) of rime_redvis_fwd / rime_redvis_bwd, built with numpy on the host (no GPU
     needed) and cached per device as int32 tensors: `red` [Nbl], the group (model row) of every baseline; `tmap` [Nt], the
@@ -2522,14 +2546,16 @@ class RedVisPlan:
     goff [Nred + 1] / gmem [Nbl] (baselines of every group, ascending) and toff [Ntm + 1] / tmem [Nt] (times of every model
     time, ascending).  A `red` entry outside [0, Nred) or a `tmap` entry outside [0, Ntm) is a ValueError.
     """
+    _TABLES = ('red', 'tmap', 'goff', 'gmem', 'toff', 'tmem')
+
     def __init__(self, red, Nred, tmap=None, Ntm=None):
-        red = np.asarray(red.cpu() if torch.is_tensor(red) else red).reshape(-1)
+        red = _host_array(red, flat=True)
         if tmap is None:
             if Ntm is None:
                 raise ValueError('RedVisPlan needs tmap or, for the identity, Ntm')
             tmap, self.identity_t = np.arange(int(Ntm)), True
         else:
-            tmap, self.identity_t = np.asarray(tmap.cpu() if torch.is_tensor(tmap) else tmap).reshape(-1), False
+            tmap, self.identity_t = _host_array(tmap, flat=True), False
             if Ntm is None:
                 raise ValueError('RedVisPlan needs Ntm with tmap')
         for name, a in (('red', red), ('tmap', tmap)):
@@ -2545,20 +2571,6 @@ class RedVisPlan:
         self.toff, self.tmem = _csr(tmap, self.Ntm)
         self.max_members = int(np.diff(self.goff).max())
 
-    def tables(self, device):
-        """dict of the six int32 tables on `device`, cached"""
-        key = str(torch.device(device))
-        tabs = self.__dict__.setdefault('_tabs', {})
-        if key not in tabs:
-            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous()
-                         for k in ('red', 'tmap', 'goff', 'gmem', 'toff', 'tmem')}
-        return tabs[key]
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_tabs', None)
-        return state
-
 
 def _redvis_bwd_call(plan, gout, sign):
     """gmodel [NP, NP, Nred, Ntm, Nf] of a contiguous gout [NP, NP, Nbl, Nt, Nf]: every element written by the kernel"""
@@ -2566,8 +2578,8 @@ def _redvis_bwd_call(plan, gout, sign):
     code, _ = _real_dtype(gout)
     T = plan.tables(gout.device)
     gm = torch.empty((NP, NP, plan.Nred, plan.Ntm, Nf), dtype=gout.dtype, device=gout.device)
-    rc = lib.rime_redvis_bwd(code, NP, _ptr(torch.view_as_real(gout)), _ptr(T['goff']), _ptr(T['gmem']), _ptr(T['toff']),
-                             _ptr(T['tmem']), Nbl, Nt, Nf, plan.Nred, plan.Ntm, sign, _ptr(torch.view_as_real(gm)), _stream())
+    rc = lib.rime_redvis_bwd(code, NP, _cptr(gout), _ptr(T['goff']), _ptr(T['gmem']), _ptr(T['toff']),
+                             _ptr(T['tmem']), Nbl, Nt, Nf, plan.Nred, plan.Ntm, sign, _cptr(gm), _stream())
     check(rc, 'rime_redvis_bwd')
     return gm
 
@@ -2601,9 +2613,8 @@ class _RedVis(torch.autograd.Function):
         code, _ = _real_dtype(m)
         T = plan.tables(m.device)
         out = torch.empty(shape, dtype=dtype, device=m.device)
-        rc = lib.rime_redvis_fwd(code, NP, _ptr(torch.view_as_real(v) if v is not None else None), _ptr(torch.view_as_real(m)),
-                                 _ptr(T['red']), _ptr(None if plan.identity_t else T['tmap']), plan.Nbl, plan.Nt, Nf,
-                                 plan.Nred, plan.Ntm, st[1], st[2], st[3], st[4], sign, _ptr(torch.view_as_real(out)), _stream())
+        rc = lib.rime_redvis_fwd(code, NP, _cptr(v), _cptr(m), _ptr(T['red']), _ptr(None if plan.identity_t else T['tmap']),
+                                 plan.Nbl, plan.Nt, Nf, plan.Nred, plan.Ntm, st[1], st[2], st[3], st[4], sign, _cptr(out), _stream())
         check(rc, 'rime_redvis_fwd')
         ctx.plan, ctx.sign, ctx.mdtype = plan, sign, model.dtype
         return out
@@ -2613,7 +2624,7 @@ class _RedVis(torch.autograd.Function):
     def backward(ctx, gout):
         gm = None
         if ctx.needs_input_grad[1]:
-            gm = _redvis_bwd_call(ctx.plan, gout.detach().resolve_conj().contiguous(), ctx.sign)
+            gm = _redvis_bwd_call(ctx.plan, _dense(gout), ctx.sign)
             if gm.dtype != ctx.mdtype:
                 gm = gm.to(ctx.mdtype)
         return (gout if ctx.needs_input_grad[0] else None), gm, None, None
@@ -2633,7 +2644,7 @@ def redvis(vis, model, plan, undo=False):
 # ---------------------------------------------------------------------------------------
 # LST alignment: rephasing, weighting and the average of the integrations of every bin in one pass (csrc/lstbin.hip)
 # ---------------------------------------------------------------------------------------
-class TimeAvgPlan:
+class TimeAvgPlan(_IndexPlan):
     """
     Bin table of rime_vis_timeavg_fwd / rime_vis_timeavg_bwd, built with numpy on the host (no GPU needed), validated here on
     the host copies and cached per device as int32 tensors.  bins: a list with the time indices of every bin (any integer
@@ -2642,16 +2653,13 @@ class TimeAvgPlan:
     table of the backward gather: t_ptr [Nt + 1], t_pos [Nmem] (the table positions that hold every time, ascending) and
     pos_bin [Nmem] (the bin of every table position).  A member outside [0, Nt) is a ValueError.
     """
+    _TABLES = ('bin_ptr', 'members', 't_ptr', 't_pos', 'pos_bin')
+
     def __init__(self, bins, Nt):
         self.Nt, self.Nbin = int(Nt), len(bins)
         if self.Nt < 0:
             raise ValueError('Nt must not be negative')
-        rows = []
-        for b in bins:
-            b = np.asarray(b.cpu() if torch.is_tensor(b) else b).reshape(-1)
-            if b.size and not np.issubdtype(b.dtype, np.integer):
-                raise ValueError('time indices must be integers')
-            rows.append(b.astype(np.int64))
+        rows = [_host_array(b, flat=True, integer='time indices must be integers').astype(np.int64) for b in bins]
         self.bin_ptr = np.zeros(self.Nbin + 1, dtype=np.int32)
         if rows:
             np.cumsum([r.size for r in rows], out=self.bin_ptr[1:])
@@ -2662,20 +2670,6 @@ class TimeAvgPlan:
         self.members = members.astype(np.int32)
         self.pos_bin = np.repeat(np.arange(self.Nbin), np.diff(self.bin_ptr)).astype(np.int32)
         self.t_ptr, self.t_pos = _csr(members, self.Nt) if self.Nt else (np.zeros(1, dtype=np.int32), np.zeros(0, dtype=np.int32))
-
-    def tables(self, device):
-        """dict of the five int32 tables on `device`, cached"""
-        key = str(torch.device(device))
-        tabs = self.__dict__.setdefault('_tabs', {})
-        if key not in tabs:
-            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous()
-                         for k in ('bin_ptr', 'members', 't_ptr', 't_pos', 'pos_bin')}
-        return tabs[key]
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_tabs', None)
-        return state
 
 
 def _host_ip(a):
@@ -2707,7 +2701,7 @@ class _VisTimeAvg(torch.autograd.Function):
         if Nt != plan.Nt:
             raise ValueError('data of %d times, the plan has %d' % (Nt, plan.Nt))
         Npp = int(np.prod(lead)) if lead else 1
-        d = data.detach().resolve_conj().contiguous()
+        d = _dense(data)
         code, rdt = _real_dtype(d)
         dev = d.device
 
@@ -2727,10 +2721,10 @@ class _VisTimeAvg(torch.autograd.Function):
         sum_w = torch.empty(oshape, dtype=rdt, device=dev)
         avg_cov = torch.empty(oshape, dtype=rdt, device=dev) if c is not None else None
         avg_flag = torch.empty(oshape, dtype=torch.bool, device=dev) if fl is not None else None
-        rc = lib.rime_vis_timeavg_fwd(code, _ptr(torch.view_as_real(d)), _ptr(w), _ptr(c), _ptr(fl), _ptr(tau), int(bool(by_member)),
+        rc = lib.rime_vis_timeavg_fwd(code, _cptr(d), _ptr(w), _ptr(c), _ptr(fl), _ptr(tau), int(bool(by_member)),
                                       _ptr(fr), _ptr(T['bin_ptr']), _ptr(T['members']), _host_ip(plan.bin_ptr),
                                       _host_ip(plan.members), Npp, Nbl, Nt, Nf, plan.Nbin, plan.Nmem,
-                                      _ptr(torch.view_as_real(avg)), _ptr(sum_w), _ptr(avg_cov), _ptr(avg_flag), _stream())
+                                      _cptr(avg), _ptr(sum_w), _ptr(avg_cov), _ptr(avg_flag), _stream())
         check(rc, 'rime_vis_timeavg_fwd')
         ctx.plan, ctx.by_member, ctx.shape, ctx.ddtype = plan, bool(by_member), tuple(d.shape), data.dtype
         ctx.save_for_backward(w, sum_w, tau, fr)
@@ -2745,18 +2739,16 @@ class _VisTimeAvg(torch.autograd.Function):
             return (None,) * 8
         plan = ctx.plan
         w, sum_w, tau, fr = ctx.saved_tensors
-        g = gavg.detach().resolve_conj().contiguous()
-        code, _ = _real_dtype(sum_w)
-        if g.dtype != (torch.complex64 if code == RIME_F32 else torch.complex128):
-            g = g.to(torch.complex64 if code == RIME_F32 else torch.complex128)
+        code, rdt = _real_dtype(sum_w)
+        g = _dense(gavg, _lib_cdtype(rdt))
         Nbl, Nt, Nf = ctx.shape[-3:]
         Npp = int(np.prod(ctx.shape[:-3])) if len(ctx.shape) > 3 else 1
         T = plan.tables(g.device)
         gd = torch.empty(ctx.shape, dtype=g.dtype, device=g.device)
-        rc = lib.rime_vis_timeavg_bwd(code, _ptr(torch.view_as_real(g)), _ptr(w), _ptr(sum_w), _ptr(tau), int(ctx.by_member),
+        rc = lib.rime_vis_timeavg_bwd(code, _cptr(g), _ptr(w), _ptr(sum_w), _ptr(tau), int(ctx.by_member),
                                       _ptr(fr), _ptr(T['t_ptr']), _ptr(T['t_pos']), _ptr(T['pos_bin']), _host_ip(plan.t_ptr),
                                       _host_ip(plan.t_pos), _host_ip(plan.pos_bin), Npp, Nbl, Nt, Nf, plan.Nbin, plan.Nmem,
-                                      _ptr(torch.view_as_real(gd)), _stream())
+                                      _cptr(gd), _stream())
         check(rc, 'rime_vis_timeavg_bwd')
         if gd.dtype != ctx.ddtype:
             gd = gd.to(ctx.ddtype)
@@ -2793,7 +2785,7 @@ def rephase_phasor(tau, freqs, dtype=torch.complex64):
     code, _ = _real_dtype(out)
     rc = lib.rime_vis_timeavg_fwd(code, _ptr(None), _ptr(None), _ptr(None), _ptr(None), _ptr(tau), 0, _ptr(fr), _ptr(T['bin_ptr']),
                                   _ptr(T['members']), _host_ip(plan.bin_ptr), _host_ip(plan.members), 1, Nbl, Nt, Nf, Nt, Nt,
-                                  _ptr(torch.view_as_real(out)), _ptr(None), _ptr(None), _ptr(None), _stream())
+                                  _cptr(out), _ptr(None), _ptr(None), _ptr(None), _stream())
     check(rc, 'rime_vis_timeavg_fwd')
     return out
 
@@ -2806,7 +2798,7 @@ COUPLING_PROD = {'both': 0, 'left': 1, 'right': 2}
 _COUPLING_FWD, _COUPLING_BWD, _COUPLING_EXPAND_BWD = 0, 1, 2
 
 
-class CouplingPlan:
+class CouplingPlan(_IndexPlan):
     """
     Tables of rime_coupling_fwd / rime_coupling_bwd for one (antenna order, baseline list), built and range-checked with numpy
     on the host (no GPU needed) and cached per device as int32 tensors.
@@ -2820,9 +2812,10 @@ class CouplingPlan:
     read twice in the same sense or only conjugated, a row read conjugated anywhere but at the transpose of the entry that
     reads it plain (the folded gradient pairs (a, b) with (b, a)), an output position outside the matrix or named twice.
     """
+    _TABLES = ('table', 'otab', 'ftab')
+
     def __init__(self, table, out_rows, Nbl):
-        table = np.asarray(table.cpu() if torch.is_tensor(table) else table)
-        out_rows = np.asarray(out_rows.cpu() if torch.is_tensor(out_rows) else out_rows).reshape(-1)
+        table, out_rows = _host_array(table), _host_array(out_rows, flat=True)
         if table.ndim != 2 or table.shape[0] != table.shape[1] or table.shape[0] < 1 or not np.issubdtype(table.dtype, np.integer):
             raise ValueError('table must be a square integer matrix')
         if out_rows.size < 1 or not np.issubdtype(out_rows.dtype, np.integer):
@@ -2856,42 +2849,23 @@ class CouplingPlan:
         self.out_rows = out_rows.astype(np.int64)
         self.unread = bool((nplain == 0).any())           # rows of the data outside the matrix: their gradient is zero
 
-    def tables(self, device):
-        """dict of the three int32 tables on `device`, cached"""
-        key = str(torch.device(device))
-        tabs = self.__dict__.setdefault('_tabs', {})
-        if key not in tabs:
-            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous()
-                         for k in ('table', 'otab', 'ftab')}
-        return tabs[key]
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_tabs', None)
-        return state
-
 
 def _coupling_operands(coupling, dly, dtype, Nf=None):
     """(x, dly, N, Tm, Fm, Nf) contiguous in `dtype`: coupling (N, N, Tm, Fm), dly (N, N, 1, Nf) or None"""
     assert coupling.is_complex() and coupling.ndim == 4 and coupling.shape[0] == coupling.shape[1], \
         'complex coupling of shape (Nant, Nant, Ntimes | 1, Nfreqs | 1)'
-    x = coupling.detach().resolve_conj().to(dtype).contiguous()
+    x = _dense(coupling, dtype)
     N, _, Tm, Fm = x.shape
     d = None
     if dly is not None:
         assert dly.is_complex() and dly.ndim == 4 and tuple(dly.shape[:3]) == (N, N, 1), 'complex dly of shape (Nant, Nant, 1, Nfreqs)'
-        d = dly.detach().resolve_conj().to(dtype).contiguous()
+        d = _dense(dly, dtype)
         if Nf is not None and d.shape[3] != Nf:
             raise ValueError('dly of %d channels, data of %d' % (d.shape[3], Nf))
         Nf = d.shape[3]
     elif Nf is None:
         Nf = Fm
     return x, d, N, Tm, Fm, Nf
-
-
-def _coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, stage, device):
-    nbytes = lib.rime_coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, stage)
-    return (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None), nbytes
 
 
 def _coupling_fwd_call(coupling, dly, data, plan, add_I, prod, out=None):
@@ -2907,11 +2881,9 @@ def _coupling_fwd_call(coupling, dly, data, plan, add_I, prod, out=None):
     if out is None:
         out = torch.empty((plan.Nout, Nt, Nf), dtype=data.dtype, device=data.device)
     assert out.is_contiguous() and tuple(out.shape) == (plan.Nout, Nt, Nf) and out.dtype == data.dtype
-    ws, nbytes = _coupling_workspace(code, N, Nt, Nf, Tm, Fm, COUPLING_PROD[prod], _COUPLING_FWD, data.device)
-    rc = lib.rime_coupling_fwd(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
-                               _ptr(torch.view_as_real(data)), _ptr(T['table']), _ptr(T['otab']), N, Nbl, plan.Nout, Nt, Nf,
-                               Tm, Fm, int(bool(add_I)), COUPLING_PROD[prod], _ptr(torch.view_as_real(out)), _ptr(ws), nbytes,
-                               _stream())
+    ws, nbytes = _workspace(lib.rime_coupling_workspace(code, N, Nt, Nf, Tm, Fm, COUPLING_PROD[prod], _COUPLING_FWD), data.device)
+    rc = lib.rime_coupling_fwd(code, _cptr(x), _cptr(d), _cptr(data), _ptr(T['table']), _ptr(T['otab']), N, Nbl, plan.Nout, Nt, Nf,
+                               Tm, Fm, int(bool(add_I)), COUPLING_PROD[prod], _cptr(out), _ptr(ws), nbytes, _stream())
     check(rc, 'rime_coupling_fwd')
     return out
 
@@ -2924,7 +2896,7 @@ class _CouplingApply(torch.autograd.Function):
         assert data.is_complex() and data.ndim == 3, 'complex data of shape (Nbls, Ntimes, Nfreqs)'
         if prod not in COUPLING_PROD:
             raise ValueError("prod must be 'both', 'left' or 'right'")
-        v = data.detach().resolve_conj().contiguous()
+        v = _dense(data)
         out = _coupling_fwd_call(coupling, dly, v, plan, add_I, prod)
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(coupling.detach(), dly.detach() if dly is not None else None, v)
@@ -2938,7 +2910,7 @@ class _CouplingApply(torch.autograd.Function):
         plan = ctx.plan
         Nbl, Nt, Nf = v.shape
         x, d, N, Tm, Fm, _ = _coupling_operands(coupling, dly, v.dtype, Nf)
-        g = gout.detach().resolve_conj().to(v.dtype).contiguous()
+        g = _dense(gout, v.dtype)
         code, _ = _real_dtype(v)
         T = plan.tables(v.device)
         gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
@@ -2946,12 +2918,10 @@ class _CouplingApply(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             gd = torch.zeros_like(v) if plan.unread else torch.empty_like(v)
         prod = COUPLING_PROD[ctx.prod]
-        ws, nbytes = _coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, _COUPLING_BWD, v.device)
-        rc = lib.rime_coupling_bwd(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
-                                   _ptr(torch.view_as_real(v)), _ptr(torch.view_as_real(g)), _ptr(T['table']), _ptr(T['otab']),
+        ws, nbytes = _workspace(lib.rime_coupling_workspace(code, N, Nt, Nf, Tm, Fm, prod, _COUPLING_BWD), v.device)
+        rc = lib.rime_coupling_bwd(code, _cptr(x), _cptr(d), _cptr(v), _cptr(g), _ptr(T['table']), _ptr(T['otab']),
                                    _ptr(T['ftab']), N, Nbl, plan.Nout, Nt, Nf, Tm, Fm, int(ctx.add_I), prod,
-                                   _ptr(torch.view_as_real(gd) if gd is not None else None),
-                                   _ptr(torch.view_as_real(gx) if gx is not None else None), _ptr(ws), nbytes, _stream())
+                                   _cptr(gd), _cptr(gx), _ptr(ws), nbytes, _stream())
         check(rc, 'rime_coupling_bwd')
         if gx is not None and gx.dtype != ctx.xdtype:
             gx = gx.to(ctx.xdtype)
@@ -2968,8 +2938,7 @@ class _CouplingExpand(torch.autograd.Function):
         x, d, N, Tm, Fm, Nf = _coupling_operands(coupling, dly, coupling.dtype)
         code, _ = _real_dtype(x)
         E = torch.empty((N, N, Tm, Nf), dtype=x.dtype, device=x.device)
-        rc = lib.rime_coupling_expand(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
-                                      N, Tm, Nf, Tm, Fm, int(bool(add_I)), _ptr(torch.view_as_real(E)), _stream())
+        rc = lib.rime_coupling_expand(code, _cptr(x), _cptr(d), N, Tm, Nf, Tm, Fm, int(bool(add_I)), _cptr(E), _stream())
         check(rc, 'rime_coupling_expand')
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(x, d)
@@ -2981,13 +2950,12 @@ class _CouplingExpand(torch.autograd.Function):
         x, d = ctx.saved_tensors
         N, _, Tm, Fm = x.shape
         Nf = gE.shape[3]
-        g = gE.detach().resolve_conj().to(x.dtype).contiguous()
+        g = _dense(gE, x.dtype)
         code, _ = _real_dtype(x)
         gx = torch.empty_like(x)
-        ws, nbytes = _coupling_workspace(code, N, Tm, Nf, Tm, Fm, 0, _COUPLING_EXPAND_BWD, x.device)
-        rc = lib.rime_coupling_expand_bwd(code, _ptr(torch.view_as_real(x)), _ptr(torch.view_as_real(d) if d is not None else None),
-                                          _ptr(torch.view_as_real(g)), N, Tm, Nf, Tm, Fm, _ptr(torch.view_as_real(gx)), _ptr(ws),
-                                          nbytes, _stream())
+        ws, nbytes = _workspace(lib.rime_coupling_workspace(code, N, Tm, Nf, Tm, Fm, 0, _COUPLING_EXPAND_BWD), x.device)
+        rc = lib.rime_coupling_expand_bwd(code, _cptr(x), _cptr(d), _cptr(g), N, Tm, Nf, Tm, Fm, _cptr(gx), _ptr(ws), nbytes,
+                                          _stream())
         check(rc, 'rime_coupling_expand_bwd')
         return gx, None, None
 
@@ -3024,7 +2992,7 @@ REDCOUPLING_SEG = 64                             # words of a segment of a term'
 REDCOUPLING_FLAG = 1 << 30                       # column word: the visibility is read conjugated; term word: role b
 
 
-class RedCouplingPlan:
+class RedCouplingPlan(_IndexPlan):
     """
     Tables of rime_redcoupling_fwd / _bwd_data / _bwd_coupling, built and range-checked with numpy on the host (no GPU
     needed) and cached per device as int32 tensors.  Entry e = (row[e], col[e], conj[e], a[e], b[e]) adds
@@ -3039,7 +3007,7 @@ class RedCouplingPlan:
     def __init__(self, row, col, conj, a, b, Nout, Nin, Nterms, seg=REDCOUPLING_SEG):
         arrs = []
         for name, x in (('row', row), ('col', col), ('conj', conj), ('a', a), ('b', b)):
-            x = np.asarray(x.cpu() if torch.is_tensor(x) else x).reshape(-1)
+            x = _host_array(x, flat=True)
             if x.dtype == bool:
                 x = x.astype(np.int64)
             if x.size and not np.issubdtype(x.dtype, np.integer):
@@ -3086,27 +3054,14 @@ class RedCouplingPlan:
 
     _TABLES = ('ent', 'roff', 'coff', 'cmem', 'toff', 'tmem', 'segterm', 'segstart', 'tsoff')
 
-    def tables(self, device):
-        """dict of the int32 tables on `device`, cached"""
-        key = str(torch.device(device))
-        tabs = self.__dict__.setdefault('_tabs', {})
-        if key not in tabs:
-            tabs[key] = {k: torch.as_tensor(getattr(self, k), dtype=torch.int32, device=device).contiguous() for k in self._TABLES}
-        return tabs[key]
-
-    def __getstate__(self):
-        state = dict(self.__dict__)
-        state.pop('_tabs', None)
-        return state
-
 
 def _redcoupling_operands(coupling, dly, data, plan):
     """(x, d, v, Tm, Fm) contiguous in the dtype of the data"""
     assert data.is_complex() and data.ndim == 3, 'complex data of shape (Nin, Ntimes, Nfreqs)'
     assert coupling.is_complex() and coupling.ndim == 3, 'complex coupling of shape (Nterms, Ntimes | 1, Nfreqs | 1)'
-    v = data.detach().resolve_conj().contiguous()
+    v = _dense(data)
     Nin, Nt, Nf = v.shape
-    x = coupling.detach().resolve_conj().to(v.dtype).contiguous()
+    x = _dense(coupling, v.dtype)
     Nterms, Tm, Fm = x.shape
     if Nin != plan.Nin or Nterms != plan.Nterms:
         raise ValueError('data of %d rows and coupling of %d terms, the plan has %d and %d' % (Nin, Nterms, plan.Nin, plan.Nterms))
@@ -3115,12 +3070,8 @@ def _redcoupling_operands(coupling, dly, data, plan):
     d = None
     if dly is not None:
         assert dly.is_complex() and tuple(dly.shape) == (Nterms, Nf), 'complex dly of shape (Nterms, Nfreqs)'
-        d = dly.detach().resolve_conj().to(v.dtype).contiguous()
+        d = _dense(dly, v.dtype)
     return x, d, v, Tm, Fm
-
-
-def _cptr(t):
-    return _ptr(torch.view_as_real(t)) if t is not None else _ptr(None)
 
 
 class _RedCouplingApply(torch.autograd.Function):
@@ -3148,7 +3099,7 @@ class _RedCouplingApply(torch.autograd.Function):
         plan = ctx.plan
         _, Nt, Nf = v.shape
         _, Tm, Fm = x.shape
-        g = gout.detach().resolve_conj().to(v.dtype).contiguous()
+        g = _dense(gout, v.dtype)
         code, _ = _real_dtype(v)
         T = plan.tables(v.device)
         dims = (plan.Nout, plan.Nin, plan.Nterms, plan.Nent)
@@ -3162,8 +3113,7 @@ class _RedCouplingApply(torch.autograd.Function):
                 gd = gd.to(ctx.ddtype)
         if ctx.needs_input_grad[0]:
             gx = torch.empty_like(x)
-            nbytes = lib.rime_redcoupling_workspace(code, plan.Nseg, Nt, Nf)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=v.device) if nbytes else None
+            ws, nbytes = _workspace(lib.rime_redcoupling_workspace(code, plan.Nseg, Nt, Nf), v.device)
             seg = [_ptr(T[k]) if plan.Nseg else _ptr(None) for k in ('tmem', 'segterm', 'segstart')]
             rc = lib.rime_redcoupling_bwd_coupling(code, _cptr(x), _cptr(d), _cptr(v), _cptr(g), _ptr(T['ent']), _ptr(T['toff']),
                                                    seg[0], seg[1], seg[2], _ptr(T['tsoff']), *dims, plan.Nmem, plan.Nseg,

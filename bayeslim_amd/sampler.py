@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib, utils
-from .ops import _require_cuda, _stream, _ptr
+from .ops import _require_cuda, _stream, _ptr, _dtype_code
 from .paramdict import ParamDict
 
 # elements of one work-group and chunk of rime_hmc_step (256 lanes x 64 bytes), and the most work-groups of a launch
@@ -59,7 +59,7 @@ def hmc_step(q, p, g, eps, c, kick, drift, energy=None, ws=None):
     header allows; energy a float64 tensor of one element or None; ws the workspace for the energy (allocated if None).
     """
     _require_cuda(p)
-    N, code = p.numel(), (_lib.RIME_F32 if _real_dtype(p.dtype) == torch.float32 else _lib.RIME_F64)
+    N, code = p.numel(), _dtype_code(_real_dtype(p.dtype))
     for t in (q, g, eps, c):
         if t is not None and (t.dtype != p.dtype or t.numel() != N or t.device != p.device or not t.is_contiguous()):
             raise ValueError('sampler: contiguous vectors of %s [%d] on %s are needed' % (p.dtype, N, p.device))

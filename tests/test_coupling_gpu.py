@@ -246,3 +246,32 @@ def test_chain_in_logprob_and_identity_coupling():
             vin.data = vin.data.to(dt)
             cp.clear_vd_cache()
             assert torch.equal(cp(vin, add_I=True).data, vin.data)
+
+
+def test_left_product_without_a_workspace():
+    """prod 'left' at N = 2, Nt = Nf = 1 needs no workspace in either direction: the kernels get the null pointer and zero
+    bytes.  W = (I + X) V and both gradients against torch in complex128: sums of two products of numbers of order one, so
+    64 roundings of 2^-53 on a magnitude below 16 bound every element."""
+    from bayeslim_amd import ops
+    from bayeslim_amd._lib import lib
+    for stage in (0, 1):
+        assert lib.rime_coupling_workspace(ops.RIME_F64, 2, 1, 1, 1, 1, ops.COUPLING_PROD['left'], stage) == 0
+    rng = np.random.default_rng(7)
+    cx = lambda *s: torch.as_tensor(rng.uniform(-1, 1, size=s) + 1j * rng.uniform(-1, 1, size=s))
+    X, d, w = cx(2, 2, 1, 1), cx(3, 1, 1), cx(4, 1, 1)
+    table, out_rows = [[0, 1], [1 | ops.COUPLING_CONJ, 2]], [0, 1, 2, 3]
+
+    def ref(X, d):
+        V = torch.stack([torch.stack([d[0], d[1]]), torch.stack([d[1].conj(), d[2]])])          # (2, 2, 1, 1)
+        E = torch.eye(2, dtype=X.dtype)[:, :, None, None] + X
+        return torch.einsum('abtf,bctf->actf', E, V).reshape(4, 1, 1)
+
+    Xr, dr = X.clone().requires_grad_(True), d.clone().requires_grad_(True)
+    out_r = ref(Xr, dr)
+    gXr, gdr = torch.autograd.grad((out_r * w.conj()).real.sum(), [Xr, dr])
+    Xg, dg = X.to(DEV).requires_grad_(True), d.to(DEV).requires_grad_(True)
+    out = ops.coupling_apply(Xg, None, dg, table, out_rows, prod='left')
+    gX, gd = torch.autograd.grad((out * w.to(DEV).conj()).real.sum(), [Xg, dg])
+    tol = 64 * 2.0 ** -53 * 16
+    for a, b in ((out, out_r), (gX, gXr), (gd, gdr)):
+        assert a.shape == b.shape and a.dtype == torch.complex128 and float((a.detach().cpu() - b.detach()).abs().max()) <= tol

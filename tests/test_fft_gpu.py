@@ -297,3 +297,24 @@ def test_fft_of_a_visdata_and_vis_wedge(f64):
     z64 = fc.oracle(xa32, win=g['wedge_win'].float(), fftshift=True, abs=True)
     assert w32.data.dtype == torch.float32
     assert ratio(w32.data, z64, fc.bound(xa32, 12, torch.float32, win=g['wedge_win'].float())) <= 1.0
+
+
+def test_profile_tuples():
+    """ops.PROFILE receives one ('fft_kernel', start, end, lines x N) per launch: the forward, then the backward"""
+    from bayeslim_amd import ops
+    rng = np.random.default_rng(5)
+    x = torch.as_tensor(rng.normal(size=(3, 8)) + 1j * rng.normal(size=(3, 8))).to(torch.complex64).to(DEV).requires_grad_(True)
+    plan = plan_for(8, 'f32')
+    prof = []
+    ops.PROFILE = prof
+    try:
+        y = ops.fft_apply(x, plan)
+        assert len(prof) == 1
+        y.abs().sum().backward()
+    finally:
+        ops.PROFILE = None
+    torch.cuda.synchronize()
+    assert len(prof) == 2 and all(len(k) == 4 and k[0] == 'fft_kernel' and k[3] == 24 for k in prof), prof
+    assert all(k[1].elapsed_time(k[2]) >= 0 for k in prof)
+    ops.fft_apply(x.detach(), plan)
+    assert len(prof) == 2                                      # nothing is recorded once PROFILE is None again

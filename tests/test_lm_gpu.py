@@ -379,3 +379,26 @@ def test_rime_lm_mini_against_the_reference(prec):
         assert ev < tv and es < tg and eb < tg
     finally:
         torch.set_default_dtype(old)
+
+
+def test_profile_tuples():
+    """ops.PROFILE receives one ('lm_kernel', start, end, O R I K) per launch: the forward, then the adjoint of the backward"""
+    from bayeslim_amd import ops
+    rng = np.random.default_rng(6)
+    A = torch.as_tensor(rng.normal(size=(5, 3))).float()
+    x = torch.as_tensor(rng.normal(size=(3, 4))).float().to(DEV).requires_grad_(True)
+    plan = ops.LMPlan(A)
+    O, K, R, I = 1, 3, 5, 4
+    prof = []
+    ops.PROFILE = prof
+    try:
+        y = ops.lm_apply(x, plan, dim=0)
+        assert y.shape == (R, I) and len(prof) == 1
+        y.sum().backward()
+    finally:
+        ops.PROFILE = None
+    torch.cuda.synchronize()
+    assert len(prof) == 2 and all(len(k) == 4 and k[0] == 'lm_kernel' and k[3] == O * R * I * K for k in prof), prof
+    assert all(k[1].elapsed_time(k[2]) >= 0 for k in prof)
+    ops.lm_apply(x.detach(), plan, dim=0)
+    assert len(prof) == 2                                      # nothing is recorded once PROFILE is None again

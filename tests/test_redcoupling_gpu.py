@@ -252,3 +252,23 @@ def test_chain_in_logprob():
         for dt in (torch.complex128, torch.complex64):
             vin.data = vin.data.to(dt)
             assert torch.equal(cp(vin).data, vin.data[:, :, torch.as_tensor(cp.red_bl_inds, device=DEV)])
+
+
+def test_plan_without_a_term_word():
+    """no entry names a term: Nseg = 0, the gradient of the coefficients takes no workspace (null pointer, zero bytes) and no
+    segment tables, and is zero; out = data[0] + conj(data[1]) and the gradient of the data are exact (one addition of two
+    copies, no product)"""
+    from bayeslim_amd import ops
+    from bayeslim_amd._lib import lib
+    plan = ops.RedCouplingPlan(row=[0, 0], col=[0, 1], conj=[0, 1], a=[-1, -1], b=[-1, -1], Nout=1, Nin=2, Nterms=2)
+    assert (plan.Nseg, plan.Nmem) == (0, 0) and lib.rime_redcoupling_workspace(ops.RIME_F64, 0, 3, 5) == 0
+    rng = np.random.default_rng(8)
+    cx = lambda *s: torch.as_tensor(rng.uniform(-1, 1, size=s) + 1j * rng.uniform(-1, 1, size=s))
+    X, d, w = cx(2, 1, 1).to(DEV).requires_grad_(True), cx(2, 3, 5).to(DEV).requires_grad_(True), cx(1, 3, 5).to(DEV)
+    out = ops.redcoupling_apply(X, None, d, plan)
+    gX, gd = torch.autograd.grad((out * w.conj()).real.sum(), [X, d])
+    dr = d.detach().clone().requires_grad_(True)
+    out_r = (dr[0] + dr[1].conj())[None]
+    gdr, = torch.autograd.grad((out_r * w.conj()).real.sum(), [dr])
+    assert torch.equal(out, out_r) and torch.equal(gd, gdr)
+    assert gX.shape == X.shape and not bool(gX.any())
