@@ -65,15 +65,8 @@ class PixelBeam(utils.Module):
     def push(self, device):
         if not isinstance(device, torch.dtype):
             self.device = device
-        self.params = utils.push(self.params, device)
-        self.R.push(device)
         self.freqs = utils.push(torch.as_tensor(self.freqs), device)
-        if self.p0 is not None:
-            self.p0 = utils.push(self.p0, device)
-        for prs in (self.priors_inp_params, self.priors_out_params):
-            for pr in (prs or []):
-                if pr is not None:
-                    pr.push(device)
+        self._push_params(device)
         self.clear_cache()
 
     # -- FoV cut -------------------------------------------------------------------------
@@ -98,7 +91,7 @@ class PixelBeam(utils.Module):
         zen, az = zen[cut], az[cut]
         if zen_hash:
             zen._arr_hash = zen_hash
-        p = self.params if self.p0 is None else self.params + self.p0
+        p = self._full_params()
         tx, ty = getattr(self, 'theta_x', 0), getattr(self, 'theta_y', 0)
         if tx > 0 or ty > 0:
             nz, na = pointing_offset(utils.tensor2numpy(zen) * D2R, utils.tensor2numpy(az) * D2R, tx, ty)
@@ -110,11 +103,9 @@ class PixelBeam(utils.Module):
             beam = self.R(p, new_zen, new_az, self.freqs, out_stride=out_stride)
         else:
             beam = self.R(p, new_zen, new_az, self.freqs)
-        if getattr(self, '_hook_registry', None) is not None:
-            bc = getattr(self.R, 'beam_cache', None)
-            if bc is not None and bc.requires_grad:
-                for r in self._hook_registry:
-                    bc.register_hook(r)
+        bc = getattr(self.R, 'beam_cache', None)
+        if bc is not None:
+            self._hook_response(bc)
         self.eval_prior(prior_cache)
         return beam, cut, zen, az
 
@@ -125,7 +116,7 @@ class PixelBeam(utils.Module):
         per forward on the concatenated, already-cut angles of all time steps of the minibatch,
         so one interpolation launch serves every time step.
         """
-        p = self.params if self.p0 is None else self.params + self.p0
+        p = self._full_params()
         tx, ty = getattr(self, 'theta_x', 0), getattr(self, 'theta_y', 0)
         if tx > 0 or ty > 0:
             h = getattr(zen, '_arr_hash', None)
@@ -135,11 +126,9 @@ class PixelBeam(utils.Module):
             if h is not None:
                 zen._arr_hash = h
         beam = self.R(p, zen, az, self.freqs)
-        if getattr(self, '_hook_registry', None) is not None:
-            bc = getattr(self.R, 'beam_cache', None)
-            if bc is not None and bc.requires_grad:
-                for r in self._hook_registry:
-                    bc.register_hook(r)
+        bc = getattr(self.R, 'beam_cache', None)
+        if bc is not None:
+            self._hook_response(bc)
         self.eval_prior(prior_cache)
         return beam
 
@@ -158,7 +147,7 @@ class PixelBeam(utils.Module):
             return None
         if getattr(self, 'theta_x', 0) > 0 or getattr(self, 'theta_y', 0) > 0:
             return None
-        p = self.params if self.p0 is None else self.params + self.p0
+        p = self._full_params()
         if p.dim() != 5 or p.shape[2] != 1:
             return None
         if R.beam_cache is None:
@@ -166,9 +155,7 @@ class PixelBeam(utils.Module):
         bc = R.beam_cache
         if bc.is_complex() or bc.dim() != 5 or tuple(bc.shape[:3]) != (1, 1, 1):
             return None
-        if getattr(self, '_hook_registry', None) is not None and bc.requires_grad:
-            for r in self._hook_registry:
-                bc.register_hook(r)
+        self._hook_response(bc)
         self.eval_prior(prior_cache)
         return bc, R.get_stencil(zen, az)
 
@@ -256,7 +243,7 @@ class PixelBeam(utils.Module):
         if self.priors_out_params is not None:
             if out_params is None and hasattr(self.R, 'beam_cache'):
                 if self.R.beam_cache is None:
-                    self.R.set_beam_cache(self.params if self.p0 is None else self.params + self.p0)
+                    self.R.set_beam_cache(self._full_params())
                 out_params = self.R.beam_cache
             for pr in self.priors_out_params:
                 if pr is not None:

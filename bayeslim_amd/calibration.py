@@ -46,6 +46,11 @@ def _index_tensor(idx, device):
     return torch.as_tensor(idx, device=device).to(torch.int32).contiguous()
 
 
+def _require_gpu(data):
+    if not data.is_cuda:
+        raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
+
+
 def _invert_gains(gains, polmode, vis_type):
     """the `undo` branch (calibration.py:2430-2443) without the per-antenna Python loop"""
     if polmode in ('1pol', '2pol'):
@@ -71,8 +76,7 @@ def _apply_cal(vis, gains, g1_idx, g2_idx, cal_2pol=False, cov=None, vis_type='c
     call).  Returns (new_vis, new_cov) like the reference (calibration.py:2412-2487).
     """
     assert vis.shape[:2] == gains.shape[:2], "vis and gains must have same Npols"
-    if not vis.is_cuda:
-        raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
+    _require_gpu(vis)
     polmode = '1pol' if vis.shape[:2] == (1, 1) else '4pol'
     if cal_2pol and polmode == '4pol':
         polmode = '2pol'
@@ -339,39 +343,88 @@ class IndexCache:
         return params
 
 
-class JonesModel(utils.Module, IndexCache):
+class _CalTerm(utils.Module, IndexCache):
+    """
+    What the calibration terms (JonesModel, RedVisModel / VisModel, VisCoupling, RedVisCoupling) share: the constructor head,
+    the caches with the cached output VisData `_vd`, the chain parameters -> response -> hooks -> priors (_response) and push.
+    A new term adds its indexing and its `ops` call, not another copy of these.
+    """
+    _clear_on_push = None            # name of the cache-clearing method that a push to a device calls
+    _push_names = ()                 # tensor (or tuple-of-tensor) attributes of the class that push moves, where they exist
+
+    def __init__(self, params, R, parameter=True, p0=None, name=None, atol=1e-5, bls=None):
+        utils.Module.__init__(self, name=name)
+        self.params = torch.nn.Parameter(params) if parameter else params
+        self.p0 = p0
+        self.device = params.device
+        self.R = R
+        IndexCache.__init__(self, times=getattr(self.R, 'times', None), bls=bls, atol=atol)
+        self.clear_cache()
+
+    def clear_cache(self):
+        """clear all caches, some come from IndexCache"""
+        self.clear_time_cache()
+        self.clear_bl_cache()
+        self.clear_vd_cache()
+
+    def clear_vd_cache(self):
+        self._vd = None
+
+    def __getstate__(self):
+        """pickle and deepcopy leave the cached output behind: after a forward its data is a node of an autograd graph"""
+        state = dict(self.__dict__)
+        state['_vd'] = None
+        return state
+
+    def _response(self, prior_cache, out=None):
+        """params (+ p0) -> R (unless its output `out` is given) -> gradient hooks -> priors into prior_cache"""
+        if out is None:
+            out = self.R(self._full_params())
+        self._hook_response(out)
+        self.eval_prior(prior_cache, inp_params=self.params, out_params=out)
+        return out
+
+    def push(self, device):
+        """push to a new device or dtype"""
+        if not isinstance(device, torch.dtype):
+            if self._clear_on_push is not None:
+                getattr(self, self._clear_on_push)()
+            self.device = device
+            if isinstance(self._times, torch.Tensor):
+                self._times = utils.push(self._times, device)
+            if isinstance(self._bls, torch.Tensor):
+                self._bls = utils.push(self._bls, device)
+        for k in self._push_names:
+            v = getattr(self, k, None)
+            if v is not None:
+                setattr(self, k, tuple(utils.push(a, device) for a in v) if isinstance(v, tuple) else utils.push(v, device))
+        self._push_params(device)
+
+
+class JonesModel(_CalTerm):
     """
     Antenna-based, direction-independent Jones term V^d_pq = J_p V^m_pq J_q^dagger applied to a VisData
     (calibration.py:416-742): 1-pol (1, 1), 2-pol (diagonal) and 4-pol (full 2 x 2) parameters of shape
     (Npol, Npol, Nant, Ntimes | Ncoeff, Nfreqs | Ncoeff); forward(vd, undo=False, prior_cache=None, jones=None) -> VisData.
     """
+    _clear_on_push = 'clear_cache'   # a device push drops every cache
+
     def __init__(self, params, ants, p0=None, refant=None, R=None, parameter=True, polmode='1pol', single_ant=False,
                  name=None, vis_type='com', atol=1e-5):
-        utils.Module.__init__(self, name=name)
-        self.params = torch.nn.Parameter(params) if parameter else params
-        self.device = params.device
-        self.p0 = p0
+        super().__init__(params, R if R is not None else JonesResponse(), parameter=parameter, p0=p0, name=name, atol=atol)
         self.ants = list(ants)
         self.Nants = len(self.ants)
-        self.R = R if R is not None else JonesResponse()
-        IndexCache.__init__(self, times=getattr(self.R, 'times', None), atol=atol)
         self.polmode, self.single_ant, self.vis_type = polmode, single_ant, vis_type
         self.set_refant(refant)
-        self.clear_cache()
         self._args = dict(refant=refant, polmode=polmode)
         self._args[self.R.__class__.__name__] = getattr(self.R, '_args', None)
 
     def clear_cache(self):
-        self.clear_time_cache()
-        self.clear_bl_cache()
+        super().clear_cache()
         self.cache_aidx = {}
-        self._vd = None
 
     def clear_ant_cache(self):
         self.cache_aidx = {}
-
-    def clear_vd_cache(self):
-        self._vd = None
 
     def get_ant_idx(self, bls):
         """(g1_idx, g2_idx): antenna-axis indices of the two gains of every baseline, cached by the baseline array"""
@@ -405,35 +458,13 @@ class JonesModel(utils.Module, IndexCache):
         if self.refant_idx is not None:
             self.fix_refant_phs()
         if getattr(self, '_vd', None) is None:
-            self._vd = vd.copy(copydata=True, copymeta=True)
+            self._vd = vd.copy(copydata=True, copymeta=True)        # a full copy is cached and a fresh copy returned
         vout = self._vd.copy(copydata=False, copymeta=False)
-        params = self.params if self.p0 is None else self.params + self.p0
-        if jones is None:
-            jones = self.R(params)
-        if getattr(self, '_hook_registry', None) is not None and jones.requires_grad:
-            for r in self._hook_registry:
-                jones.register_hook(r)
-        self.eval_prior(prior_cache, inp_params=self.params, out_params=jones)
-        jones = self.index_params(jones, times=vd.times)
+        jones = self.index_params(self._response(prior_cache, out=jones), times=vd.times)
         g1_idx, g2_idx = self.get_ant_idx(vd._blnums)
         vout.data, _ = _apply_cal(vd.data, jones, g1_idx, g2_idx, cal_2pol=self.polmode == '2pol',
                                   vis_type=self.vis_type, undo=undo)
         return vout
-
-    def push(self, device):
-        if not isinstance(device, torch.dtype):
-            self.clear_cache()
-            self.device = device
-            if isinstance(self._times, torch.Tensor):
-                self._times = utils.push(self._times, device)
-        self.params = utils.push(self.params, device)
-        self.R.push(device)
-        if self.p0 is not None:
-            self.p0 = utils.push(self.p0, device)
-        for prs in (self.priors_inp_params, self.priors_out_params):
-            for pr in (prs or []):
-                if pr is not None:
-                    pr.push(device)
 
 
 # ---------------------------------------------------------------------------------------
@@ -464,39 +495,19 @@ def _sel2index(sel, N):
     return np.asarray(sel, dtype=np.int64).reshape(-1)
 
 
-class _VisTerm(utils.Module, IndexCache):
-    """what RedVisModel and VisModel share: parameters -> response -> hooks / priors -> ops.redvis with a cached plan"""
-    def _setup(self, params, R, parameter, p0, bls, atol):
-        self.params = torch.nn.Parameter(params) if parameter else params
-        self.device = params.device
-        self.R = R if R is not None else VisModelResponse()
-        self.p0 = p0
-        IndexCache.__init__(self, times=getattr(self.R, 'times', None), bls=bls, atol=atol)
-        self.clear_cache()
+class _VisTerm(_CalTerm):
+    """what RedVisModel and VisModel share: the response output -> ops.redvis with a cached plan"""
+    _clear_on_push = 'clear_cache'   # a device push drops every cache
 
-    def clear_cache(self):
-        """clear all caches, some come from IndexCache"""
-        self.clear_time_cache()
-        self.clear_bl_cache()
-        self.clear_vd_cache()
+    def __init__(self, params, R, parameter, p0, name, atol, bls=None):
+        super().__init__(params, R if R is not None else VisModelResponse(), parameter=parameter, p0=p0, name=name,
+                         atol=atol, bls=bls)
 
-    def clear_time_cache(self):
+    def clear_time_cache(self):      # the plans hold time and baseline indices: either clear drops them too
         self.cache_tidx, self.cache_plan = {}, {}
 
     def clear_bl_cache(self):
         self.cache_bidx, self.cache_plan = {}, {}
-
-    def clear_vd_cache(self):
-        self._vd = None
-
-    def _model(self, prior_cache):
-        params = self.params if self.p0 is None else self.params + self.p0
-        vis = self.R(params)
-        if getattr(self, '_hook_registry', None) is not None and vis.requires_grad:
-            for r in self._hook_registry:
-                vis.register_hook(r)
-        self.eval_prior(prior_cache, inp_params=self.params, out_params=vis)
-        return vis
 
     def _time_index(self, vd, Ntm):
         """(tmap or None for the identity, cache key): the model time of every time of vd"""
@@ -508,8 +519,7 @@ class _VisTerm(utils.Module, IndexCache):
         return _sel2index(sel, Ntm), utils.arr_hash(vd.times)
 
     def _apply(self, vd, model, red, Nred, bkey, undo):
-        if not vd.data.is_cuda:
-            raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
+        _require_gpu(vd.data)
         if getattr(self, '_vd', None) is None:
             self._vd = vd.copy(copydata=False)
         vout = self._vd
@@ -525,24 +535,6 @@ class _VisTerm(utils.Module, IndexCache):
         vout.data = ops.redvis(vd.data, model, self.cache_plan[key], undo=undo)
         return vout
 
-    def push(self, device):
-        """push to a new device or dtype"""
-        if not isinstance(device, torch.dtype):
-            self.clear_cache()
-            self.device = device
-            if isinstance(self._times, torch.Tensor):
-                self._times = utils.push(self._times, device)
-            if isinstance(self._bls, torch.Tensor):
-                self._bls = utils.push(self._bls, device)
-        self.params = utils.push(self.params, device)
-        self.R.push(device)
-        if self.p0 is not None:
-            self.p0 = utils.push(self.p0, device)
-        for prs in (self.priors_inp_params, self.priors_out_params):
-            for pr in (prs or []):
-                if pr is not None:
-                    pr.push(device)
-
 
 class RedVisModel(_VisTerm):
     """
@@ -556,9 +548,8 @@ class RedVisModel(_VisTerm):
     _select_equal_times = True       # the reference indexes the model's time axis whenever the response knows the times
 
     def __init__(self, params, bl2red, R=None, parameter=True, p0=None, name=None, atol=1e-5):
-        utils.Module.__init__(self, name=name)
+        super().__init__(params, R, parameter, p0, name, atol)
         self.bl2red = bl2red
-        self._setup(params, R, parameter, p0, None, atol)
 
     def get_bl_idx(self, bls):
         """index tensor that expands the Nredvis axis to the baselines `bls` (baseline numbers); overloads IndexCache.get_bl_idx"""
@@ -571,7 +562,7 @@ class RedVisModel(_VisTerm):
         return self.cache_bidx[h]
 
     def forward(self, vd, undo=False, prior_cache=None):
-        redvis = self._model(prior_cache)
+        redvis = self._response(prior_cache)
         Nbl, Nred = vd.data.shape[-3], redvis.shape[-3]
         if Nred != Nbl:
             return self._apply(vd, redvis, lambda: self.get_bl_idx(vd._blnums), Nred, utils.arr_hash(vd._blnums), undo)
@@ -587,11 +578,10 @@ class VisModel(_VisTerm):
     _select_equal_times = False      # ... and here only when the input holds fewer times than the model
 
     def __init__(self, params, R=None, parameter=True, p0=None, blnums=None, name=None, atol=1e-5):
-        utils.Module.__init__(self, name=name)
-        self._setup(params, R, parameter, p0, blnums, atol)
+        super().__init__(params, R, parameter, p0, name, atol, bls=blnums)
 
     def forward(self, vd, undo=False, prior_cache=None, **kwargs):
-        vis = self._model(prior_cache)
+        vis = self._response(prior_cache)
         Nbl, Nmod = vd.data.shape[-3], vis.shape[-3]
         if Nmod != Nbl:
             assert self._bls is not None, 'a baseline minibatch needs blnums'
@@ -603,7 +593,65 @@ class VisModel(_VisTerm):
 # ---------------------------------------------------------------------------------------
 # antenna mutual coupling (calibration.py:1258-1586)
 # ---------------------------------------------------------------------------------------
-class VisCoupling(utils.Module, IndexCache):
+def _coupling_delay(lengths, freqs, min_dly, sign, c):
+    """complex128 numpy phasor exp(sign 2 pi i (f - f_0) / c * max(min_dly, length)), shape lengths.shape + (Nfreqs,)"""
+    if min_dly is not None:
+        lengths = np.maximum(lengths, min_dly)
+    fr = np.asarray(torch.as_tensor(freqs).detach().cpu(), dtype=np.float64)
+    return np.exp(1j * (2 * np.pi * sign * (fr - fr[0]) / c * lengths[..., None]))
+
+
+def _check_bls(bls, known, who):
+    """ValueError for the first baseline that names an antenna outside `known`, has ant2 < ant1 or appeared before (tested in
+    that order); `who` is the class named in the message"""
+    seen = set()
+    for bl in bls:
+        bl = tuple(bl)
+        if bl[0] not in known or bl[1] not in known:
+            raise ValueError('baseline %s names an antenna that is not in antpos' % (bl,))
+        if bl[1] < bl[0]:
+            raise ValueError('baseline %s: %s needs ant2 >= ant1' % (bl, who))
+        if bl in seen:
+            raise ValueError('baseline %s appears twice' % (bl,))
+        seen.add(bl)
+
+
+class _CouplingTerm(_CalTerm):
+    """what VisCoupling and RedVisCoupling add to _CalTerm: the array attributes, the guards of a forward that needs
+    setup_coupling(), and a coupling of one time bin that broadcasts"""
+    def __init__(self, params, freqs, antpos, R, parameter, p0, name, atol):
+        super().__init__(params, R if R is not None else VisModelResponse(), parameter=parameter, p0=p0, name=name, atol=atol)
+        self.freqs = freqs
+        self.Nfreqs = len(freqs)
+        self.antpos = antpos
+        self.Nants = len(antpos)
+        self.c = 2.99792458e8
+        self.Npol = params.shape[0]
+        assert self.Npol == 1, "multi-pol not currently supported"
+
+    def index_params(self, params, times=None):
+        """overloads IndexCache.index_params: one time bin in params broadcasts"""
+        if times is not None and params.shape[-2] != 1:
+            params = IndexCache.index_params(self, params, times=times)
+        return params
+
+    def _check_input(self, vd, Nbl_attr):
+        """the guards of forward: setup_coupling() has run, GPU tensors, the baselines the plan was set up for"""
+        who = type(self).__name__
+        if getattr(self, 'plan', None) is None:
+            raise RuntimeError('%s: run setup_coupling() before forward()' % who)
+        _require_gpu(vd.data)
+        Nbl = getattr(self.plan, Nbl_attr)
+        if tuple(vd.data.shape[:3]) != (1, 1, Nbl):
+            raise ValueError('input of shape %s, %s was set up for (1, 1, %d, Ntimes, Nfreqs)' % (tuple(vd.data.shape), who, Nbl))
+
+    def _coupling(self, vd, prior_cache):
+        """the response output at the times of vd, complex in the precision of the data"""
+        coupling = self.index_params(self._response(prior_cache), times=vd.times)
+        return coupling if coupling.is_complex() else coupling.to(vd.data.dtype)
+
+
+class VisCoupling(_CouplingTerm):
     """
     Mutual coupling of antennas as a linear map of visibilities across the baseline axis (calibration.py:1258-1586): with V
     the Nant x Nant matrix of all visibilities of one time and channel (lower triangle the conjugate of the upper, baselines
@@ -619,39 +667,14 @@ class VisCoupling(utils.Module, IndexCache):
     The form fitted on a redundant array, with one coefficient per coupling vector (gen_coupling_terms), is RedVisCoupling;
     CouplingInflate turns its parameters into the matrix used here.  Not built: PartialRedVisInflate, CouplingExpand.
     """
+    # a device push clears no cache here (_clear_on_push stays None)
+    _push_names = ('flat_data_idx', 'flat_data_null', 'flat_conj_idx', 'flat_unconj_idx', 'bls_idx', 'I', 'dly', 'freqs')
+
     def __init__(self, params, freqs, antpos, bls, R=None, parameter=True, p0=None, name=None, atol=1e-5, add_I=True,
                  prod='both', double=False):
-        utils.Module.__init__(self, name=name)
-        self.params = torch.nn.Parameter(params) if parameter else params
-        self.p0 = p0
-        self.freqs = freqs
-        self.Nfreqs = len(freqs)
-        self.antpos = antpos
-        self.Nants = len(antpos)
+        super().__init__(params, freqs, antpos, R, parameter, p0, name, atol)
         self.bls = bls
-        self.c = 2.99792458e8
-        self.device = params.device
-        self.Npol = params.shape[0]
-        assert self.Npol == 1, "multi-pol not currently supported"
         self.add_I, self.prod, self.double = add_I, prod, double
-        self.R = R if R is not None else VisModelResponse()
-        IndexCache.__init__(self, times=getattr(self.R, 'times', None), atol=atol)
-        self.clear_cache()
-
-    def clear_cache(self):
-        """clear all caches, some come from IndexCache"""
-        self.clear_time_cache()
-        self.clear_bl_cache()
-        self.clear_vd_cache()
-
-    def clear_vd_cache(self):
-        self._vd = None
-
-    def __getstate__(self):
-        """pickle and deepcopy leave the cached output behind: after a forward its data is a node of an autograd graph"""
-        state = dict(self.__dict__)
-        state['_vd'] = None
-        return state
 
     def setup_coupling(self, bls=None, min_dly=None, conj=True):
         """
@@ -669,24 +692,14 @@ class VisCoupling(utils.Module, IndexCache):
         where = {a: i for i, a in enumerate(ants)}
         N = self.Nants
         pairs = [(int(b[0]), int(b[1])) for b in self.bls]
-        rows = {}
-        for r, (a1, a2) in enumerate(pairs):
-            if a1 not in where or a2 not in where:
-                raise ValueError('baseline %s names an antenna that is not in antpos' % ((a1, a2),))
-            if a2 < a1:
-                raise ValueError('baseline %s: VisCoupling needs ant2 >= ant1' % ((a1, a2),))
-            if (a1, a2) in rows:
-                raise ValueError('baseline %s appears twice' % ((a1, a2),))
-            rows[(a1, a2)] = r
+        _check_bls(pairs, where, 'VisCoupling')
+        rows = {bl: r for r, bl in enumerate(pairs)}
 
         # delay phasor between coupled antennas
         vecs = np.stack([np.asarray(torch.as_tensor(self.antpos[a]).detach().cpu(), dtype=np.float64) for a in ants])
-        length = np.linalg.norm(vecs[None, :, :] - vecs[:, None, :], axis=-1)
-        if min_dly is not None:
-            length = np.maximum(length, min_dly)
-        fr = np.asarray(torch.as_tensor(self.freqs).detach().cpu(), dtype=np.float64)
-        phase = 2 * np.pi * (1 if conj else -1) * (fr - fr[0])[None, None, :] / self.c * length[:, :, None]
-        self.dly = torch.as_tensor(np.exp(1j * phase)[None, None, :, :, None, :]).to(dtype=utils._cfloat(), device=self.device)
+        dly = _coupling_delay(np.linalg.norm(vecs[None, :, :] - vecs[:, None, :], axis=-1), self.freqs, min_dly,
+                              1 if conj else -1, self.c)
+        self.dly = torch.as_tensor(dly[None, None, :, :, None, :]).to(dtype=utils._cfloat(), device=self.device)
 
         # matrix entry (i, j): the row of (ant_i, ant_j) when ant_j >= ant_i, else the conjugate of the row of (ant_j, ant_i)
         table = np.full((N, N), -1, dtype=np.int64)
@@ -709,63 +722,20 @@ class VisCoupling(utils.Module, IndexCache):
         self.bls_idx = torch.as_tensor(out_rows, device=self.device)
         self.I = torch.eye(N, dtype=utils._float(), device=self.device)[None, None, :, :, None, None]
 
-    def index_params(self, params, times=None):
-        """overloads IndexCache.index_params: one time bin in params broadcasts"""
-        if times is not None and params.shape[-2] != 1:
-            params = IndexCache.index_params(self, params, times=times)
-        return params
-
     def forward(self, vd, prior_cache=None, add_I=None, prod=None, double=False, **kwargs):
         """vd: VisData of shape (1, 1, Nbls, Ntimes, Nfreqs) holding exactly the baselines of setup_coupling, in their order;
         returns the cached output VisData with the coupled visibilities"""
-        if getattr(self, 'plan', None) is None:
-            raise RuntimeError('VisCoupling: run setup_coupling() before forward()')
-        if not vd.data.is_cuda:
-            raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
-        if tuple(vd.data.shape[:3]) != (1, 1, self.plan.Nbl):
-            raise ValueError('input of shape %s, VisCoupling was set up for (1, 1, %d, Ntimes, Nfreqs)'
-                             % (tuple(vd.data.shape), self.plan.Nbl))
+        self._check_input(vd, 'Nbl')
         if getattr(self, '_vd', None) is None:
             self._vd = vd.copy(copydata=False)
         vout = self._vd
-        params = self.params if self.p0 is None else self.params + self.p0
-        coupling = self.R(params)
-        if getattr(self, '_hook_registry', None) is not None and coupling.requires_grad:
-            for r in self._hook_registry:
-                coupling.register_hook(r)
-        self.eval_prior(prior_cache, inp_params=self.params, out_params=coupling)
-        coupling = self.index_params(coupling, times=vd.times)
-        if not coupling.is_complex():
-            coupling = coupling.to(vd.data.dtype)
+        coupling = self._coupling(vd, prior_cache)
         double = double if double is not None else self.double
         out = ops.coupling_apply(coupling[0, 0], self.dly[0, 0], vd.data[0, 0], self.plan,
                                  add_I=add_I if add_I is not None else self.add_I,
                                  prod=prod if prod is not None else self.prod, double=bool(double))
         vout.data = out[None, None]
         return vout
-
-    def push(self, device):
-        """push to a new device or dtype"""
-        dtype = isinstance(device, torch.dtype)
-        if not dtype:
-            self.device = device
-            if isinstance(self._times, torch.Tensor):
-                self._times = utils.push(self._times, device)
-            for k in ('flat_data_idx', 'flat_data_null', 'flat_conj_idx', 'flat_unconj_idx', 'bls_idx'):
-                if hasattr(self, k):
-                    setattr(self, k, getattr(self, k).to(device))
-        for k in ('I', 'dly'):
-            if hasattr(self, k):
-                setattr(self, k, utils.push(getattr(self, k), device))
-        self.params = utils.push(self.params, device)
-        self.freqs = utils.push(self.freqs, device)
-        self.R.push(device)
-        if self.p0 is not None:
-            self.p0 = utils.push(self.p0, device)
-        for prs in (self.priors_inp_params, self.priors_out_params):
-            for pr in (prs or []):
-                if pr is not None:
-                    pr.push(device)
 
 
 # ---------------------------------------------------------------------------------------
@@ -945,7 +915,7 @@ _RVC_TUPLES = ('unconj_param_unconj_vis', 'unconj_param_conj_vis', 'conj_param_u
                'sq_param_unconj_vis', 'sq_param_conj_vis')
 
 
-class RedVisCoupling(utils.Module, IndexCache):
+class RedVisCoupling(_CouplingTerm):
     """
     Mutual coupling with a redundant visibility model as input and all physical baselines as output
     (calibration.py:1588-2115):  Vc = A @ Vr + B @ conj(Vr),  A and B (Nbls_out, Nbls_in) matrices of the first-order terms
@@ -963,42 +933,17 @@ class RedVisCoupling(utils.Module, IndexCache):
     term on a visibility (plain / conjugated) the reference skips its second-order terms too, and so does the plan.
     Single polarisation; no CPU implementation.
     """
+    _clear_on_push = 'clear_vd_cache'          # a device push drops only the cached output
+    _push_names = _RVC_TUPLES + ('dly',)
+
     def __init__(self, params, freqs, antpos, coupling_terms, bls_in, bls_out, coupling_idx=None, R=None, parameter=True,
                  p0=None, name=None, atol=1e-5):
-        utils.Module.__init__(self, name=name)
-        self.params = torch.nn.Parameter(params) if parameter else params
-        self.p0 = p0
-        self.freqs = freqs
-        self.Nfreqs = len(freqs)
-        self.antpos = antpos
-        self.Nants = len(antpos)
-        self.c = 2.99792458e8
-        self.device = params.device
-        self.Npol = params.shape[0]
-        assert self.Npol == 1, "multi-pol not currently supported"
-        self.R = R if R is not None else VisModelResponse()
-        IndexCache.__init__(self, times=getattr(self.R, 'times', None), atol=atol)
-        self.clear_cache()
+        super().__init__(params, freqs, antpos, R, parameter, p0, name, atol)
         self.coupling_terms = coupling_terms
         self.coupling_idx = coupling_idx if coupling_idx is not None else {c: i for i, c in enumerate(coupling_terms)}
         self.Nterms = len(coupling_terms)
         self.bls_in, self.bls_out = bls_in, bls_out
         self.plan = None
-
-    def clear_cache(self):
-        """clear all caches, some come from IndexCache"""
-        self.clear_time_cache()
-        self.clear_bl_cache()
-        self.clear_vd_cache()
-
-    def clear_vd_cache(self):
-        self._vd = None
-
-    def __getstate__(self):
-        """pickle and deepcopy leave the cached output behind: after a forward its data is a node of an autograd graph"""
-        state = dict(self.__dict__)
-        state['_vd'] = None
-        return state
 
     def setup_coupling(self, use_reds=True, copydata=False, redtol=1.0, include_second_order=True, min_len=None,
                        max_len=None, max_EW=None, max_NS=None, second_max_len=None, second_max_EW=None, second_max_NS=None,
@@ -1014,16 +959,8 @@ class RedVisCoupling(utils.Module, IndexCache):
         with use_reds `red_bl_inds`, and `plan`, the ops.RedCouplingPlan of all of them.  ValueError for an output baseline
         with ant2 < ant1, a duplicate, or an antenna that is not in antpos.  Nproc, Ntask, use_pathos: ignored.
         """
-        seen, known = set(), set(self.antpos.keys())
-        for bl in self.bls_out:
-            bl = tuple(bl)
-            if bl[0] not in known or bl[1] not in known:
-                raise ValueError('baseline %s names an antenna that is not in antpos' % (bl,))
-            if bl[1] < bl[0]:
-                raise ValueError('baseline %s: RedVisCoupling needs ant2 >= ant1' % (bl,))
-            if bl in seen:
-                raise ValueError('baseline %s appears twice' % (bl,))
-            seen.add(bl)
+        known = set(self.antpos.keys())
+        _check_bls(self.bls_out, known, 'RedVisCoupling')
         for ct in self.coupling_terms:
             if ct[0] not in known or ct[1] not in known:
                 raise ValueError('coupling term %s names an antenna that is not in antpos' % (tuple(ct),))
@@ -1042,11 +979,8 @@ class RedVisCoupling(utils.Module, IndexCache):
         where = {a: i for i, a in enumerate(keys)}
         vecs = vecs.astype(np.float64)
         length = np.array([np.linalg.norm(vecs[where[a2]] - vecs[where[a1]]) for a1, a2 in self.coupling_terms])
-        if min_dly is not None:
-            length = np.maximum(length, min_dly)
-        fr = np.asarray(torch.as_tensor(self.freqs).detach().cpu(), dtype=np.float64)
-        phase = 2 * np.pi * (fr - fr[0])[None, :] / self.c * length[:, None]
-        self.dly = torch.as_tensor(np.exp(1j * phase)[None, None, :, None, :]).to(dtype=utils._cfloat(), device=self.device)
+        dly = _coupling_delay(length, self.freqs, min_dly, 1, self.c)
+        self.dly = torch.as_tensor(dly[None, None, :, None, :]).to(dtype=utils._cfloat(), device=self.device)
 
         Arows = configure_coupling_matrix_singlepath(self.antpos, bls=self.bls_out, bl2red=bl2red,
                                                      include_second_order=include_second_order, min_len=min_len,
@@ -1135,22 +1069,10 @@ class RedVisCoupling(utils.Module, IndexCache):
         cat = lambda x: np.concatenate([np.asarray(y, dtype=np.int64) for y in x])
         return ops.RedCouplingPlan(cat(row), cat(col), cat(cj), cat(a), cat(b), Nout, Nin, self.Nterms)
 
-    def index_params(self, params, times=None):
-        """overloads IndexCache.index_params: one time bin in params broadcasts"""
-        if times is not None and params.shape[-2] != 1:
-            params = IndexCache.index_params(self, params, times=times)
-        return params
-
     def forward(self, vd, prior_cache=None, **kwargs):
         """vd: VisData of shape (1, 1, Nbls_in, Ntimes, Nfreqs) holding bls_in in their order; returns a VisData of the
         baselines bls_out with the coupled visibilities (cached between calls, with new data)"""
-        if getattr(self, 'plan', None) is None:
-            raise RuntimeError('RedVisCoupling: run setup_coupling() before forward()')
-        if not vd.data.is_cuda:
-            raise RuntimeError('bayeslim_amd.calibration needs tensors on the GPU (no CPU implementation)')
-        if tuple(vd.data.shape[:3]) != (1, 1, self.plan.Nin):
-            raise ValueError('input of shape %s, RedVisCoupling was set up for (1, 1, %d, Ntimes, Nfreqs)'
-                             % (tuple(vd.data.shape), self.plan.Nin))
+        self._check_input(vd, 'Nin')
         if getattr(self, '_vd', None) is None:
             if self.use_reds:
                 take = lambda x: None if x is None else x.index_select(2, torch.as_tensor(self.red_bl_inds, device=x.device))
@@ -1163,39 +1085,10 @@ class RedVisCoupling(utils.Module, IndexCache):
             else:
                 self._vd = vd.copy(copydata=False)
         vout = self._vd
-        params = self.params if self.p0 is None else self.params + self.p0
-        coupling = self.R(params)
-        if getattr(self, '_hook_registry', None) is not None and coupling.requires_grad:
-            for r in self._hook_registry:
-                coupling.register_hook(r)
-        self.eval_prior(prior_cache, inp_params=self.params, out_params=coupling)
-        coupling = self.index_params(coupling, times=vd.times)
-        if not coupling.is_complex():
-            coupling = coupling.to(vd.data.dtype)
+        coupling = self._coupling(vd, prior_cache)
         out = ops.redcoupling_apply(coupling[0, 0], self.dly[0, 0, :, 0], vd.data[0, 0], self.plan)
         vout.data = out[None, None]
         return vout
-
-    def push(self, device):
-        """push to a new device or dtype"""
-        if not isinstance(device, torch.dtype):
-            self.device = device
-            self.clear_vd_cache()
-            if isinstance(self._times, torch.Tensor):
-                self._times = utils.push(self._times, device)
-            for k in _RVC_TUPLES:
-                if hasattr(self, k):
-                    setattr(self, k, tuple(a.to(device) for a in getattr(self, k)))
-        if hasattr(self, 'dly'):
-            self.dly = utils.push(self.dly, device)
-        self.params = utils.push(self.params, device)
-        self.R.push(device)
-        if self.p0 is not None:
-            self.p0 = utils.push(self.p0, device)
-        for prs in (self.priors_inp_params, self.priors_out_params):
-            for pr in (prs or []):
-                if pr is not None:
-                    pr.push(device)
 
     def get_coupling_hits(self):
         """{coupling term: how often the index tuples name its row}, counted as the reference counts (calibration.py:2092-2115:

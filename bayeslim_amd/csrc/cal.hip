@@ -12,14 +12,9 @@
 // the host side (deterministic).  Gains broadcast over time / channel through element strides (0).
 #include <hip/hip_runtime.h>
 #include "rime_common.h"
+#include "cplx.h"
 
 namespace rime {
-
-template <typename T> struct cx { T re, im; };
-template <typename T> __device__ __forceinline__ cx<T> cmul(cx<T> a, cx<T> b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-template <typename T> __device__ __forceinline__ cx<T> cmulc(cx<T> a, cx<T> b) { return {a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im}; }   // a conj(b)
-template <typename T> __device__ __forceinline__ cx<T> cconj(cx<T> a) { return {a.re, -a.im}; }
-template <typename T> __device__ __forceinline__ cx<T> cadd(cx<T> a, cx<T> b) { return {a.re + b.re, a.im + b.im}; }
 
 struct CalArgs {
     const void* vis; const void* gains; const void* gout;      // vis / gout [NP,NP,Nbl,Nt,Nf,2]; gains [NP,NP,Nant,Ntg,Nfg,2]

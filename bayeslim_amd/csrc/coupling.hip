@@ -19,6 +19,7 @@
 // null and clamps on the N, Nt, Nf edges (N and Nf need not be multiples of anything).
 #include <hip/hip_runtime.h>
 #include "rime_common.h"
+#include "cplx.h"
 
 namespace rime {
 
@@ -30,8 +31,6 @@ constexpr int CP_TK = 8;             // k slab held in LDS
 constexpr int CP_THREADS = CP_TS * CP_TS * CP_FR;                  // 512
 constexpr int CP_ROW = 0x3fffffff, CP_BIT = 0x40000000;            // table word: row, conjugate (operand) / single term (result)
 enum { CP_DENSE = 0, CP_TABLE = 1 };
-
-template <typename T> struct ccx { T re, im; };
 
 struct CpOperand {
     const void* p;                   // dense: (N, N, Tm, Fm) complex;  table: (Nrows, Nt, Nf) complex
@@ -55,9 +54,9 @@ struct CpArgs {
 
 // element (r, c) of op(O) at batch (t, f); zero outside the matrix and beyond the last channel
 template <typename T>
-__device__ __forceinline__ ccx<T> cp_fetch(const CpOperand& O, int r, int c, int t, int f, int N, int Nt, int Nf)
+__device__ __forceinline__ cx<T> cp_fetch(const CpOperand& O, int r, int c, int t, int f, int N, int Nt, int Nf)
 {
-    ccx<T> v = {T(0), T(0)};
+    cx<T> v = {T(0), T(0)};
     if (r >= N || c >= N || f >= Nf) return v;
     if (O.op) { const int s = r; r = c; c = s; }
     const size_t rc = (size_t)r * N + c;
@@ -65,14 +64,14 @@ __device__ __forceinline__ ccx<T> cp_fetch(const CpOperand& O, int r, int c, int
         const int e = O.tab[rc];
         const int row = e & CP_ROW;
         if (e < 0 || row >= O.Nrows) return v;
-        v = reinterpret_cast<const ccx<T>*>(O.p)[((size_t)row * Nt + t) * Nf + f];
+        v = reinterpret_cast<const cx<T>*>(O.p)[((size_t)row * Nt + t) * Nf + f];
         if (e & CP_BIT) v.im = -v.im;
     } else {
         const int tt = O.Tm == 1 ? 0 : t, ff = O.Fm == 1 ? 0 : f;
-        v = reinterpret_cast<const ccx<T>*>(O.p)[(rc * O.Tm + tt) * O.Fm + ff];
+        v = reinterpret_cast<const cx<T>*>(O.p)[(rc * O.Tm + tt) * O.Fm + ff];
         if (O.mul) {
-            const ccx<T> m = reinterpret_cast<const ccx<T>*>(O.mul)[rc * Nf + f];
-            v = {v.re * m.re - v.im * m.im, v.re * m.im + v.im * m.re};
+            const cx<T> m = reinterpret_cast<const cx<T>*>(O.mul)[rc * Nf + f];
+            v = cmul(v, m);
         }
         if (O.addI && r == c) v.re += T(1);
     }
@@ -82,8 +81,8 @@ __device__ __forceinline__ ccx<T> cp_fetch(const CpOperand& O, int r, int c, int
 
 // acc += op(A) . op(B) over all k in ascending order, for the block's tile (i0, j0) and channels f0 .. f0 + CP_FR - 1 of time t
 template <typename T>
-__device__ __forceinline__ void cp_accumulate(const CpOperand& A, const CpOperand& B, ccx<T> (&acc)[CP_TT][CP_TT],
-                                              ccx<T> (&As)[CP_TK][CP_TILE][CP_FR], ccx<T> (&Bs)[CP_TK][CP_TILE][CP_FR],
+__device__ __forceinline__ void cp_accumulate(const CpOperand& A, const CpOperand& B, cx<T> (&acc)[CP_TT][CP_TT],
+                                              cx<T> (&As)[CP_TK][CP_TILE][CP_FR], cx<T> (&Bs)[CP_TK][CP_TILE][CP_FR],
                                               int i0, int j0, int t, int f0, int N, int Nt, int Nf)
 {
     const int tid = threadIdx.x;
@@ -97,16 +96,13 @@ __device__ __forceinline__ void cp_accumulate(const CpOperand& A, const CpOperan
         __syncthreads();
 #pragma unroll
         for (int kk = 0; kk < CP_TK; ++kk) {
-            ccx<T> a[CP_TT], b[CP_TT];
+            cx<T> a[CP_TT], b[CP_TT];
 #pragma unroll
             for (int x = 0; x < CP_TT; ++x) { a[x] = As[kk][ti + CP_TS * x][lf]; b[x] = Bs[kk][tj + CP_TS * x][lf]; }
 #pragma unroll
             for (int x = 0; x < CP_TT; ++x)
 #pragma unroll
-                for (int y = 0; y < CP_TT; ++y) {
-                    acc[x][y].re = tfma<T>(-a[x].im, b[y].im, tfma<T>(a[x].re, b[y].re, acc[x][y].re));
-                    acc[x][y].im = tfma<T>(a[x].im, b[y].re, tfma<T>(a[x].re, b[y].im, acc[x][y].im));
-                }
+                for (int y = 0; y < CP_TT; ++y) cfma(acc[x][y], a[x], b[y]);
         }
         __syncthreads();                                       // the slabs are rewritten by the next step
     }
@@ -116,7 +112,7 @@ template <typename T>
 __global__ void __launch_bounds__(CP_THREADS)
 coupling_product_kernel(CpArgs P)
 {
-    __shared__ ccx<T> As[CP_TK][CP_TILE][CP_FR], Bs[CP_TK][CP_TILE][CP_FR];
+    __shared__ cx<T> As[CP_TK][CP_TILE][CP_FR], Bs[CP_TK][CP_TILE][CP_FR];
     const int N = P.N, Nt = P.Nt, Nf = P.Nf;
     const int nfr = (Nf + CP_FR - 1) / CP_FR;
     const int t = (int)(blockIdx.x / nfr), f0 = (int)(blockIdx.x % nfr) * CP_FR;
@@ -126,7 +122,7 @@ coupling_product_kernel(CpArgs P)
     const int f = f0 + lf;
     if (t >= Nt) return;                                       // block-uniform; the grid is exact, this is the clamp
 
-    ccx<T> acc[CP_TT][CP_TT];
+    cx<T> acc[CP_TT][CP_TT];
 #pragma unroll
     for (int x = 0; x < CP_TT; ++x)
 #pragma unroll
@@ -155,22 +151,22 @@ coupling_product_kernel(CpArgs P)
             const int i = i0 + ti + CP_TS * x, j = j0 + tj + CP_TS * y;
             if (i >= N || j >= N) continue;
             const size_t ij = (size_t)i * N + j;
-            ccx<T> v = acc[x][y];
+            cx<T> v = acc[x][y];
             if (P.C.mode == CP_TABLE) {
                 const int e = P.C.tab[ij];
                 const int row = e & CP_ROW;
                 if (e < 0 || row >= P.C.Nrows) continue;
-                reinterpret_cast<ccx<T>*>(P.C.p)[((size_t)row * Nt + t) * Nf + f] = v;
+                reinterpret_cast<cx<T>*>(P.C.p)[((size_t)row * Nt + t) * Nf + f] = v;
             } else {
                 if (P.add.p) {
-                    const ccx<T> s = cp_fetch<T>(P.add, i, j, t, f, N, Nt, Nf);
-                    v.re += s.re; v.im += s.im;
+                    const cx<T> s = cp_fetch<T>(P.add, i, j, t, f, N, Nt, Nf);
+                    v.re += s.re; v.im += s.im;                // `v += s` swaps the operands of the packed add
                 }
                 if (P.C.cmul) {
-                    const ccx<T> m = reinterpret_cast<const ccx<T>*>(P.C.cmul)[ij * Nf + f];
-                    v = {v.re * m.re + v.im * m.im, v.im * m.re - v.re * m.im};
+                    const cx<T> m = reinterpret_cast<const cx<T>*>(P.C.cmul)[ij * Nf + f];
+                    v = cmulc(v, m);
                 }
-                reinterpret_cast<ccx<T>*>(P.C.p)[(ij * Nt + t) * Nf + f] = v;
+                reinterpret_cast<cx<T>*>(P.C.p)[(ij * Nt + t) * Nf + f] = v;
             }
         }
 }
@@ -181,19 +177,19 @@ template <typename T>
 __global__ void __launch_bounds__(256)
 coupling_reduce_kernel(const void* in_, void* out_, size_t NN, int Nt, int Nf, int Tm, int Fm)
 {
-    const ccx<T>* in = reinterpret_cast<const ccx<T>*>(in_);
-    ccx<T>* out = reinterpret_cast<ccx<T>*>(out_);
+    const cx<T>* in = reinterpret_cast<const cx<T>*>(in_);
+    cx<T>* out = reinterpret_cast<cx<T>*>(out_);
     const size_t total = NN * Tm * Fm;
     for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (size_t)gridDim.x * blockDim.x) {
         const int fm = (int)(o % Fm), tm = (int)((o / Fm) % Tm);
         const size_t ab = o / ((size_t)Fm * Tm);
         const int ta = Tm == 1 ? 0 : tm, tb = Tm == 1 ? Nt : tm + 1;
         const int fa = Fm == 1 ? 0 : fm, fb = Fm == 1 ? Nf : fm + 1;
-        ccx<T> s = {T(0), T(0)};
+        cx<T> s = {T(0), T(0)};
         for (int t = ta; t < tb; ++t)
             for (int f = fa; f < fb; ++f) {
-                const ccx<T> v = in[(ab * Nt + t) * Nf + f];
-                s.re += v.re; s.im += v.im;
+                const cx<T> v = in[(ab * Nt + t) * Nf + f];
+                s.re += v.re; s.im += v.im;                    // `s += v` moves the zeroing of s in the double kernel
             }
         out[o] = s;
     }

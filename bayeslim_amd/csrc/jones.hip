@@ -16,14 +16,9 @@
 //   gJ2 = g^H (J1 S)        (real part for a real beam)
 #include <hip/hip_runtime.h>
 #include "rime_common.h"
+#include "cplx.h"
 
 namespace rime {
-
-template <typename T> struct cx { T x, y; };
-template <typename T> __device__ __forceinline__ cx<T> cmul(cx<T> a, cx<T> b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-template <typename T> __device__ __forceinline__ cx<T> cmulc(cx<T> a, cx<T> b) { return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y}; }   // a conj(b)
-template <typename T> __device__ __forceinline__ cx<T> cadd(cx<T> a, cx<T> b) { return {a.x + b.x, a.y + b.y}; }
-template <typename T> __device__ __forceinline__ cx<T> cconj(cx<T> a) { return {a.x, -a.y}; }
 
 template <typename T, bool REALB>
 __device__ __forceinline__ cx<T> load_j(const T* J, size_t plane, size_t N, size_t n)
@@ -104,7 +99,7 @@ jones_apply_bwd_kernel(const T* __restrict__ J1, const T* __restrict__ J2, const
     mmh(g, t, r);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        if constexpr (REALB) gJ1[(size_t)k * N + n] = r[k].x;
+        if constexpr (REALB) gJ1[(size_t)k * N + n] = r[k].re;
         else reinterpret_cast<cx<T>*>(gJ1)[(size_t)k * N + n] = r[k];
     }
     // gJ2 = g^H (J1 S)
@@ -112,7 +107,7 @@ jones_apply_bwd_kernel(const T* __restrict__ J1, const T* __restrict__ J2, const
     hmm(g, t, r);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        if constexpr (REALB) gJ2[(size_t)k * N + n] = r[k].x;
+        if constexpr (REALB) gJ2[(size_t)k * N + n] = r[k].re;
         else reinterpret_cast<cx<T>*>(gJ2)[(size_t)k * N + n] = r[k];
     }
 }
@@ -158,7 +153,7 @@ stokes2coh_bwd_kernel(const T* __restrict__ g, const T* __restrict__ fr, long lo
     const T fq = f[0], fu = f[fs_k], fv = f[2 * fs_k];
     const cx<T>* gg = reinterpret_cast<const cx<T>*>(g);
     const cx<T> g00 = gg[n], g01 = gg[N + n], g10 = gg[2 * N + n], g11 = gg[3 * N + n];
-    gI[n] = (g00.x + g11.x) + fq * (g00.x - g11.x) + fu * (g01.x + g10.x) + fv * (g10.y - g01.y);
+    gI[n] = (g00.re + g11.re) + fq * (g00.re - g11.re) + fu * (g01.re + g10.re) + fv * (g10.im - g01.im);
 }
 
 } // namespace rime

@@ -23,6 +23,7 @@
 // has range-checked (ops.RedCouplingPlan); the kernels also skip any word that points outside.
 #include <hip/hip_runtime.h>
 #include "rime_common.h"
+#include "cplx.h"
 #include "lane_vec.h"
 
 namespace rime {
@@ -30,8 +31,6 @@ namespace rime {
 constexpr int RC_WAVES = 4;          // waves of a block
 constexpr int RC_COLS = 64;          // columns of a work item = lanes of a wave
 constexpr int RC_IDX = 0x3fffffff, RC_FLAG = 0x40000000;       // column word: conjugated visibility; term word: role b
-
-template <typename T> struct qcx { T re, im; };
 
 struct RcArgs {
     const void* x; const void* dly; const void* data; const void* gout;     // [Nterms][Tm][Fm], [Nterms][Nf], [Nin][Nt][Nf], [Nout][Nt][Nf]
@@ -42,43 +41,24 @@ struct RcArgs {
     int Nout, Nin, Nterms, Nent, Nmem, Nseg, seg, Nt, Nf, Tm, Fm;
 };
 
-template <typename T> __device__ __forceinline__ qcx<T> q_mul(qcx<T> a, qcx<T> b)          // a b
-{
-    return {tfma<T>(-a.im, b.im, a.re * b.re), tfma<T>(a.im, b.re, a.re * b.im)};
-}
-template <typename T> __device__ __forceinline__ qcx<T> q_mulc(qcx<T> a, qcx<T> b)         // a conj(b)
-{
-    return {tfma<T>(a.im, b.im, a.re * b.re), tfma<T>(a.im, b.re, -(a.re * b.im))};
-}
-template <typename T> __device__ __forceinline__ void q_fma(qcx<T>& s, qcx<T> a, qcx<T> b) // s += a b
-{
-    s.re = tfma<T>(-a.im, b.im, tfma<T>(a.re, b.re, s.re));
-    s.im = tfma<T>(a.im, b.re, tfma<T>(a.re, b.im, s.im));
-}
-template <typename T> __device__ __forceinline__ void q_fmac(qcx<T>& s, qcx<T> a, qcx<T> b) // s += conj(a) b
-{
-    s.re = tfma<T>(a.im, b.im, tfma<T>(a.re, b.re, s.re));
-    s.im = tfma<T>(-a.im, b.re, tfma<T>(a.re, b.im, s.im));
-}
-
 // C[c] = x[c] o dly[c] at (t, f); c in [0, Nterms)
 template <typename T>
-__device__ __forceinline__ qcx<T> rc_C(const RcArgs& A, int c, int t, int f)
+__device__ __forceinline__ cx<T> rc_C(const RcArgs& A, int c, int t, int f)
 {
     const int tt = A.Tm == 1 ? 0 : t, ff = A.Fm == 1 ? 0 : f;
-    qcx<T> v = reinterpret_cast<const qcx<T>*>(A.x)[((size_t)c * A.Tm + tt) * A.Fm + ff];
-    if (A.dly) v = q_mul<T>(v, reinterpret_cast<const qcx<T>*>(A.dly)[(size_t)c * A.Nf + f]);
+    cx<T> v = reinterpret_cast<const cx<T>*>(A.x)[((size_t)c * A.Tm + tt) * A.Fm + ff];
+    if (A.dly) v = cmul_fma<T>(v, reinterpret_cast<const cx<T>*>(A.dly)[(size_t)c * A.Nf + f]);
     return v;
 }
 
 template <typename T>
-__device__ __forceinline__ qcx<T> rc_coef(const RcArgs& A, int a, int b, int t, int f)
+__device__ __forceinline__ cx<T> rc_coef(const RcArgs& A, int a, int b, int t, int f)
 {
-    qcx<T> k = {T(1), T(0)};
+    cx<T> k = {T(1), T(0)};
     if (a >= 0) k = rc_C<T>(A, a, t, f);
     if (b >= 0) {
-        const qcx<T> cb = rc_C<T>(A, b, t, f);
-        k = a >= 0 ? q_mulc<T>(k, cb) : qcx<T>{cb.re, -cb.im};
+        const cx<T> cb = rc_C<T>(A, b, t, f);
+        k = a >= 0 ? cmulc_fma<T>(k, cb) : cx<T>{cb.re, -cb.im};
     }
     return k;
 }
@@ -103,23 +83,23 @@ redcoupling_row_kernel(RcArgs A)
     const size_t ncol = (size_t)A.Nt * A.Nf, ntile = (ncol + RC_COLS - 1) / RC_COLS;
     const int nrow = BWD ? A.Nin : A.Nout;
     const size_t nwork = (size_t)nrow * ntile;
-    const qcx<T>* src = reinterpret_cast<const qcx<T>*>(BWD ? A.gout : A.data);
-    qcx<T>* out = reinterpret_cast<qcx<T>*>(A.out);
+    const cx<T>* src = reinterpret_cast<const cx<T>*>(BWD ? A.gout : A.data);
+    cx<T>* out = reinterpret_cast<cx<T>*>(A.out);
     for (size_t wk = (size_t)blockIdx.x * RC_WAVES + w; wk < nwork; wk += (size_t)gridDim.x * RC_WAVES) {
         const int r = (int)(wk / ntile);
         const size_t col = (wk % ntile) * RC_COLS + lane;
         if (col >= ncol) continue;
         const int t = (int)(col / A.Nf), f = (int)(col % A.Nf);
         const int m0 = max(A.off[r], 0), m1 = min(A.off[r + 1], A.Nent);
-        qcx<T> acc = {T(0), T(0)};
+        cx<T> acc = {T(0), T(0)};
         for (int m = m0; m < m1; ++m) {
             RcEntry E;
             if (!rc_entry(A, BWD ? A.mem[m] : m, E)) continue;
-            const qcx<T> k = rc_coef<T>(A, E.a, E.b, t, f);
-            qcx<T> v = src[(size_t)(BWD ? E.i : E.j) * ncol + col];
+            const cx<T> k = rc_coef<T>(A, E.a, E.b, t, f);
+            cx<T> v = src[(size_t)(BWD ? E.i : E.j) * ncol + col];
             if (E.cj) v.im = -v.im;                             // forward: conj(data);  backward: coef conj(g)
-            if (BWD && !E.cj) q_fmac<T>(acc, k, v);             // conj(coef) g
-            else q_fma<T>(acc, k, v);
+            if (BWD && !E.cj) cfmac<T>(acc, k, v);             // conj(coef) g
+            else cfma<T>(acc, k, v);
         }
         out[(size_t)r * ncol + col] = acc;
     }
@@ -133,16 +113,16 @@ redcoupling_seg_kernel(RcArgs A)
     const int lane = threadIdx.x % RC_COLS, w = threadIdx.x / RC_COLS;
     const size_t ncol = (size_t)A.Nt * A.Nf, ntile = (ncol + RC_COLS - 1) / RC_COLS;
     const size_t nwork = (size_t)A.Nseg * ntile;
-    const qcx<T>* data = reinterpret_cast<const qcx<T>*>(A.data);
-    const qcx<T>* gout = reinterpret_cast<const qcx<T>*>(A.gout);
-    qcx<T>* ws = reinterpret_cast<qcx<T>*>(A.ws);
+    const cx<T>* data = reinterpret_cast<const cx<T>*>(A.data);
+    const cx<T>* gout = reinterpret_cast<const cx<T>*>(A.gout);
+    cx<T>* ws = reinterpret_cast<cx<T>*>(A.ws);
     for (size_t wk = (size_t)blockIdx.x * RC_WAVES + w; wk < nwork; wk += (size_t)gridDim.x * RC_WAVES) {
         const int s = (int)(wk / ntile);
         const size_t col = (wk % ntile) * RC_COLS + lane;
         if (col >= ncol) continue;
         const int t = (int)(col / A.Nf), f = (int)(col % A.Nf);
         const int c = A.segterm[s];
-        qcx<T> acc = {T(0), T(0)};
+        cx<T> acc = {T(0), T(0)};
         if ((unsigned)c < (unsigned)A.Nterms) {
             const int m0 = max(A.segstart[s], 0);
             const int m1 = min(min(m0 + A.seg, A.off[c + 1]), A.Nmem);
@@ -150,18 +130,18 @@ redcoupling_seg_kernel(RcArgs A)
                 const int word = A.mem[m];
                 RcEntry E;
                 if (word < 0 || !rc_entry(A, word & RC_IDX, E)) continue;
-                qcx<T> v = data[(size_t)E.j * ncol + col];
+                cx<T> v = data[(size_t)E.j * ncol + col];
                 if (E.cj) v.im = -v.im;
-                const qcx<T> g = gout[(size_t)E.i * ncol + col];
+                const cx<T> g = gout[(size_t)E.i * ncol + col];
                 if (word & RC_FLAG) {                           // role b: w' conj(g)
-                    if (E.a >= 0) v = q_mul<T>(rc_C<T>(A, E.a, t, f), v);
-                    q_fma<T>(acc, v, qcx<T>{g.re, -g.im});
+                    if (E.a >= 0) v = cmul_fma<T>(rc_C<T>(A, E.a, t, f), v);
+                    cfma<T>(acc, v, cx<T>{g.re, -g.im});
                 } else {                                        // role a: conj(w) g
-                    if (E.b >= 0) v = q_mulc<T>(v, rc_C<T>(A, E.b, t, f));
-                    q_fmac<T>(acc, v, g);
+                    if (E.b >= 0) v = cmulc_fma<T>(v, rc_C<T>(A, E.b, t, f));
+                    cfmac<T>(acc, v, g);
                 }
             }
-            if (A.dly) acc = q_mulc<T>(acc, reinterpret_cast<const qcx<T>*>(A.dly)[(size_t)c * A.Nf + f]);
+            if (A.dly) acc = cmulc_fma<T>(acc, reinterpret_cast<const cx<T>*>(A.dly)[(size_t)c * A.Nf + f]);
         }
         ws[(size_t)s * ncol + col] = acc;
     }
@@ -172,10 +152,10 @@ template <typename T>
 __global__ void __launch_bounds__(RC_WAVES * RC_COLS)
 redcoupling_combine_kernel(RcArgs A)
 {
-    __shared__ qcx<T> part[RC_WAVES - 1][RC_COLS];
+    __shared__ cx<T> part[RC_WAVES - 1][RC_COLS];
     const int lane = threadIdx.x % RC_COLS, w = threadIdx.x / RC_COLS;
-    const qcx<T>* ws = reinterpret_cast<const qcx<T>*>(A.ws);
-    qcx<T>* gx = reinterpret_cast<qcx<T>*>(A.out);
+    const cx<T>* ws = reinterpret_cast<const cx<T>*>(A.ws);
+    cx<T>* gx = reinterpret_cast<cx<T>*>(A.out);
     const int nft = A.Fm == 1 ? 1 : (A.Nf + RC_COLS - 1) / RC_COLS;
     const size_t nwork = (size_t)A.Nterms * A.Tm * nft;
     for (size_t wk = blockIdx.x; wk < nwork; wk += gridDim.x) {                  // block-uniform trip count
@@ -183,11 +163,11 @@ redcoupling_combine_kernel(RcArgs A)
         const int s0 = max(A.tsoff[c], 0), s1 = min(A.tsoff[c + 1], A.Nseg);
         const int ta = A.Tm == 1 ? 0 : tm, tb = A.Tm == 1 ? A.Nt : tm + 1;
         const int fa = ft * RC_COLS + lane, fb = A.Fm == 1 ? A.Nf : min(fa + 1, A.Nf);
-        qcx<T> acc = {T(0), T(0)};
+        cx<T> acc = {T(0), T(0)};
         for (int s = s0 + w; s < s1; s += RC_WAVES)
             for (int t = ta; t < tb; ++t)
                 for (int f = fa; f < fb; f += RC_COLS) {
-                    const qcx<T> v = ws[((size_t)s * A.Nt + t) * A.Nf + f];
+                    const cx<T> v = ws[((size_t)s * A.Nt + t) * A.Nf + f];
                     acc.re += v.re; acc.im += v.im;
                 }
         if (A.Fm == 1) { acc.re = wave_sum<T>(acc.re); acc.im = wave_sum<T>(acc.im); }

@@ -14,13 +14,12 @@
 // written exactly once (groups and model times without members get 0); no atomics, no workspace, no prior memset.
 #include <hip/hip_runtime.h>
 #include "rime_common.h"
+#include "cplx.h"
 
 namespace rime {
 
 constexpr int RV_WAVES = 4;          // waves of a backward block = slices of a group's member list
 constexpr int RV_COLS = 64;          // columns (model time x channel) of a backward block = lanes of a wave
-
-template <typename T> struct rcx { T re, im; };
 
 struct RedVisArgs {
     const void* vis; const void* model; void* out;             // vis / out [NP*NP, Nbl, Nt, Nf] complex; model strided
@@ -37,9 +36,9 @@ __global__ void __launch_bounds__(256)
 redvis_fwd_kernel(RedVisArgs A)
 {
     const size_t plane = (size_t)A.Nbl * A.Nt * A.Nf;          // complex elements per pol entry of vis
-    const rcx<T>* vis = reinterpret_cast<const rcx<T>*>(A.vis);
-    const rcx<T>* model = reinterpret_cast<const rcx<T>*>(A.model);
-    rcx<T>* out = reinterpret_cast<rcx<T>*>(A.out);
+    const cx<T>* vis = reinterpret_cast<const cx<T>*>(A.vis);
+    const cx<T>* model = reinterpret_cast<const cx<T>*>(A.model);
+    cx<T>* out = reinterpret_cast<cx<T>*>(A.out);
     const T s = (T)A.sign;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < plane; i += (size_t)gridDim.x * blockDim.x) {
         const int f = (int)(i % A.Nf);
@@ -51,9 +50,9 @@ redvis_fwd_kernel(RedVisArgs A)
         const size_t mo = in ? (size_t)r * A.mst_r + (size_t)tm * A.mst_t + (size_t)f * A.mst_f : 0;
 #pragma unroll
         for (int p = 0; p < NP * NP; ++p) {
-            rcx<T> m = model[mo + (size_t)p * A.mst_p];
+            cx<T> m = model[mo + (size_t)p * A.mst_p];
             if (!in) m = {T(0), T(0)};
-            rcx<T> v = {T(0), T(0)};
+            cx<T> v = {T(0), T(0)};
             if (vis) v = vis[(size_t)p * plane + i];
             out[(size_t)p * plane + i] = {v.re + s * m.re, v.im + s * m.im};
         }
@@ -64,9 +63,9 @@ template <typename T>
 __global__ void __launch_bounds__(RV_WAVES * RV_COLS)
 redvis_bwd_kernel(RedVisArgs A)
 {
-    __shared__ rcx<T> part[RV_WAVES - 1][RV_COLS];
-    const rcx<T>* gout = reinterpret_cast<const rcx<T>*>(A.gout);
-    rcx<T>* gmodel = reinterpret_cast<rcx<T>*>(A.gmodel);
+    __shared__ cx<T> part[RV_WAVES - 1][RV_COLS];
+    const cx<T>* gout = reinterpret_cast<const cx<T>*>(A.gout);
+    cx<T>* gmodel = reinterpret_cast<cx<T>*>(A.gmodel);
     const int lane = threadIdx.x % RV_COLS, w = threadIdx.x / RV_COLS;
     const size_t ncol = (size_t)A.Ntm * A.Nf;                  // columns of one (pol entry, group)
     const size_t ntile = (ncol + RV_COLS - 1) / RV_COLS;
@@ -78,7 +77,7 @@ redvis_bwd_kernel(RedVisArgs A)
         const int r = (int)(wk / ntile);
         const size_t col = (wk % ntile) * RV_COLS + lane;
         const int m0 = max(A.goff[r], 0), m1 = min(A.goff[r + 1], A.Nbl);        // the host checks the tables; never read outside
-        rcx<T> acc = {T(0), T(0)};
+        cx<T> acc = {T(0), T(0)};
         if (col < ncol) {
             const int tp = (int)(col / A.Nf), f = (int)(col % A.Nf);
             const int q0 = max(A.toff[tp], 0), q1 = min(A.toff[tp + 1], A.Nt);
@@ -90,8 +89,8 @@ redvis_bwd_kernel(RedVisArgs A)
                 for (int m = m0 + w; m < m1; m += RV_WAVES) {
                     const int b = A.gmem[m];
                     if ((unsigned)b >= (unsigned)A.Nbl) continue;
-                    const rcx<T> g = gout[base + (size_t)b * row];
-                    acc.re += g.re; acc.im += g.im;
+                    const cx<T> g = gout[base + (size_t)b * row];
+                    acc += g;
                 }
             }
         }

@@ -41,30 +41,17 @@ class SkyBase(utils.Module):
     def _push(self, device, attrs=[]):
         if not isinstance(device, torch.dtype):
             self.device = device
-        self.params = utils.push(self.params, device)
         for a in attrs:
             if hasattr(self, a):
                 setattr(self, a, getattr(self, a).to(device))
-        self.R.push(device)
-        if self.p0 is not None:
-            self.p0 = utils.push(self.p0, device)
         if isinstance(self.angs, torch.Tensor):
             self.angs = utils.push(self.angs, device)
         else:
             self.angs = tuple(utils.push(a, device) for a in self.angs)
-        for prs in (self.priors_inp_params, self.priors_out_params):
-            for pr in (prs or []):
-                if pr is not None:
-                    pr.push(device)
-
-    def _forward_params(self, params):
-        params = self.params if params is None else params
-        return params if self.p0 is None else params + self.p0
+        self._push_params(device)
 
     def _emit(self, sky, prior_cache):
-        if getattr(self, '_hook_registry', None) is not None and sky.requires_grad:
-            for r in self._hook_registry:
-                sky.register_hook(r)
+        self._hook_response(sky)
         self.eval_prior(prior_cache, inp_params=self.params, out_params=sky)
         out = dataset.MapData()
         out.setup_meta(name=getattr(self, 'name', None))
@@ -82,7 +69,7 @@ class PointSky(SkyBase):
         self.angs = angs
 
     def forward(self, params=None, prior_cache=None, **kwargs):
-        sky = self.R(self._forward_params(params))
+        sky = self.R(self._full_params(params))
         out, freqs, angs = self._emit(sky, prior_cache)
         out.setup_data(freqs=freqs, data=sky, angs=angs)
         return out
@@ -145,7 +132,7 @@ class PixelSky(SkyBase):
         self.px_area = torch.as_tensor(px_area)
 
     def forward(self, params=None, prior_cache=None, **kwargs):
-        sky = self.R(self._forward_params(params))
+        sky = self.R(self._full_params(params))
         out, freqs, angs = self._emit(sky, prior_cache)
         if self.px_area.device != sky.device:
             self.px_area = self.px_area.to(sky.device)      # once: a per-call H2D copy is a host sync

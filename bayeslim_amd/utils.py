@@ -503,10 +503,7 @@ class Module(torch.nn.Module):
                     val = val + pr(inp_params)
         if self.priors_out_params is not None:
             if out_params is None and hasattr(self, 'params') and hasattr(self, 'R'):
-                p = self.params
-                if getattr(self, 'p0', None) is not None:
-                    p = p + self.p0
-                out_params = self.R(p)
+                out_params = self.R(self._full_params())
             if out_params is not None:
                 for pr in self.priors_out_params:
                     if pr is not None:
@@ -517,6 +514,30 @@ class Module(torch.nn.Module):
         if registry is not None and not isinstance(registry, (list, tuple)):
             registry = [registry]
         self._hook_registry = registry
+
+    # the three pieces every module with params / p0 / R shares
+    def _full_params(self, params=None):
+        """params (default self.params) + p0 when p0 is set: what the response R is called with"""
+        params = self.params if params is None else params
+        p0 = getattr(self, 'p0', None)
+        return params if p0 is None else params + p0
+
+    def _hook_response(self, out):
+        """register every hook of register_response_hooks on the response output, if it requires grad"""
+        if getattr(self, '_hook_registry', None) is not None and out.requires_grad:
+            for r in self._hook_registry:
+                out.register_hook(r)
+
+    def _push_params(self, device):
+        """the tail of every push(): params, R, p0 and the priors of both lists, in that order"""
+        self.params = push(self.params, device)
+        self.R.push(device)
+        if self.p0 is not None:
+            self.p0 = push(self.p0, device)
+        for prs in (self.priors_inp_params, self.priors_out_params):
+            for pr in (prs or []):
+                if pr is not None:
+                    pr.push(device)
 
     def clear_graph_tensors(self):
         pass

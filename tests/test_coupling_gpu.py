@@ -203,6 +203,13 @@ def test_no_grad_saves_nothing_and_module_caches():
     assert torch.equal(m(vd, double=None).data, m(vd, double=True).data)
 
 
+def test_deepcopy_after_backward():
+    """hex-7, 2 times, 3 channels: a deep copy taken after forward and backward holds no cached output and computes the same
+    bits; the original's cached output is untouched"""
+    import calterm_common as ct
+    ct.check_deepcopy_after_backward('VisCoupling', DEV)
+
+
 def test_chain_in_logprob_and_identity_coupling():
     """Sequential(RedVisModel -> VisCoupling -> JonesModel) in optim.LogProb on hex-7: closure() gives a finite loss and finite,
     non-zero gradients of all three parameter tensors; with X = 0 and add_I the coupling stage returns its input bit for bit"""

@@ -211,6 +211,14 @@ def test_vd_cache_and_push_round_trip():
     assert model._vd is None and model.cache_bidx == {} and model.cache_tidx == {}
 
 
+@pytest.mark.parametrize('name', ['JonesModel', 'RedVisModel'])
+def test_deepcopy_after_backward(name):
+    """hex-7, 2 times, 3 channels: a deep copy taken after forward and backward holds no cached output (whose data is a node
+    of the graph for RedVisModel) and computes the same bits"""
+    import calterm_common as ct
+    ct.check_deepcopy_after_backward(name, DEV)
+
+
 def test_remove_redcal_degen_with_redvis_against_the_reference():
     from bayeslim_amd import calibration as cal, utils
     g = rc.golden()

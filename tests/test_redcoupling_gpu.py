@@ -212,6 +212,13 @@ def test_analytic_check(second):
     assert r <= 1.0 and np.abs(want).max() > 0
 
 
+def test_deepcopy_after_backward():
+    """hex-7, 2 times, 3 channels: a deep copy taken after forward and backward holds no cached output and computes the same
+    bits; the original's cached output is untouched"""
+    import calterm_common as ct
+    ct.check_deepcopy_after_backward('RedVisCoupling', DEV)
+
+
 def test_chain_in_logprob():
     """Sequential(RedVisModel -> RedVisCoupling -> JonesModel) in optim.LogProb on the fixture's array: closure() gives a finite
     loss and finite, non-zero gradients of all three parameter tensors; with zero coupling the stage is the inflation, bit for bit"""
