@@ -203,6 +203,42 @@ class FringeGeometry:
             self.mp_offsets = (ctypes.c_int * (self.Nmp + 1))(*[int(o) for o in offs])
             self.bl_order = torch.as_tensor(order, dtype=torch.int32, device=dev)
 
+    def _setup_antenna_path(self, antpos, bl_ants, force=False, bl_mp=None, mp_pairs=None, group=None):
+        """enable the antenna-factored matrix-core kernels when the baseline set suits them: self.ant"""
+        group = group or MFMA_GROUP
+        Nant = int(antpos.shape[0])
+        bl_ants = [(int(a), int(b)) for a, b in bl_ants]
+        ant_model = _antenna_models(self, Nant, bl_ants, force, bl_mp, mp_pairs)
+        if ant_model is False:
+            return
+        posh = antpos.detach().to(torch.float64).cpu().numpy()
+        # a point-symmetric array of more than 128 antennas with one beam model: symmetric groups (_pair_cross_plan)
+        plan = None
+        if PAIR_CROSS and MIRROR and PAIR and ant_model is None and group == MFMA_GROUP and Nant > MFMA_GROUP:
+            plan = _pair_cross_plan(posh, bl_ants)
+        raw = _antenna_blocks(bl_ants, Nant, bl_mp if ant_model is not None else None, ant_model, group,
+                              groups=None if plan is None else plan['ants'])
+        if raw is None:
+            return
+        # the factorisation must reproduce the baseline vectors it replaces
+        dev = self.blvecs.device
+        pos = antpos.detach().to(torch.float64).to(dev).contiguous()
+        i1 = torch.as_tensor([a for a, _ in bl_ants], device=dev)
+        i2 = torch.as_tensor([b for _, b in bl_ants], device=dev)
+        if not torch.allclose(pos[i2] - pos[i1], self.blvecs, rtol=0, atol=1e-9):
+            return
+        blocks = [_plain_block(r, pos, dev) for r in raw]
+        ant = dict(blocks=blocks, Nant=Nant, two_pass_mask=_two_pass_mask(blocks, raw, self.Nbl, dev), multi_model=ant_model is not None)
+        if MIRROR:
+            ant.update(_symmetric_forms(blocks, raw, posh, plan, dev, self.Nbl))
+        # executed matrix-core work per real-psky pass, from the blocks that run it: MFMAs per 16 pixels (_mfma_counts) of
+        # 2*32*32*16 flop each
+        run = ant.get('blocks_real', blocks)
+        per16 = self.Nt * self.Nf * (self.Pstride // 16) * 32768
+        ant['mfma_fwd'], ant['mfma_bwd'] = sum(b['mf_fwd'] for b in run), sum(b['mf_bwd_real'] for b in run)
+        ant['mfma_flops_fwd'], ant['mfma_flops_bwd'] = per16 * ant['mfma_fwd'], per16 * ant['mfma_bwd']
+        self.ant = ant
+
 
 def _env_int(name, default):
     """C atoi() of an environment variable (leading integer, else 0), as csrc/ reads its switches"""
@@ -274,8 +310,7 @@ def _antenna_blocks(bl_ants, Nant, bl_mp=None, ant_model=None, group=MFMA_GROUP,
 
     def get(key):
         if key not in tabs:
-            tabs[key] = (np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32),
-                         np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32))
+            tabs[key] = (_slot_table(), _slot_table())
         return tabs[key]
 
     for b, (a1, a2) in enumerate(bl_ants):
@@ -297,7 +332,7 @@ def _antenna_blocks(bl_ants, Nant, bl_mp=None, ant_model=None, group=MFMA_GROUP,
     blocks = []
 
     def compact(tab, rows, cols):
-        out = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
+        out = _slot_table()
         out[:len(rows), :len(cols)] = tab[np.ix_(rows, cols)]
         return out
 
@@ -427,7 +462,88 @@ def _mirror_order(P, packed=None):
     return rows, (1 << Gm) - 1, c
 
 
-def _mirror_block(blk, P, dev):
+# THE BLOCK PLAN.  A block is a dict; the mirror, pair and pair cross forms below are their plain block on new rows.
+
+
+def _mfma_counts(kind, ri, rj=0, hub=False):
+    """(mf_fwd, mf_bwd, mf_bwd_real, mf_self) of one block: MFMAs per 16-pixel K step of the real-psky forward, the one-pass
+    complex backward, the real-psky backward and the one-pass complex forward (None: the form has no such pass).  A full
+    32 x 32 antenna tile takes 12 MFMAs of 2*32*32*16 flop (3 hi/lo products x 4 real products)."""
+    if kind == 'diag':
+        # ri antennas in TA row tiles: 12 per tile above the diagonal; a diagonal tile 7 forward (symmetric products folded) and
+        # 9 backward (symmetric form, round 3); 33..48 antennas on the packed forward: 7 + 6 + 3 = 16 (round 4); the complex
+        # passes run all TA (TA + 1) / 2 tiles in full (mf_self: where the block runs as a self block, _plain_block)
+        TA = (ri + 31) // 32
+        off, full = 12 * (TA * (TA - 1) // 2), 12 * (TA * (TA + 1) // 2)
+        return 16 if (32 < ri <= 48 and FWD_PACKED) else off + 7 * TA, full, off + 9 * TA, full
+    if kind == 'cross':                                      # ri x rj rows of the kernel's shape: every tile in full
+        mf = 12 * (ri // 32) * (rj // 32)
+        return mf, mf, mf, None
+    if kind == 'pair':
+        # ri rows: one row tile (<= 32 rows, no hub) 7 and 9 as a diagonal tile; two row tiles 26 (against 63 / 100 of the
+        # three- / four-tile plain kernels) and 30
+        return 26 if ri > 32 or hub else 7, None, 30 if ri > 32 else 9, None
+    # forward 12 on each of the four tiles whatever the row counts (48); backward 12 per (row tile of I that holds a row, 16 rows
+    # of J that hold a row) and 32 pixels (64 x 64 rows: 48).  A mirror block keeps the counts of its plain block.
+    assert kind == 'xpair', kind
+    return 48, None, 6 * ((ri + 31) // 32) * ((rj + 15) // 16), None
+
+
+def _slot_table(rows=MFMA_GROUP):
+    return np.full((rows, MFMA_GROUP), -1, dtype=np.int32)
+
+
+def _assert_slots_once(slots, *tables):
+    """every baseline slot of `slots` sits in exactly one entry of `tables` (a row order must never drop or double one)"""
+    out = np.sort(np.concatenate([t[t >= 0] for t in tables]))
+    assert np.array_equal(out, np.sort(slots)) and (np.diff(out) > 0).all()
+
+
+def _remap_tables(od, oc, vrow, hub=None):
+    """
+    The slot tables of a diagonal block on new rows, numpy in and out.  od[i, j] = b: baseline b runs from antenna i to antenna
+    j, oc[i, j] = b: from j to i (_antenna_blocks); vrow[a]: the row of antenna a.  Returns (direct, conj, centre): a baseline
+    from row r1 to row r2 sits in direct[r1, r2] where r1's row tile is not behind r2's, else in conj[r2, r1]; the baselines of
+    `hub`, an antenna served outside the rows, in centre[0, r] (hub -> row r) or centre[1, r] (row r -> hub) (None: no hub).
+    None when the hub's autocorrelation is asked for (not a column sum of the image).
+    """
+    od, oc = (np.asarray(t).reshape(MFMA_GROUP, MFMA_GROUP) for t in (od, oc))
+    (i, j), (k, l) = np.nonzero(od >= 0), np.nonzero(oc >= 0)
+    a1, a2 = np.concatenate([i, l]), np.concatenate([j, k])            # every baseline runs from antenna a1 to antenna a2
+    slot = np.concatenate([od[i, j], oc[k, l]])
+    h1, h2 = a1 == (-1 if hub is None else hub), a2 == (-1 if hub is None else hub)
+    if (h1 & h2).any():
+        return None
+    r1, r2 = np.asarray(vrow)[a1], np.asarray(vrow)[a2]
+    assert (r1[~h1] >= 0).all() and (r2[~h2] >= 0).all()                # every antenna has a row
+    direct, conj, centre = _slot_table(), _slot_table(), (None if hub is None else _slot_table(2))
+    if hub is not None:
+        centre[0, r2[h1]] = slot[h1]
+        centre[1, r1[h2]] = slot[h2]
+    up = ~(h1 | h2) & (r1 // 32 <= r2 // 32)
+    down = ~(h1 | h2) & (r1 // 32 > r2 // 32)
+    direct[r1[up], r2[up]] = slot[up]
+    conj[r2[down], r1[down]] = slot[down]
+    _assert_slots_once(slot, *(t for t in (direct, conj, centre) if t is not None))
+    return direct, conj, centre
+
+
+def _derived_block(blk, dev, pos, direct, conj, mf=None, **keys):
+    """the plain block `blk` on new rows: their positions and slot tables on `dev`, the counts `mf` the form has of its own
+    (_mfma_counts), the keys of the form; one real plane per call (no single complex pass forward, no self block)"""
+    dev_t = lambda x: torch.as_tensor(x, device=dev).contiguous()
+    keys.update({k: v for k, v in zip(('mf_fwd', 'mf_bwd', 'mf_bwd_real'), mf or ()) if v is not None})
+    return dict(blk, pos=dev_t(pos), direct=dev_t(direct.reshape(-1)), conj=dev_t(conj.reshape(-1)), fwd_cpass=0,
+                self_pos=None, mf_self=0, **keys)
+
+
+def _plain_tables(blk, host):
+    """(direct, conj) of the plain block `blk` as numpy: `host`, the arrays its device tables were made from, where the caller
+    still has them, else read back from the device"""
+    return host if host is not None else tuple(blk[k].cpu().numpy() for k in ('direct', 'conj'))
+
+
+def _mirror_block(blk, P, dev, host=None):
     """the mirrored form of a built diagonal block (see _mirror_order): positions measured from the centre of symmetry in
     the new row order, pair tables rebuilt for it, `mirror` mask; None when the block has no usable symmetry"""
     n = int(blk['nrows'])
@@ -438,31 +554,15 @@ def _mirror_block(blk, P, dev):
         return None
     rows, mask, c = found
     newrow = -np.ones(n, dtype=np.int64)
-    for r, a in enumerate(rows):
-        if a >= 0:
-            newrow[a] = r
-    assert (newrow >= 0).all() and len(rows) <= 32 * ((n + 31) // 32)
     pos = np.zeros((len(rows), 3))
     for r, a in enumerate(rows):
         if a >= 0:
-            pos[r] = P[a] - c
-    direct = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
-    conj = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
-    od, oc = blk['direct'].reshape(MFMA_GROUP, MFMA_GROUP).cpu().numpy(), blk['conj'].reshape(MFMA_GROUP, MFMA_GROUP).cpu().numpy()
-    # direct[i, j] = b: baseline b runs from antenna i to antenna j; conj[i, j] = b: from j to i (_antenna_blocks)
-    for tab, swap in ((od, False), (oc, True)):
-        for i, j in zip(*np.nonzero(tab >= 0)):
-            a1, a2 = (j, i) if swap else (i, j)
-            r1, r2 = newrow[a1], newrow[a2]
-            if r1 // 32 <= r2 // 32:
-                direct[r1, r2] = tab[i, j]
-            else:
-                conj[r2, r1] = tab[i, j]
+            newrow[a], pos[r] = r, P[a] - c
+    assert (newrow >= 0).all() and len(rows) <= 32 * ((n + 31) // 32)
+    direct, conj, _ = _remap_tables(*_plain_tables(blk, host), newrow)
     nd, nc = int((direct >= 0).sum()), int((conj >= 0).sum())
-    assert nd + nc == int((od >= 0).sum()) + int((oc >= 0).sum())
-    return dict(blk, pos=torch.as_tensor(pos, device=dev).contiguous(), nrows=len(rows), mirror=int(mask), rows=list(rows),
-                cpass=(1 if nc == 0 else (-1 if nd == 0 else 0)), fwd_cpass=0, self_pos=None, mf_self=0,
-                direct=torch.as_tensor(direct.reshape(-1), device=dev), conj=torch.as_tensor(conj.reshape(-1), device=dev))
+    return _derived_block(blk, dev, pos, direct, conj, nrows=len(rows), mirror=int(mask), rows=list(rows),
+                          cpass=(1 if nc == 0 else (-1 if nd == 0 else 0)))
 
 
 # CONJUGATE-PAIR FORM (round 5; csrc/fringe_mfma.hip, "CONJUGATE-PAIR FORM"): a diagonal block of a point-symmetric array
@@ -578,13 +678,30 @@ def _pair_ap_order(pos):
     return order
 
 
-def _pair_block(blk, P, dev):
+def _pair_rows(firsts, partner):
+    """{antenna: virtual row} of the pair forms: row k holds firsts[k], row 64 + k its mirror antenna"""
+    rows = {int(a): k for k, a in enumerate(firsts)}
+    rows.update({int(b): 64 + k for k, b in enumerate(partner) if b >= 0})
+    return rows
+
+
+def _rows_from_centre(P, rows, c):
+    """(pos, flat): the positions of the antennas `rows` measured from the centre c.  A coplanar array measured from a centre
+    in its plane has z = 0 within the tolerance of the pairing itself -> exactly 0 and the `flat` licence (the kernels skip that
+    term of the phase)"""
+    pos = np.asarray(P)[rows] - c
+    flat = int(np.abs(pos[:, 2]).max() <= MIRROR_TOL)
+    if flat:
+        pos[:, 2] = 0.0
+    return pos, flat
+
+
+def _pair_block(blk, P, dev, host=None):
     """the conjugate-pair form of a built diagonal block (include/rime_hip.h, rime_fringe_pair_fwd_block): positions of the
     rows from the centre of symmetry, the pair tables of the virtual 128-row block (row k: firsts[k], row 64 + k: its
     mirror), the hub's slot table; None when the block does not qualify.  More than 64 antennas: up to 64 rows + the hub (two
-    row tiles: 26 MFMAs per K step against 63 / 100 of the three- / four-tile kernels); 33..64 antennas: up to 32 rows (one row
-    tile: 7 against 16 / 26); up to 32 antennas keep the one-tile kernels (the same 7 MFMAs; their generation is already
-    halved by the mirror pairs)."""
+    row tiles); 33..64 antennas: up to 32 rows (one row tile); up to 32 antennas keep the one-tile kernels (the same MFMAs,
+    _mfma_counts; their generation is already halved by the mirror pairs)."""
     n = int(blk['nrows'])
     if blk['cross'] != 0 or n <= 32:
         return None
@@ -592,50 +709,19 @@ def _pair_block(blk, P, dev):
     if lay is None:
         return None
     firsts, partner, hub, c = lay
-    od, oc = blk['direct'].reshape(MFMA_GROUP, MFMA_GROUP).cpu().numpy(), blk['conj'].reshape(MFMA_GROUP, MFMA_GROUP).cpu().numpy()
+    od, oc = _plain_tables(blk, host)
 
     def tables(firsts, partner):
         vrow = -np.ones(n, dtype=np.int64)
-        for k, (a, b) in enumerate(zip(firsts, partner)):
-            vrow[a] = k
-            if b >= 0:
-                vrow[b] = 64 + k
-        direct = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
-        conj = np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32)
-        centre = np.full((2, MFMA_GROUP), -1, dtype=np.int32)
-        # direct[i, j] = b: baseline b runs from antenna i to antenna j; conj[i, j] = b: from j to i (_antenna_blocks)
-        for tab, swap in ((od, False), (oc, True)):
-            for i, j in zip(*np.nonzero(tab >= 0)):
-                a1, a2 = (j, i) if swap else (i, j)
-                if a1 == hub and a2 == hub:
-                    return None                                  # the hub's autocorrelation: not a column sum of the image
-                if a1 == hub:
-                    centre[0, vrow[a2]] = tab[i, j]
-                elif a2 == hub:
-                    centre[1, vrow[a1]] = tab[i, j]
-                else:
-                    r1, r2 = vrow[a1], vrow[a2]
-                    if r1 // 32 <= r2 // 32:
-                        direct[r1, r2] = tab[i, j]
-                    else:
-                        conj[r2, r1] = tab[i, j]
-        nslots = int((direct >= 0).sum()) + int((conj >= 0).sum()) + int((centre >= 0).sum())
-        assert nslots == int((od >= 0).sum()) + int((oc >= 0).sum())
-        # ... and every baseline slot of the plain block exactly once (a row order must never drop or double one)
-        slots = np.sort(np.concatenate([t[t >= 0] for t in (direct, conj, centre)]))
-        assert np.array_equal(slots, np.sort(np.concatenate([od[od >= 0], oc[oc >= 0]]))) and (np.diff(slots) > 0).all()
-        return direct, conj, centre
+        rows = _pair_rows(firsts, partner)
+        vrow[list(rows)] = list(rows.values())
+        return _remap_tables(od, oc, vrow, hub)
 
     tabs = tables(firsts, partner)
     if tabs is None:
-        return None
+        return None                                          # the hub's autocorrelation is asked for
     direct, conj, centre = tabs
-    pos = np.asarray(P)[firsts] - c
-    # a coplanar array measured from a centre in its plane: z = 0 within the tolerance of the pairing itself -> exactly 0 and
-    # the `flat` licence (the kernels skip that term of the phase)
-    flat = int(np.abs(pos[:, 2]).max() <= MIRROR_TOL)
-    if flat:
-        pos[:, 2] = 0.0
+    pos, flat = _rows_from_centre(P, firsts, c)
     dev_t = lambda x: torch.as_tensor(x, device=dev).contiguous()
     # the backward's own row order (round 6, _pair_ap_order): the same rows permuted, tables rebuilt for them; the forward keeps
     # the plain order, so no bit of it moves
@@ -646,12 +732,9 @@ def _pair_block(blk, P, dev):
         bd, bc, bcen = tables(bf, bp)
         bwd = dict(firsts=bf, partner=bp, pos=dev_t(pos[order]), direct=dev_t(bd.reshape(-1)), conj=dev_t(bc.reshape(-1)),
                    centre=None if hub is None else dev_t(bcen.reshape(-1)))
-    return dict(blk, pos=torch.as_tensor(pos, device=dev).contiguous(), nrows=len(firsts), mirror=0, pair=1,
-                firsts=list(firsts), partner=list(partner), hub=hub, flat=flat, bwd=bwd,
-                centre=None if hub is None else torch.as_tensor(centre.reshape(-1), device=dev),
-                cpass=0, fwd_cpass=0, self_pos=None, mf_self=0, mf_fwd=26 if len(firsts) > 32 or hub is not None else 7,
-                mf_bwd_real=30 if len(firsts) > 32 else 9,
-                direct=torch.as_tensor(direct.reshape(-1), device=dev), conj=torch.as_tensor(conj.reshape(-1), device=dev))
+    return _derived_block(blk, dev, pos, direct, conj, _mfma_counts('pair', len(firsts), hub=hub is not None), nrows=len(firsts),
+                          mirror=0, pair=1, firsts=list(firsts), partner=list(partner), hub=hub, flat=flat, bwd=bwd, cpass=0,
+                          centre=None if hub is None else dev_t(centre.reshape(-1)))
 
 
 # PAIR CROSS BLOCKS (csrc/fringe_xpair.hip): a point-symmetric array of MORE than MFMA_GROUP antennas.  The cut by index makes
@@ -671,22 +754,21 @@ def _plain_plan_cost(P, bl_ants, group=MFMA_GROUP):
     sizes = [min(group, Nant - k) for k in range(0, Nant, group)]
     mf = rows = 0
     for g, n in enumerate(sizes):
-        TA = (n + 31) // 32
         lay = None
         if n > 32 and PAIR:
             lay = _pair_layout(P[g * group:g * group + n]) if n > 64 else _pair_layout(P[g * group:g * group + n], rows=32, hub_ok=False)
         if lay is not None:
-            mf += 26 if n > 64 else 7
+            mf += _mfma_counts('pair', len(lay[0]), hub=lay[2] is not None)[0]
             rows += len(lay[0])
         else:
-            mf += 16 if (32 < n <= 48 and FWD_PACKED) else 12 * (TA * (TA - 1) // 2) + 7 * TA
+            mf += _mfma_counts('diag', n)[0]
             rows += n
     shared = {(min(a // group, b // group), max(a // group, b // group)) for a, b in bl_ants if a // group != b // group}
     for x, y in shared:
         ci, cj = _group_capacity(sizes[x], group), _group_capacity(sizes[y], group)
         if (ci, cj) not in ((32, 32), (32, 64), (64, 32), (64, 64), (128, 128)):
             ci = cj = 128
-        mf += 12 * (ci // 32) * (cj // 32)
+        mf += _mfma_counts('cross', ci, cj)[0]
         rows += sizes[x] + sizes[y]
     return mf, rows
 
@@ -724,12 +806,14 @@ def _pair_cross_plan(antpos, bl_ants, rows=PAIR_ROWS):
     assert len(groups) == G and all(len(g['firsts']) <= rows for g in groups)
     gid, vrow = {}, {}
     for g, grp in enumerate(groups):
-        for k, (a, b) in enumerate(zip(grp['firsts'], grp['partner'])):
-            gid[a], vrow[a] = g, k
-            if b >= 0:
-                gid[b], vrow[b] = g, 64 + k
+        grp_rows = _pair_rows(grp['firsts'], grp['partner'])
+        vrow.update(grp_rows)
+        gid.update(dict.fromkeys(grp_rows, g))
     assert len(gid) == Nant
-    cross = {}
+    # the tables of a cross block are filled from the baseline list itself (no plain block exists yet), rows from group I and
+    # columns from group J, the orientation decided by the order of the GROUPS -- not by row tiles as inside a diagonal block
+    # (_remap_tables); what the two share: the virtual rows and the exactly-once check
+    cross, slots = {}, {}
     seen = set()
     for slot, (a1, a2) in enumerate(bl_ants):
         a1, a2 = int(a1), int(a2)
@@ -741,25 +825,24 @@ def _pair_cross_plan(antpos, bl_ants, rows=PAIR_ROWS):
             continue
         key = (min(g1, g2), max(g1, g2))
         if key not in cross:
-            cross[key] = dict(direct=np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32),
-                              conj=np.full((MFMA_GROUP, MFMA_GROUP), -1, dtype=np.int32))
+            cross[key], slots[key] = dict(direct=_slot_table(), conj=_slot_table()), []
+        slots[key].append(slot)
         if g1 < g2:
             cross[key]['direct'][vrow[a1], vrow[a2]] = slot          # I -> J: V[r, c]
         else:
             cross[key]['conj'][vrow[a2], vrow[a1]] = slot            # J -> I: conj(V[r, c])
-    # cost against the groups by index: matrix work and generated rows, both must shrink
+    # cost against the groups by index: matrix work and generated rows, both must shrink; every group costed as a pair block of
+    # two row tiles (64 rows), whatever its rows
     bl = [(int(a), int(b)) for a, b in bl_ants]
-    mf_new = 26 * G + 48 * len(cross)
+    mf_new = _mfma_counts('pair', 64)[0] * G + _mfma_counts('xpair', 64, 64)[0] * len(cross)
     rows_new = R + sum(len(groups[gi]['firsts']) + len(groups[gj]['firsts']) for gi, gj in cross)
     mf_old, rows_old = _plain_plan_cost(P, bl)
     if mf_new >= mf_old or rows_new >= rows_old:
         return None
     for (gi, gj), blk in cross.items():
+        _assert_slots_once(slots[gi, gj], blk['direct'], blk['conj'])
         fi, fj = groups[gi]['firsts'], groups[gj]['firsts']
-        pos = np.concatenate([P[fi], P[fj]]) - c
-        flat = int(np.abs(pos[:, 2]).max() <= MIRROR_TOL)
-        if flat:
-            pos[:, 2] = 0.0
+        pos, flat = _rows_from_centre(P, fi + fj, c)
         blk.update(rows_i=len(fi), rows_j=len(fj), pos=pos, flat=flat)
     return dict(centre=c, groups=groups, cross=cross,
                 ants=[g['firsts'] + [b for b in g['partner'] if b >= 0] for g in groups])
@@ -767,13 +850,10 @@ def _pair_cross_plan(antpos, bl_ants, rows=PAIR_ROWS):
 
 def _pair_cross_block(blk, plan_blk, dev):
     """the device form of one block of _pair_cross_plan in place of the built plain cross block `blk` (include/rime_hip.h,
-    rime_fringe_pair_cross_fwd_block).  MFMAs per 16-pixel K step: forward 12 on each of the four tiles, whatever the row counts
-    (48); backward 12 per (row tile of I that holds a row, 16 rows of J that hold a row) and 32 pixels (64 x 64 rows: 48)."""
+    rime_fringe_pair_cross_fwd_block)"""
     ri, rj = int(plan_blk['rows_i']), int(plan_blk['rows_j'])
-    dev_t = lambda x: torch.as_tensor(x, device=dev).contiguous()
-    return dict(blk, pos=dev_t(plan_blk['pos']), nrows=ri + rj, rows_i=ri, rows_j=rj, xpair=1, mirror=0, flat=int(plan_blk['flat']),
-                cpass=0, fwd_cpass=0, self_pos=None, mf_self=0, mf_fwd=48, mf_bwd_real=6 * ((ri + 31) // 32) * ((rj + 15) // 16),
-                direct=dev_t(plan_blk['direct'].reshape(-1)), conj=dev_t(plan_blk['conj'].reshape(-1)))
+    return _derived_block(blk, dev, plan_blk['pos'], plan_blk['direct'], plan_blk['conj'], _mfma_counts('xpair', ri, rj),
+                          nrows=ri + rj, rows_i=ri, rows_j=rj, xpair=1, mirror=0, flat=int(plan_blk['flat']), cpass=0)
 
 
 def _dense_strides(t):
@@ -934,20 +1014,18 @@ def _fringe_ant_call(geom, backward, inp, out, strides, Npp, cplx):
     return flops * per16
 
 
-def _setup_antenna_path(self, antpos, bl_ants, force=False, bl_mp=None, mp_pairs=None, group=MFMA_GROUP):
-    """enable the antenna-factored matrix-core kernels when the baseline set suits them"""
-    Nant = int(antpos.shape[0])
-    bl_ants = [(int(a), int(b)) for a, b in bl_ants]
-    if Nant > MFMA_MAX_ANTS or len(bl_ants) != self.Nbl or self.Nt > 65535:      # (reduce kernels: t on grid.z)
-        return
+def _antenna_models(geom, Nant, bl_ants, force, bl_mp, mp_pairs):
+    """whether the baseline set suits the antenna-factored kernels, and the beam model of every antenna: False (it does not),
+    None (one model for all) or the list of models"""
+    if Nant > MFMA_MAX_ANTS or len(bl_ants) != geom.Nbl or geom.Nt > 65535:      # (reduce kernels: t on grid.z)
+        return False
     # worth it when the array needs at least two 32-antenna tiles and most pairs are requested
     # (measured against the baseline-formulation kernels: 128 antennas / 8128 baselines 4.8x (fwd)
     # and 5.8x (bwd) faster; 37 antennas / 666 baselines 1.1x and 1.6x faster; 19 antennas 1.7x and
     # 1.1x slower)
-    if not force and (Nant < MFMA_MIN_ANTS or self.Nbl < Nant * Nant // 8):
-        return
+    if not force and (Nant < MFMA_MIN_ANTS or geom.Nbl < Nant * Nant // 8):
+        return False
     # several beam models: every antenna must carry ONE model (beam_model.py:303-327 pairs models per baseline)
-    ant_model = None
     if bl_mp is not None and mp_pairs is not None and len(mp_pairs) > 1:
         ant_model = [None] * Nant
         for (a1, a2), mp in zip(bl_ants, bl_mp):
@@ -955,114 +1033,87 @@ def _setup_antenna_path(self, antpos, bl_ants, force=False, bl_mp=None, mp_pairs
                 if ant_model[ant] is None:
                     ant_model[ant] = mdl
                 elif ant_model[ant] != mdl:
-                    return
-        ant_model = [0 if mdl is None else mdl for mdl in ant_model]
-    elif bl_mp is not None and any(int(x) != 0 for x in bl_mp):          # (bl_mp is only passed when Nmp > 1)
+                    return False
+        return [0 if mdl is None else mdl for mdl in ant_model]
+    if bl_mp is not None and any(int(x) != 0 for x in bl_mp):            # (bl_mp is only passed when Nmp > 1)
         # without a model table the blocks read psky plane 0: several planes, or one plane that is not plane 0,
         # stay on the baseline-formulation kernels
-        return
-    # a point-symmetric array of more than 128 antennas with one beam model: symmetric groups (_pair_cross_plan)
-    plan = None
-    if PAIR_CROSS and MIRROR and PAIR and ant_model is None and group == MFMA_GROUP and Nant > MFMA_GROUP:
-        plan = _pair_cross_plan(antpos.detach().to(torch.float64).cpu().numpy(), bl_ants)
-    raw = _antenna_blocks(bl_ants, Nant, bl_mp if ant_model is not None else None, ant_model, group,
-                          groups=None if plan is None else plan['ants'])
-    if raw is None:
-        return
-    # the factorisation must reproduce the baseline vectors it replaces
-    pos = antpos.detach().to(torch.float64).to(self.blvecs.device).contiguous()
-    i1 = torch.as_tensor([a for a, _ in bl_ants], device=pos.device)
-    i2 = torch.as_tensor([b for _, b in bl_ants], device=pos.device)
-    if not torch.allclose(pos[i2] - pos[i1], self.blvecs, rtol=0, atol=1e-9):
-        return
-    dev = self.blvecs.device
-    blocks, mfma_fwd, mfma_bwd = [], 0, 0
-    two_pass_mask = torch.zeros(self.Nbl, 1, 1, 1, dtype=torch.float32, device=dev)
-    for blk in raw:
-        pi = pos[torch.as_tensor(blk['ants_i'], device=dev)]
-        if blk['ants_j'] is None:
-            rows, TA = pi.contiguous(), (pi.shape[0] + 31) // 32
-            mf_fwd = 12 * (TA * (TA - 1) // 2) + 7 * TA      # diagonal tiles: symmetric products folded
-            if 32 < pi.shape[0] <= 48 and FWD_PACKED:
-                mf_fwd = 16                                  # packed second row tile (round 4): 7 + 6 + 3 MFMAs per K step
-            mf_bwd = 12 * (TA * (TA + 1) // 2)
-            mf_bwd_real = 12 * (TA * (TA - 1) // 2) + 9 * TA   # real psky: symmetric form on the diagonal tiles (round 3)
-            cross, fwd_cpass = 0, 0                          # forward diagonal blocks: one real plane per call ...
-            self_pos, mf_self = None, 0
-            if SELF_BLOCKS and blk['cpass'] != 0:
-                # ... unless psky is complex and every baseline has one orientation: then the block runs as the
-                # triangular cross block of the group with itself, ONE complex pass (rime_fringe_ant_fwd_block
-                # with cross == Nrows)
-                self_pos = torch.zeros(TA * 32, 3, dtype=torch.float64, device=dev)
-                self_pos[:pi.shape[0]] = pi
-                mf_self = 12 * (TA * (TA + 1) // 2)
-                fwd_cpass = blk['cpass']
-        else:
-            self_pos, mf_self = None, 0
-            pj = pos[torch.as_tensor(blk['ants_j'], device=dev)]
-            rows = torch.zeros(blk['rows_i'] + blk['rows_j'], 3, dtype=torch.float64, device=dev)
-            rows[:pi.shape[0]] = pi
-            rows[blk['rows_i']:blk['rows_i'] + pj.shape[0]] = pj
-            mf_fwd = mf_bwd = mf_bwd_real = 12 * (blk['rows_i'] // 32) * (blk['rows_j'] // 32)
-            cross, fwd_cpass = blk['rows_i'], blk['cpass']
-        if fwd_cpass == 0:
-            slots = np.concatenate([blk['direct'][blk['direct'] >= 0], blk['conj'][blk['conj'] >= 0]])
-            two_pass_mask[torch.as_tensor(slots, dtype=torch.int64, device=dev)] = 1.0
-        blocks.append(dict(pos=rows, nrows=int(rows.shape[0]), cross=int(cross), mp=blk['mp'], mirror=0,
-                           cpass=blk['cpass'], fwd_cpass=fwd_cpass, mf_fwd=mf_fwd, mf_bwd=mf_bwd, mf_bwd_real=mf_bwd_real,
-                           self_pos=self_pos, mf_self=mf_self,
-                           direct=torch.as_tensor(blk['direct'].reshape(-1), device=dev),
-                           conj=torch.as_tensor(blk['conj'].reshape(-1), device=dev)))
-        mfma_fwd += mf_fwd
-        mfma_bwd += mf_bwd_real
-    # executed matrix-core work per pass: per 16 pixels, 12 MFMAs of 2*32*32*16 flop on each 32x32
-    # antenna tile of every block (3 hi/lo products x 4 real products); the forward runs 7 on the
-    # diagonal tiles of a diagonal block
-    per16 = self.Nt * self.Nf * (self.Pstride // 16) * 32768
-    self.ant = dict(blocks=blocks, Nant=Nant, mfma_fwd=mfma_fwd, mfma_bwd=mfma_bwd, two_pass_mask=two_pass_mask,
-                    mfma_flops_fwd=per16 * mfma_fwd, mfma_flops_bwd=per16 * mfma_bwd,
-                    multi_model=ant_model is not None)
-    # arrays with point symmetry: the REAL-psky passes run on mirrored forms of the diagonal blocks (conjugate phasors are
-    # not evaluated twice); complex psky keeps the plain blocks (its single-pass forms depend on the pair orientation, which
-    # a re-ordering of the rows changes)
-    if MIRROR:
-        posh = pos.cpu().numpy()
-        mb = [(_mirror_block(b, posh[np.asarray(r['ants_i'])], dev) if r['ants_j'] is None else None) for b, r in zip(blocks, raw)]
-        # ... and, where a block of more than 64 antennas fits into 64 rows of firsts (+ the hub), on the conjugate-pair form,
-        # which does not contract the mirror rows either
-        pb = [(_pair_block(b, posh[np.asarray(r['ants_i'])], dev) if (PAIR and r['ants_j'] is None) else None)
-              for b, r in zip(blocks, raw)]
-        # ... and the blocks between the symmetric groups of a larger array on the pair cross form
-        xb = [None] * len(blocks)
-        if plan is not None:
-            xb = [(_pair_cross_block(b, plan['cross'][(min(r['gi'], r['gj']), max(r['gi'], r['gj']))], dev)
-                   if r['ants_j'] is not None else None) for b, r in zip(blocks, raw)]
-            pb = [x if x is not None else q for x, q in zip(xb, pb)]
-        if any(m is not None for m in mb) or any(q is not None for q in pb):
-            self.ant['blocks_mirror'] = [m if m is not None else b for m, b in zip(mb, blocks)]
-            self.ant['blocks_real'] = [q if q is not None else m for q, m in zip(pb, self.ant['blocks_mirror'])]
-            self.ant['mirror_groups'] = [(bin(m['mirror']).count('1'), (m['nrows'] + 15) // 16)
-                                         for m, q in zip(mb, pb) if m is not None and q is None]
-            self.ant['pair_blocks'] = [(sum(1 for x in q['partner'] if x >= 0), q['nrows'], int(q['hub'] is not None))
-                                       for q in pb if q is not None and not q.get('xpair')]
+        return False
+    return None
+
+
+def _plain_block(r, pos, dev):
+    """the block `r` of _antenna_blocks as the kernels take it: the positions of its rows (pos: every antenna, on `dev`), its
+    tables on `dev`, its counts"""
+    pi = pos[torch.as_tensor(r['ants_i'], device=dev)]
+    self_pos, mf_self = None, 0
+    if r['ants_j'] is None:
+        rows, (mf_fwd, mf_bwd, mf_bwd_real, mf_full) = pi.contiguous(), _mfma_counts('diag', pi.shape[0])
+        cross, fwd_cpass = 0, 0                              # forward diagonal blocks: one real plane per call ...
+        if SELF_BLOCKS and r['cpass'] != 0:
+            # ... unless psky is complex and every baseline has one orientation: then the block runs as the
+            # triangular cross block of the group with itself, ONE complex pass (rime_fringe_ant_fwd_block
+            # with cross == Nrows)
+            self_pos = torch.zeros((pi.shape[0] + 31) // 32 * 32, 3, dtype=torch.float64, device=dev)
+            self_pos[:pi.shape[0]] = pi
+            fwd_cpass, mf_self = r['cpass'], mf_full
+    else:
+        pj = pos[torch.as_tensor(r['ants_j'], device=dev)]
+        rows = torch.zeros(r['rows_i'] + r['rows_j'], 3, dtype=torch.float64, device=dev)
+        rows[:pi.shape[0]] = pi
+        rows[r['rows_i']:r['rows_i'] + pj.shape[0]] = pj
+        cross, fwd_cpass = r['rows_i'], r['cpass']
+        mf_fwd, mf_bwd, mf_bwd_real, _ = _mfma_counts('cross', r['rows_i'], r['rows_j'])
+    return dict(pos=rows, nrows=int(rows.shape[0]), cross=int(cross), mp=r['mp'], mirror=0, cpass=r['cpass'], fwd_cpass=fwd_cpass,
+                mf_fwd=mf_fwd, mf_bwd=mf_bwd, mf_bwd_real=mf_bwd_real, self_pos=self_pos, mf_self=mf_self,
+                direct=torch.as_tensor(r['direct'].reshape(-1), device=dev), conj=torch.as_tensor(r['conj'].reshape(-1), device=dev))
+
+
+def _two_pass_mask(blocks, raw, Nbl, dev):
+    """float32 (Nbl, 1, 1, 1): 1 on the baseline slots of the blocks of a list whose complex forward takes one pass per real
+    plane (fwd_cpass == 0), 0 on the slots of its single-pass blocks.  The slots are read from the host tables `raw` of the
+    plain blocks: a derived form holds exactly the slots of its plain block (_assert_slots_once)."""
+    mask = torch.zeros(Nbl, 1, 1, 1, dtype=torch.float32, device=dev)
+    slots = [r[k][r[k] >= 0] for b, r in zip(blocks, raw) if b['fwd_cpass'] == 0 for k in ('direct', 'conj')]
+    if slots:
+        mask[torch.as_tensor(np.concatenate(slots), dtype=torch.int64, device=dev)] = 1.0
+    return mask
+
+
+def _symmetric_forms(blocks, raw, posh, plan, dev, Nbl):
+    """
+    The keys that point symmetry adds to geom.ant ({}: no block has a symmetric form).  The REAL-psky passes run every block
+    on the first form it has (blocks_real): the pair cross form between the symmetric groups of a larger array (`plan`,
+    _pair_cross_plan), the conjugate-pair form, which does not contract the mirror rows either, the mirror form (conjugate
+    phasors are not evaluated twice; blocks_mirror), the plain block.  Complex psky keeps the plain blocks (their single-pass
+    forms depend on the pair orientation, which a re-ordering of the rows changes) except where a block has a pair form: two
+    real passes of that (blocks_cplx).
+    """
+    mirror, real, cplx, mirror_groups, pair_blocks, pair_cross_blocks = [], [], [], [], [], []
+    for b, r in zip(blocks, raw):
+        m = q = None
+        if r['ants_j'] is not None:
             if plan is not None:
-                self.ant['pair_cross_blocks'] = [(x['rows_i'], x['rows_j']) for x in xb if x is not None]
-            if PAIR_CPLX and any(q is not None for q in pb):
-                # complex psky: pair blocks (two real passes: fwd_cpass = cpass = 0) in place of their plain blocks
-                self.ant['blocks_cplx'] = [q if q is not None else b for q, b in zip(pb, blocks)]
-                mask = torch.zeros_like(two_pass_mask)
-                for b in self.ant['blocks_cplx']:
-                    if b['fwd_cpass'] == 0:
-                        tabs = [b['direct'], b['conj']] + ([b['centre']] if b.get('centre') is not None else [])
-                        slots = torch.cat([t[t >= 0] for t in tabs]).to(torch.int64)
-                        mask[slots] = 1.0
-                self.ant['two_pass_mask_cplx'] = mask
-            self.ant['mfma_fwd'] = sum(b['mf_fwd'] for b in self.ant['blocks_real'])
-            self.ant['mfma_bwd'] = sum(b['mf_bwd_real'] for b in self.ant['blocks_real'])
-            self.ant['mfma_flops_fwd'], self.ant['mfma_flops_bwd'] = per16 * self.ant['mfma_fwd'], per16 * self.ant['mfma_bwd']
-
-
-FringeGeometry._setup_antenna_path = _setup_antenna_path
+                q = _pair_cross_block(b, plan['cross'][(min(r['gi'], r['gj']), max(r['gi'], r['gj']))], dev)
+                pair_cross_blocks.append((q['rows_i'], q['rows_j']))
+        else:
+            P, host = posh[np.asarray(r['ants_i'])], (r['direct'], r['conj'])
+            m, q = _mirror_block(b, P, dev, host), (_pair_block(b, P, dev, host) if PAIR else None)
+            if q is not None:
+                pair_blocks.append((sum(1 for x in q['partner'] if x >= 0), q['nrows'], int(q['hub'] is not None)))
+            elif m is not None:
+                mirror_groups.append((bin(m['mirror']).count('1'), (m['nrows'] + 15) // 16))
+        mirror.append(b if m is None else m)
+        real.append(mirror[-1] if q is None else q)
+        cplx.append(b if q is None else q)
+    if all(x is b for x, b in zip(mirror + real, blocks + blocks)):
+        return {}
+    forms = dict(blocks_mirror=mirror, blocks_real=real, mirror_groups=mirror_groups, pair_blocks=pair_blocks)
+    if plan is not None:
+        forms['pair_cross_blocks'] = pair_cross_blocks
+    if PAIR_CPLX and (pair_blocks or pair_cross_blocks):
+        forms.update(blocks_cplx=cplx, two_pass_mask_cplx=_two_pass_mask(cplx, raw, Nbl, dev))
+    return forms
 
 
 def _fringe_algorithmic_bytes(geom, a, b):
