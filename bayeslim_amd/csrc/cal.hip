@@ -165,10 +165,7 @@ extern "C" int rime_apply_cal_fwd(int dtype, int NP, int diag, const void* vis, 
     A.vis = vis; A.gains = gains; A.a1 = a1; A.a2 = a2; A.out = out;
     A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nant = Nant;
     A.gst_p = gst_p; A.gst_a = gst_a; A.gst_t = gst_t; A.gst_f = gst_f;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32) return cal_launch<float, false>(A, NP, diag, st);
-    if (dtype == RIME_F64) return cal_launch<double, false>(A, NP, diag, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) { return cal_launch<decltype(t), false>(A, NP, diag, as_stream(stream)); });
 }
 
 extern "C" int rime_apply_cal_bwd(int dtype, int NP, int diag, const void* vis, const void* gains, const void* gout,
@@ -181,8 +178,5 @@ extern "C" int rime_apply_cal_bwd(int dtype, int NP, int diag, const void* vis, 
     A.vis = vis; A.gains = gains; A.gout = gout; A.a1 = a1; A.a2 = a2; A.gvis = gvis; A.d1 = d1; A.d2 = d2;
     A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nant = Nant;
     A.gst_p = gst_p; A.gst_a = gst_a; A.gst_t = gst_t; A.gst_f = gst_f;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32) return cal_launch<float, true>(A, NP, diag, st);
-    if (dtype == RIME_F64) return cal_launch<double, true>(A, NP, diag, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) { return cal_launch<decltype(t), true>(A, NP, diag, as_stream(stream)); });
 }

@@ -75,33 +75,26 @@ extern "C" int rime_chisq_fwd(int dtype, const void* pred, const void* data, con
 {
     if (!pred || !out || N == 0) return RIME_EINVAL;
     if (!workspace || workspace_bytes < rime_chisq_workspace()) return RIME_EWORKSPACE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nb = (int)std::min<size_t>((N + 255) / 256, CHI_BLOCKS);
     double* part = (double*)workspace;
-    if (dtype == RIME_F32) {
-        hipLaunchKernelGGL((chisq_partial_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)pred,
-                           (const float*)data, (const float*)icov, N, part);
-        hipLaunchKernelGGL((chisq_final_kernel<float>), dim3(1), dim3(256), 0, st, part, nb, (float*)out);
-    } else if (dtype == RIME_F64) {
-        hipLaunchKernelGGL((chisq_partial_kernel<double>), dim3(nb), dim3(256), 0, st, (const double*)pred,
-                           (const double*)data, (const double*)icov, N, part);
-        hipLaunchKernelGGL((chisq_final_kernel<double>), dim3(1), dim3(256), 0, st, part, nb, (double*)out);
-    } else return RIME_EINVAL;
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((chisq_partial_kernel<T>), dim3(nb), dim3(256), 0, as_stream(stream), (const T*)pred,
+                           (const T*)data, (const T*)icov, N, part);
+        hipLaunchKernelGGL((chisq_final_kernel<T>), dim3(1), dim3(256), 0, as_stream(stream), part, nb, (T*)out);
+        return check_launch();
+    });
 }
 
 extern "C" int rime_chisq_bwd(int dtype, const void* pred, const void* data, const void* icov, const void* g,
                               size_t N, void* gpred, void* stream)
 {
     if (!pred || !g || !gpred || N == 0) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int nb = (int)std::min<size_t>((N + 255) / 256, 8192);
-    if (dtype == RIME_F32)
-        hipLaunchKernelGGL((chisq_bwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)pred, (const float*)data,
-                           (const float*)icov, (const float*)g, N, (float*)gpred);
-    else if (dtype == RIME_F64)
-        hipLaunchKernelGGL((chisq_bwd_kernel<double>), dim3(nb), dim3(256), 0, st, (const double*)pred,
-                           (const double*)data, (const double*)icov, (const double*)g, N, (double*)gpred);
-    else return RIME_EINVAL;
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((chisq_bwd_kernel<T>), dim3(nb), dim3(256), 0, as_stream(stream), (const T*)pred,
+                           (const T*)data, (const T*)icov, (const T*)g, N, (T*)gpred);
+        return check_launch();
+    });
 }

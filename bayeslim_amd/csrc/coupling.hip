@@ -236,20 +236,20 @@ static int cp_launch(const CpShape& S, const CpResult& C, const CpOperand& A0, c
     if (add) P.add = *add;
     const unsigned nfr = (S.Nf + CP_FR - 1) / CP_FR, nt = (S.N + CP_TILE - 1) / CP_TILE;
     const dim3 grid(nfr * (unsigned)S.Nt, nt, nt);
-    if (S.dtype == RIME_F32) hipLaunchKernelGGL((coupling_product_kernel<float>), grid, dim3(CP_THREADS), 0, S.st, P);
-    else hipLaunchKernelGGL((coupling_product_kernel<double>), grid, dim3(CP_THREADS), 0, S.st, P);
-    return check_launch();
+    return with_real(S.dtype, [&](auto t) {
+        hipLaunchKernelGGL((coupling_product_kernel<decltype(t)>), grid, dim3(CP_THREADS), 0, S.st, P);
+        return check_launch();
+    });
 }
 
 static int cp_reduce(const CpShape& S, const void* in, void* out, int Tm, int Fm)
 {
     const size_t NN = (size_t)S.N * S.N, total = NN * Tm * Fm;
     const int nb = (int)std::min<size_t>((total + 255) / 256, 1u << 20);
-    if (S.dtype == RIME_F32)
-        hipLaunchKernelGGL((coupling_reduce_kernel<float>), dim3(nb), dim3(256), 0, S.st, in, out, NN, S.Nt, S.Nf, Tm, Fm);
-    else
-        hipLaunchKernelGGL((coupling_reduce_kernel<double>), dim3(nb), dim3(256), 0, S.st, in, out, NN, S.Nt, S.Nf, Tm, Fm);
-    return check_launch();
+    return with_real(S.dtype, [&](auto t) {
+        hipLaunchKernelGGL((coupling_reduce_kernel<decltype(t)>), dim3(nb), dim3(256), 0, S.st, in, out, NN, S.Nt, S.Nf, Tm, Fm);
+        return check_launch();
+    });
 }
 
 static bool cp_shape_ok(int dtype, int N, int Nt, int Nf, int Tm, int Fm)
@@ -291,7 +291,7 @@ extern "C" int rime_coupling_fwd(int dtype, const void* x, const void* dly, cons
     if (addI != 0 && addI != 1) return RIME_EINVAL;
     const size_t need = rime_coupling_workspace(dtype, N, Nt, Nf, Tm, Fm, prod, RIME_COUPLING_FWD);
     if (need && (!workspace || workspace_bytes < need)) return RIME_EWORKSPACE;
-    const CpShape S{dtype, N, Nt, Nf, reinterpret_cast<hipStream_t>(stream)};
+    const CpShape S{dtype, N, Nt, Nf, as_stream(stream)};
     const CpOperand E = cp_dense(x, dly, Tm, Fm, addI, 0), EH = cp_h(E), V = cp_table(data, tab, Nbl, 0);
     const CpResult W = cp_picked_result(out, otab, Nout);
     if (prod == RIME_COUPLING_LEFT) return cp_launch(S, W, E, V);
@@ -311,7 +311,7 @@ extern "C" int rime_coupling_bwd(int dtype, const void* x, const void* dly, cons
     if (addI != 0 && addI != 1) return RIME_EINVAL;
     const size_t need = rime_coupling_workspace(dtype, N, Nt, Nf, Tm, Fm, prod, RIME_COUPLING_BWD);
     if (need && (!workspace || workspace_bytes < need)) return RIME_EWORKSPACE;
-    const CpShape S{dtype, N, Nt, Nf, reinterpret_cast<hipStream_t>(stream)};
+    const CpShape S{dtype, N, Nt, Nf, as_stream(stream)};
     const size_t mat = (size_t)N * N * Nt * Nf * 2 * real_bytes(dtype);
     const bool both = prod == RIME_COUPLING_BOTH, bcast = Tm != Nt || Fm != Nf;
     char* ws = static_cast<char*>(workspace);
@@ -358,7 +358,7 @@ extern "C" int rime_coupling_expand(int dtype, const void* x, const void* dly, i
                                     void* e, void* stream)
 {
     if (!x || !e || !cp_shape_ok(dtype, N, Nt, Nf, Tm, Fm) || (addI != 0 && addI != 1)) return RIME_EINVAL;
-    const CpShape S{dtype, N, Nt, Nf, reinterpret_cast<hipStream_t>(stream)};
+    const CpShape S{dtype, N, Nt, Nf, as_stream(stream)};
     const CpOperand Xd = cp_dense(x, dly, Tm, Fm, 0, 0), add = cp_dense(x, dly, Tm, Fm, addI, 0);
     return cp_launch(S, cp_dense_result(e, nullptr), Xd, Xd, nullptr, nullptr, &add);   // E = [I] + Xd + Xd Xd
 }
@@ -369,7 +369,7 @@ extern "C" int rime_coupling_expand_bwd(int dtype, const void* x, const void* dl
     if (!x || !ge || !gx || !cp_shape_ok(dtype, N, Nt, Nf, Tm, Fm)) return RIME_EINVAL;
     const size_t need = rime_coupling_workspace(dtype, N, Nt, Nf, Tm, Fm, RIME_COUPLING_BOTH, RIME_COUPLING_EXPAND_BWD);
     if (need && (!workspace || workspace_bytes < need)) return RIME_EWORKSPACE;
-    const CpShape S{dtype, N, Nt, Nf, reinterpret_cast<hipStream_t>(stream)};
+    const CpShape S{dtype, N, Nt, Nf, as_stream(stream)};
     const bool bcast = Tm != Nt || Fm != Nf;
     void* buf = bcast ? workspace : gx;
     const CpOperand XH = cp_dense(x, dly, Tm, Fm, 0, 1), gE = cp_dense(ge, nullptr, Nt, Nf, 0, 0);

@@ -63,6 +63,6 @@ extern "C" int rime_eq2top(const double* ra_deg, const double* dec_deg, int N, c
     for (int k = 0; k < 3; ++k) { A.v[k] = vbary_host[k]; v2 += vbary_host[k] * vbary_host[k]; }
     if (!(v2 < 1.0)) return RIME_EINVAL;
     A.bm1 = sqrt(1.0 - v2);
-    hipLaunchKernelGGL(rime::eq2top_kernel, dim3((N + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), A);
+    hipLaunchKernelGGL(rime::eq2top_kernel, dim3((N + 255) / 256), dim3(256), 0, rime::as_stream(stream), A);
     return rime::check_launch();
 }

@@ -334,8 +334,8 @@ extern "C" int rime_fft_apply(int dtype, const void* x, const void* tw, const vo
     if (!x || !y || !tw) return RIME_EINVAL;
     if (!(scale == scale)) return RIME_EINVAL;
     if (nlines == 0) return RIME_OK;                          // nothing to write
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32)
-        return fft_launch<float>(x, tw, win, win_on_store, P, N, nlines, inverse, shift_in, shift_out, scale, epilogue, start, df, y, st);
-    return fft_launch<double>(x, tw, win, win_on_store, P, N, nlines, inverse, shift_in, shift_out, scale, epilogue, start, df, y, st);
+    return with_real(dtype, [&](auto t) {
+        return fft_launch<decltype(t)>(x, tw, win, win_on_store, P, N, nlines, inverse, shift_in, shift_out, scale, epilogue, start,
+                                       df, y, as_stream(stream));
+    });
 }

@@ -215,12 +215,13 @@ extern "C" int rime_filt_apply(int dtype, int wcplx, const void* x, const void* 
     if ((long long)Ntile * (long long)NRT > 0x7fffffffLL) return RIME_EINVAL;
     if (Ntile == 0 || Nlines == 0) return RIME_OK;            // nothing to write
     if (!x || !Wt || !y) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)(Ntile * NRT)), block(256);
-#define FILT_GO(T, CW) hipLaunchKernelGGL((filt_kernel<T, CW>), grid, block, 0, st, (const T*)x, (const T*)Wt, ic, oc, \
-                                          (const T*)base, tiles, NRT, Nfilt, M, K, Nx, Ny, Nlines, (T)s, (T*)y)
-    if (dtype == RIME_F32) { if (wcplx) FILT_GO(float, true); else FILT_GO(float, false); }
-    else { if (wcplx) FILT_GO(double, true); else FILT_GO(double, false); }
-#undef FILT_GO
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        with_bool(wcplx != 0, [&](auto cw) {
+            hipLaunchKernelGGL((filt_kernel<T, cw.value>), dim3((unsigned)(Ntile * NRT)), dim3(256), 0, as_stream(stream),
+                               (const T*)x, (const T*)Wt, ic, oc, (const T*)base, tiles, NRT, Nfilt, M, K, Nx, Ny, Nlines, (T)s,
+                               (T*)y);
+        });
+        return check_launch();
+    });
 }

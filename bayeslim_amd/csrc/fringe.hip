@@ -579,23 +579,24 @@ static int launch_fwd_t(const FringeArgs& base, const int* mp_off, int mode, hip
         A.nbx = (A.bl_cnt + block - 1) / block;
         dim3 grid((unsigned)A.nbx * A.Nt * A.S, (A.Nf + CH - 1) / CH, 1);
         size_t lds = (3 * TP + CH) * sizeof(double) + (size_t)TP * G::ASTRIDE * sizeof(T);
-#define RIME_FWD(M) hipLaunchKernelGGL((fringe_fwd_kernel<T, NPP, CPLX, CH, M>), grid, dim3(block), lds, st, A)
+        auto go = [&](auto m) {
+            hipLaunchKernelGGL((fringe_fwd_kernel<T, NPP, CPLX, CH, m.value>), grid, dim3(block), lds, st, A);
+        };
         if constexpr (sizeof(T) == 4) {
             switch (mode) {
-                case MODE_LIFT: RIME_FWD(MODE_LIFT); break;
-                case MODE_LIFT_NU: RIME_FWD(MODE_LIFT_NU); break;
-                case MODE_ROT_NU: RIME_FWD(MODE_ROT_NU); break;
-                case MODE_DIRECT: RIME_FWD(MODE_DIRECT); break;
-                default: RIME_FWD(MODE_ROT); break;
+                case MODE_LIFT: go(int_c<MODE_LIFT>{}); break;
+                case MODE_LIFT_NU: go(int_c<MODE_LIFT_NU>{}); break;
+                case MODE_ROT_NU: go(int_c<MODE_ROT_NU>{}); break;
+                case MODE_DIRECT: go(int_c<MODE_DIRECT>{}); break;
+                default: go(int_c<MODE_ROT>{}); break;
             }
         } else {
             switch (mode) {          // f64: the shear rotation is an f32 device (hardware rcp)
-                case MODE_LIFT_NU: case MODE_ROT_NU: RIME_FWD(MODE_ROT_NU); break;
-                case MODE_DIRECT: RIME_FWD(MODE_DIRECT); break;
-                default: RIME_FWD(MODE_ROT); break;
+                case MODE_LIFT_NU: case MODE_ROT_NU: go(int_c<MODE_ROT_NU>{}); break;
+                case MODE_DIRECT: go(int_c<MODE_DIRECT>{}); break;
+                default: go(int_c<MODE_ROT>{}); break;
             }
         }
-#undef RIME_FWD
     }
     if (pl.S > 1) {
         int nb = (int)std::min<size_t>((vis_elems + 255) / 256, 4096);
@@ -626,23 +627,24 @@ static int launch_bwd_t(const FringeArgs& base, const int* mp_off, int mode, hip
         size_t lds = (3 * TB + CH) * sizeof(double) + (size_t)TB * G::GSTRIDE * sizeof(T);
         // 4 waves/SIMD (<=128 VGPRs, a few spilled dwords) beat 3 at 136 VGPRs: 66.4 vs 71.9 ms (lab)
         constexpr int WPS = (sizeof(T) == 4 && NPP * (CPLX ? 2 : 1) * CH <= 32) ? 4 : 1;
-#define RIME_BWD(M, W) hipLaunchKernelGGL((fringe_bwd_kernel<T, NPP, CPLX, CH, M, PIX, W>), grid, dim3(pl.block), lds, st, A)
+        auto go = [&](auto m, auto w) {
+            hipLaunchKernelGGL((fringe_bwd_kernel<T, NPP, CPLX, CH, m.value, PIX, w.value>), grid, dim3(pl.block), lds, st, A);
+        };
         if constexpr (sizeof(T) == 4) {
             switch (mode) {
-                case MODE_LIFT: RIME_BWD(MODE_LIFT, WPS); break;
-                case MODE_LIFT_NU: RIME_BWD(MODE_LIFT_NU, WPS); break;
-                case MODE_ROT_NU: RIME_BWD(MODE_ROT_NU, WPS); break;
-                case MODE_DIRECT: RIME_BWD(MODE_DIRECT, 1); break;
-                default: RIME_BWD(MODE_ROT, WPS); break;
+                case MODE_LIFT: go(int_c<MODE_LIFT>{}, int_c<WPS>{}); break;
+                case MODE_LIFT_NU: go(int_c<MODE_LIFT_NU>{}, int_c<WPS>{}); break;
+                case MODE_ROT_NU: go(int_c<MODE_ROT_NU>{}, int_c<WPS>{}); break;
+                case MODE_DIRECT: go(int_c<MODE_DIRECT>{}, int_c<1>{}); break;
+                default: go(int_c<MODE_ROT>{}, int_c<WPS>{}); break;
             }
         } else {
             switch (mode) {
-                case MODE_LIFT_NU: case MODE_ROT_NU: RIME_BWD(MODE_ROT_NU, 1); break;
-                case MODE_DIRECT: RIME_BWD(MODE_DIRECT, 1); break;
-                default: RIME_BWD(MODE_ROT, 1); break;
+                case MODE_LIFT_NU: case MODE_ROT_NU: go(int_c<MODE_ROT_NU>{}, int_c<1>{}); break;
+                case MODE_DIRECT: go(int_c<MODE_DIRECT>{}, int_c<1>{}); break;
+                default: go(int_c<MODE_ROT>{}, int_c<1>{}); break;
             }
         }
-#undef RIME_BWD
         if (A.S > 1) {
             int nb = (int)std::min<size_t>((plane * A.Nt + 255) / 256, 4096);
             hipLaunchKernelGGL((reduce_bwd_kernel<T>), dim3(nb), dim3(256), 0, st,
@@ -741,9 +743,9 @@ static int fringe_common(bool backward, int dtype, const double* blvecs, const d
         // lifting needs |step| comfortably below half a turn: tan(pi*step) stays O(1)
         if (max_blen > 0 && max_blen * fabs(A.dfreq_c) < 0.3) mode = nu ? MODE_LIFT_NU : MODE_LIFT;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32) return dispatch<float>(backward, A, mp_off, Npp, cplx, mode, st, ws_bytes);
-    return dispatch<double>(backward, A, mp_off, Npp, cplx, mode, st, ws_bytes);
+    return with_real(dtype, [&](auto t) {
+        return dispatch<decltype(t)>(backward, A, mp_off, Npp, cplx, mode, as_stream(stream), ws_bytes);
+    });
 }
 
 extern "C" int rime_fringe_sum_fwd(int dtype, const double* blvecs, const double* sdir,
@@ -780,14 +782,11 @@ extern "C" int rime_gen_fringe(int dtype, const double* blvecs, const double* sd
 {
     if (!blvecs || !sdir || !freqs || !out) return RIME_EINVAL;
     if (Nbl <= 0 || Nf <= 0 || P <= 0 || sdir_stride < P || (sign != 1 && sign != -1)) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     dim3 grid((unsigned)((P + 255) / 256) * Nbl), block(256);
-    if (dtype == RIME_F32)
-        hipLaunchKernelGGL((gen_fringe_kernel<float>), grid, block, 0, st, blvecs, sdir, freqs, Nbl, Nf, P,
-                           sdir_stride, (double)sign, reinterpret_cast<float*>(out));
-    else if (dtype == RIME_F64)
-        hipLaunchKernelGGL((gen_fringe_kernel<double>), grid, block, 0, st, blvecs, sdir, freqs, Nbl, Nf, P,
-                           sdir_stride, (double)sign, reinterpret_cast<double*>(out));
-    else return RIME_EINVAL;
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((gen_fringe_kernel<T>), grid, block, 0, as_stream(stream), blvecs, sdir, freqs, Nbl, Nf, P,
+                           sdir_stride, (double)sign, reinterpret_cast<T*>(out));
+        return check_launch();
+    });
 }

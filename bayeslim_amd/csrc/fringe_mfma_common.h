@@ -152,14 +152,6 @@ inline dim3 fill_backward(Args& A, const float* gscale, float* gpsky, const void
     return dim3((unsigned)A.Nt * A.S * A.Nf, 1, 1);
 }
 
-// f(std::true_type) or f(std::false_type): a run-time flag as a template argument of the kernel f launches
-template <class F>
-inline void with_bool(bool flag, F&& f)
-{
-    if (flag) f(std::true_type{});
-    else f(std::false_type{});
-}
-
 // One real plane of psky: the SIGNED = true instantiation serves the rows that hold a negative value, the SIGNED = false one
 // (no sign masks) the others; each returns at once from the blocks of the other's rows.  Without row minima every row is signed.
 template <class Args>

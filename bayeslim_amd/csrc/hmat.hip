@@ -287,7 +287,8 @@ extern "C" int rime_hmat_apply(int dtype, const void* tiles, int ntiles, const l
     for (int s = 0; s < nstages; ++s)
         if (stage_first[s + 1] < stage_first[s]) return RIME_EINVAL;
     if (scratch_rows > 0 && (!workspace || workspace_bytes < rime_hmat_workspace(dtype, scratch_rows, nrhs))) return RIME_EWORKSPACE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == RIME_F32 ? hm_apply<float>(tiles, ranges, tile_ids, stage_first, nstages, x, y, workspace, nrhs, scalar, accumulate, st)
-                             : hm_apply<double>(tiles, ranges, tile_ids, stage_first, nstages, x, y, workspace, nrhs, scalar, accumulate, st);
+    return with_real(dtype, [&](auto t) {
+        return hm_apply<decltype(t)>(tiles, ranges, tile_ids, stage_first, nstages, x, y, workspace, nrhs, scalar, accumulate,
+                                     as_stream(stream));
+    });
 }

@@ -152,7 +152,7 @@ extern "C" int rime_hmc_step(int dtype, long long N, void* q, void* p, const voi
     // a flag that rounds to zero in the working type would skip its pass: refuse it
     if (dtype == RIME_F32 && ((kick != 0.0 && (float)kick == 0.0f) || (drift != 0.0 && (float)drift == 0.0f))) return RIME_EINVAL;
     if (kick == 0.0 && drift == 0.0 && energy == nullptr) return RIME_OK;               // nothing to do
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == RIME_F32 ? hmc_step<float>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, st, dtype)
-                             : hmc_step<double>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, st, dtype);
+    return with_real(dtype, [&](auto t) {
+        return hmc_step<decltype(t)>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, as_stream(stream), dtype);
+    });
 }

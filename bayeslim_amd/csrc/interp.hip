@@ -215,16 +215,17 @@ static int gather_launch(const void* m, const int* inds, const void* wgts, int R
         dim3 grid((P + 255) / 256, (Rc + RT - 1) / RT), block(256);
         const T* m_ = reinterpret_cast<const T*>(m) + (size_t)r0 * Npb * NC;
         T* o_ = reinterpret_cast<T*>(out) + (size_t)r0 * out_stride * NC;
-#define RIME_G(N) hipLaunchKernelGGL((interp_gather_kernel<T, NC, N>), grid, block, 0, st, m_, inds, w_, Rc, Npb, P, Nnn, o_, out_stride)
+        auto go = [&](auto n) {
+            hipLaunchKernelGGL((interp_gather_kernel<T, NC, n.value>), grid, block, 0, st, m_, inds, w_, Rc, Npb, P, Nnn, o_, out_stride);
+        };
         switch (Nnn) {
-            case 1: RIME_G(1); break;
-            case 4: RIME_G(4); break;
-            case 6: RIME_G(6); break;
-            case 9: RIME_G(9); break;
-            case 16: RIME_G(16); break;
-            default: RIME_G(0); break;
+            case 1: go(int_c<1>{}); break;
+            case 4: go(int_c<4>{}); break;
+            case 6: go(int_c<6>{}); break;
+            case 9: go(int_c<9>{}); break;
+            case 16: go(int_c<16>{}); break;
+            default: go(int_c<0>{}); break;
         }
-#undef RIME_G
     }
     return check_launch();
 }
@@ -239,14 +240,11 @@ extern "C" int rime_interp_gather_fwd(int dtype, int is_complex, const void* m, 
 {
     if (!m || !inds || !wgts || !out) return RIME_EINVAL;
     if (R <= 0 || Npb <= 0 || P <= 0 || Nnn <= 0 || out_stride < P) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32)
-        return is_complex ? gather_launch<float, 2>(m, inds, wgts, R, Npb, P, Nnn, out, out_stride, st)
-                          : gather_launch<float, 1>(m, inds, wgts, R, Npb, P, Nnn, out, out_stride, st);
-    if (dtype == RIME_F64)
-        return is_complex ? gather_launch<double, 2>(m, inds, wgts, R, Npb, P, Nnn, out, out_stride, st)
-                          : gather_launch<double, 1>(m, inds, wgts, R, Npb, P, Nnn, out, out_stride, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        return is_complex ? gather_launch<T, 2>(m, inds, wgts, R, Npb, P, Nnn, out, out_stride, as_stream(stream))
+                          : gather_launch<T, 1>(m, inds, wgts, R, Npb, P, Nnn, out, out_stride, as_stream(stream));
+    });
 }
 
 template <typename T>
@@ -267,11 +265,10 @@ extern "C" int rime_interp_scatter_bwd(int dtype, int is_complex, const void* go
 {
     if (!goutT || !csr_ptr || !csr_src || !wgts || !gmT) return RIME_EINVAL;
     if (R <= 0 || Npb <= 0 || P <= 0 || Nnn <= 0) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int RN = R * (is_complex ? 2 : 1);
-    if (dtype == RIME_F32) return scatter_launch<float>(goutT, csr_ptr, csr_src, wgts, RN, Npb, Nnn, gmT, st);
-    if (dtype == RIME_F64) return scatter_launch<double>(goutT, csr_ptr, csr_src, wgts, RN, Npb, Nnn, gmT, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) {
+        return scatter_launch<decltype(t)>(goutT, csr_ptr, csr_src, wgts, RN, Npb, Nnn, gmT, as_stream(stream));
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -327,24 +324,24 @@ extern "C" int rime_interp_scatter_rows_bwd(int dtype, int is_complex, const voi
 {
     // csr_src may be NULL when the index is EMPTY (every weight 0: csr_ptr is all zeros and no entry is read): the result is 0
     if (!gout || !csr_ptr || !wgts || !gm || R <= 0 || Npb <= 0 || gout_stride <= 0) return RIME_EINVAL;
-    if (!real_dtype_ok(dtype)) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     constexpr int RB = 8;
-    // rows beyond one grid's reach (65535 x RB) go to further launches on row-offset pointers (was RIME_EUNSUPPORTED)
-    const size_t esz = real_bytes(dtype) * (is_complex ? 2 : 1);
-    const int chunk = 65535 * RB;
-    for (int r0 = 0; r0 < R; r0 += chunk) {
-        const int Rc = R - r0 < chunk ? R - r0 : chunk;
-        dim3 grid((Npb + 255) / 256, (Rc + RB - 1) / RB);
-        const char* gi = (const char*)gout + (size_t)r0 * (size_t)gout_stride * esz;
-        char* go = (char*)gm + (size_t)r0 * (size_t)Npb * esz;
-#define RIME_SR(T, EW) hipLaunchKernelGGL((rime::scatter_rows_kernel<T, EW, RB>), grid, dim3(256), 0, st, (const T*)gi, gout_stride, \
-                                          csr_ptr, csr_src, (const T*)wgts, Rc, Npb, (T*)go)
-        if (dtype == RIME_F32) { if (is_complex) RIME_SR(float, 2); else RIME_SR(float, 1); }
-        else { if (is_complex) RIME_SR(double, 2); else RIME_SR(double, 1); }
-#undef RIME_SR
-    }
-    return rime::check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        with_bool(is_complex != 0, [&](auto c) {
+            constexpr int EW = c.value ? 2 : 1;
+            // rows beyond one grid's reach (65535 x RB) go to further launches on row-offset pointers (was
+            // RIME_EUNSUPPORTED)
+            const int chunk = 65535 * RB;
+            for (int r0 = 0; r0 < R; r0 += chunk) {
+                const int Rc = R - r0 < chunk ? R - r0 : chunk;
+                dim3 grid((Npb + 255) / 256, (Rc + RB - 1) / RB);
+                hipLaunchKernelGGL((scatter_rows_kernel<T, EW, RB>), grid, dim3(256), 0, as_stream(stream),
+                                   (const T*)gout + (size_t)r0 * (size_t)gout_stride * EW, gout_stride, csr_ptr, csr_src,
+                                   (const T*)wgts, Rc, Npb, (T*)gm + (size_t)r0 * (size_t)Npb * EW);
+            }
+        });
+        return check_launch();
+    });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -686,15 +683,16 @@ static int beam_sky_fwd_launch(const void* bmap, const void* sky, const int* ind
     const T* b_ = reinterpret_cast<const T*>(bmap); const T* s_ = reinterpret_cast<const T*>(sky);
     const T* w_ = reinterpret_cast<const T*>(wgts); T* o_ = reinterpret_cast<T*>(out);
     const int remap = xcd_remap_enabled(XCD_FWD);
-#define RIME_BS(N) hipLaunchKernelGGL((beam_sky_fwd_kernel<T, N>), grid, block, 0, st, b_, s_, inds, w_, cut, R, Npb, Npix, Q, Nnn, o_, remap)
+    auto go = [&](auto n) {
+        hipLaunchKernelGGL((beam_sky_fwd_kernel<T, n.value>), grid, block, 0, st, b_, s_, inds, w_, cut, R, Npb, Npix, Q, Nnn, o_, remap);
+    };
     switch (Nnn) {
-        case 1: RIME_BS(1); break;
-        case 4: RIME_BS(4); break;
-        case 9: RIME_BS(9); break;
-        case 16: RIME_BS(16); break;
-        default: RIME_BS(0); break;
+        case 1: go(int_c<1>{}); break;
+        case 4: go(int_c<4>{}); break;
+        case 9: go(int_c<9>{}); break;
+        case 16: go(int_c<16>{}); break;
+        default: go(int_c<0>{}); break;
     }
-#undef RIME_BS
     return check_launch();
 }
 
@@ -705,10 +703,9 @@ extern "C" int rime_beam_sky_fwd(int dtype, const void* bmap, const void* sky, c
 {
     if (!bmap || !sky || !inds || !wgts || !cut || !psky) return RIME_EINVAL;
     if (R <= 0 || Npb <= 0 || Npix <= 0 || Q <= 0 || Nnn <= 0) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32) return beam_sky_fwd_launch<float>(bmap, sky, inds, wgts, cut, R, Npb, Npix, Q, Nnn, psky, st);
-    if (dtype == RIME_F64) return beam_sky_fwd_launch<double>(bmap, sky, inds, wgts, cut, R, Npb, Npix, Q, Nnn, psky, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) {
+        return beam_sky_fwd_launch<decltype(t)>(bmap, sky, inds, wgts, cut, R, Npb, Npix, Q, Nnn, psky, as_stream(stream));
+    });
 }
 
 extern "C" size_t rime_beam_sky_bwd_workspace(int dtype, int R, int Npix, int Nt)
@@ -725,7 +722,7 @@ extern "C" int rime_beam_sky_bwd(int dtype, const void* gpsky, const void* bmapT
 {
     if (!gpsky || !bmapT || !sky || !inds || !wgts || !cut || !pos || !T1 || !gsky) return RIME_EINVAL;
     if (R <= 0 || Npb <= 0 || Npix <= 0 || Nt <= 0 || Ps <= 0 || Nnn <= 0) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = as_stream(stream);
     const int Q = Nt * Ps;
     const int remap = xcd_remap_enabled(XCD_SKYGRAD), remap_b = xcd_remap_enabled(XCD_BWD);
     // time splits of the sky gradient (their partial planes live in the workspace; without one the steps are walked in one go)
@@ -738,24 +735,24 @@ extern "C" int rime_beam_sky_bwd(int dtype, const void* gpsky, const void* bmapT
     S = (Nt + Tc - 1) / Tc;
     void* sg_out = S > 1 ? workspace : gsky;
     dim3 g1((Q + 63) / 64, (R + 63) / 64), g2((Npix + 63) / 64, (R + 63) / 64, S);
-#define RIME_SG(TT, N) hipLaunchKernelGGL((sky_grad_kernel<TT, N>), g2, dim3(256), 0, st, (const TT*)gpsky, (const TT*)bmapT, \
-        inds, (const TT*)wgts, pos, R, Npix, Nt, Ps, Nnn, (TT*)sg_out, remap, Tc)
-#define RIME_SG_ALL(TT) switch (Nnn) { case 1: RIME_SG(TT, 1); break; case 4: RIME_SG(TT, 4); break; \
-        case 9: RIME_SG(TT, 9); break; case 16: RIME_SG(TT, 16); break; default: RIME_SG(TT, 0); break; }
     const size_t len = (size_t)R * Npix;
     const int nb = (int)std::min<size_t>((len + 255) / 256, 4096);
-    if (dtype == RIME_F32) {
-        hipLaunchKernelGGL((beam_sky_bwd_kernel<float>), g1, dim3(256), 0, st, (const float*)gpsky, (const float*)sky, cut,
-                           R, Npix, Q, (float*)T1, remap_b);
-        RIME_SG_ALL(float)
-        if (S > 1) hipLaunchKernelGGL((plane_sum_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)workspace, (float*)gsky, len, S);
-    } else if (dtype == RIME_F64) {
-        hipLaunchKernelGGL((beam_sky_bwd_kernel<double>), g1, dim3(256), 0, st, (const double*)gpsky, (const double*)sky, cut,
-                           R, Npix, Q, (double*)T1, remap_b);
-        RIME_SG_ALL(double)
-        if (S > 1) hipLaunchKernelGGL((plane_sum_kernel<double>), dim3(nb), dim3(256), 0, st, (const double*)workspace, (double*)gsky, len, S);
-    } else return RIME_EINVAL;
-#undef RIME_SG_ALL
-#undef RIME_SG
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((beam_sky_bwd_kernel<T>), g1, dim3(256), 0, st, (const T*)gpsky, (const T*)sky, cut, R, Npix, Q, (T*)T1,
+                           remap_b);
+        auto go = [&](auto n) {
+            hipLaunchKernelGGL((sky_grad_kernel<T, n.value>), g2, dim3(256), 0, st, (const T*)gpsky, (const T*)bmapT, inds,
+                               (const T*)wgts, pos, R, Npix, Nt, Ps, Nnn, (T*)sg_out, remap, Tc);
+        };
+        switch (Nnn) {
+            case 1: go(int_c<1>{}); break;
+            case 4: go(int_c<4>{}); break;
+            case 9: go(int_c<9>{}); break;
+            case 16: go(int_c<16>{}); break;
+            default: go(int_c<0>{}); break;
+        }
+        if (S > 1) hipLaunchKernelGGL((plane_sum_kernel<T>), dim3(nb), dim3(256), 0, st, (const T*)workspace, (T*)gsky, len, S);
+        return check_launch();
+    });
 }

@@ -166,16 +166,12 @@ extern "C" int rime_stokes2coh_fwd(int dtype, const void* stokesI, const void* f
     if (!stokesI || !frac || !coh || R <= 0 || P <= 0 || fs_k < 0 || fs_r < 0 || fs_p < 0) return RIME_EINVAL;
     const long long N = R * P;
     if ((N + 255) / 256 > 0x7fffffffLL) return RIME_EUNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)((N + 255) / 256));
-    if (dtype == RIME_F32)
-        hipLaunchKernelGGL((stokes2coh_fwd_kernel<float>), grid, dim3(256), 0, st, (const float*)stokesI, (const float*)frac,
-                           fs_k, fs_r, fs_p, R, P, (float*)coh);
-    else if (dtype == RIME_F64)
-        hipLaunchKernelGGL((stokes2coh_fwd_kernel<double>), grid, dim3(256), 0, st, (const double*)stokesI, (const double*)frac,
-                           fs_k, fs_r, fs_p, R, P, (double*)coh);
-    else return RIME_EINVAL;
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((stokes2coh_fwd_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, as_stream(stream),
+                           (const T*)stokesI, (const T*)frac, fs_k, fs_r, fs_p, R, P, (T*)coh);
+        return check_launch();
+    });
 }
 
 extern "C" int rime_stokes2coh_bwd(int dtype, const void* gcoh, const void* frac, long long fs_k, long long fs_r,
@@ -184,32 +180,28 @@ extern "C" int rime_stokes2coh_bwd(int dtype, const void* gcoh, const void* frac
     if (!gcoh || !frac || !gI || R <= 0 || P <= 0 || fs_k < 0 || fs_r < 0 || fs_p < 0) return RIME_EINVAL;
     const long long N = R * P;
     if ((N + 255) / 256 > 0x7fffffffLL) return RIME_EUNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)((N + 255) / 256));
-    if (dtype == RIME_F32)
-        hipLaunchKernelGGL((stokes2coh_bwd_kernel<float>), grid, dim3(256), 0, st, (const float*)gcoh, (const float*)frac,
-                           fs_k, fs_r, fs_p, R, P, (float*)gI);
-    else if (dtype == RIME_F64)
-        hipLaunchKernelGGL((stokes2coh_bwd_kernel<double>), grid, dim3(256), 0, st, (const double*)gcoh, (const double*)frac,
-                           fs_k, fs_r, fs_p, R, P, (double*)gI);
-    else return RIME_EINVAL;
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((stokes2coh_bwd_kernel<T>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0, as_stream(stream),
+                           (const T*)gcoh, (const T*)frac, fs_k, fs_r, fs_p, R, P, (T*)gI);
+        return check_launch();
+    });
 }
 
+// The kernels' REALB is the opposite of the ABI's beam_complex: the flag is inverted here, once.
 extern "C" int rime_jones_apply_fwd(int dtype, int beam_complex, const void* J1, const void* J2, const void* S,
                                     long long N, long long Ns, void* out, void* stream)
 {
     if (!J1 || !J2 || !S || !out || N <= 0 || Ns <= 0 || N % Ns != 0) return RIME_EINVAL;
     if ((N + 255) / 256 > 0x7fffffffLL) return RIME_EUNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)((N + 255) / 256));
-#define RIME_J(T, RB) hipLaunchKernelGGL((jones_apply_fwd_kernel<T, RB>), grid, dim3(256), 0, st, (const T*)J1, (const T*)J2, \
-                                         (const T*)S, (size_t)N, (size_t)Ns, (T*)out)
-    if (dtype == RIME_F32) { if (beam_complex) RIME_J(float, false); else RIME_J(float, true); }
-    else if (dtype == RIME_F64) { if (beam_complex) RIME_J(double, false); else RIME_J(double, true); }
-    else return RIME_EINVAL;
-#undef RIME_J
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        with_bool(beam_complex != 0, [&](auto cplx) {
+            hipLaunchKernelGGL((jones_apply_fwd_kernel<T, !cplx.value>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0,
+                               as_stream(stream), (const T*)J1, (const T*)J2, (const T*)S, (size_t)N, (size_t)Ns, (T*)out);
+        });
+        return check_launch();
+    });
 }
 
 extern "C" int rime_jones_apply_bwd(int dtype, int beam_complex, const void* J1, const void* J2, const void* S,
@@ -217,13 +209,13 @@ extern "C" int rime_jones_apply_bwd(int dtype, int beam_complex, const void* J1,
 {
     if (!J1 || !J2 || !S || !G || !gJ1 || !gJ2 || !gS || N <= 0 || Ns <= 0 || N % Ns != 0) return RIME_EINVAL;
     if ((N + 255) / 256 > 0x7fffffffLL) return RIME_EUNSUPPORTED;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)((N + 255) / 256));
-#define RIME_J(T, RB) hipLaunchKernelGGL((jones_apply_bwd_kernel<T, RB>), grid, dim3(256), 0, st, (const T*)J1, (const T*)J2, \
-                                         (const T*)S, (const T*)G, (size_t)N, (size_t)Ns, (T*)gJ1, (T*)gJ2, (T*)gS)
-    if (dtype == RIME_F32) { if (beam_complex) RIME_J(float, false); else RIME_J(float, true); }
-    else if (dtype == RIME_F64) { if (beam_complex) RIME_J(double, false); else RIME_J(double, true); }
-    else return RIME_EINVAL;
-#undef RIME_J
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        with_bool(beam_complex != 0, [&](auto cplx) {
+            hipLaunchKernelGGL((jones_apply_bwd_kernel<T, !cplx.value>), dim3((unsigned)((N + 255) / 256)), dim3(256), 0,
+                               as_stream(stream), (const T*)J1, (const T*)J2, (const T*)S, (const T*)G, (size_t)N, (size_t)Ns,
+                               (T*)gJ1, (T*)gJ2, (T*)gS);
+        });
+        return check_launch();
+    });
 }

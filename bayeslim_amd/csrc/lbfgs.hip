@@ -198,9 +198,9 @@ extern "C" int rime_lbfgs_dots(int dtype, const void* const* s_rows, const void*
     if (!workspace || workspace_bytes < rime_lbfgs_workspace(m, N)) return RIME_EWORKSPACE;
     const long long nchunks = lb_chunks(N, dtype);
     const int nb = (int)std::min<long long>(nchunks, LB_MAXBLOCKS);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == RIME_F32 ? lb_dots<float>(s_rows, y_rows, m, N, v, d, k, out, (double*)workspace, nb, nchunks, st)
-                             : lb_dots<double>(s_rows, y_rows, m, N, v, d, k, out, (double*)workspace, nb, nchunks, st);
+    return with_real(dtype, [&](auto t) {
+        return lb_dots<decltype(t)>(s_rows, y_rows, m, N, v, d, k, out, (double*)workspace, nb, nchunks, as_stream(stream));
+    });
 }
 
 extern "C" int rime_lbfgs_combine(int dtype, const void* const* s_rows, const void* const* y_rows, int m, long long N, const void* v,
@@ -209,12 +209,10 @@ extern "C" int rime_lbfgs_combine(int dtype, const void* const* s_rows, const vo
     if (lb_bad(dtype, s_rows, y_rows, m, N) || !v || !a || !b || !r) return RIME_EINVAL;
     const long long nchunks = lb_chunks(N, dtype);
     if (nchunks > 0x7fffffffLL) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32)
-        hipLaunchKernelGGL((lbfgs_combine_kernel<float>), dim3((unsigned)nchunks), dim3(LB_THREADS), 0, st, (const float* const*)s_rows,
-                           (const float* const*)y_rows, (const float*)v, (const float*)d, a, b, gamma, m, N, (float*)r);
-    else
-        hipLaunchKernelGGL((lbfgs_combine_kernel<double>), dim3((unsigned)nchunks), dim3(LB_THREADS), 0, st, (const double* const*)s_rows,
-                           (const double* const*)y_rows, (const double*)v, (const double*)d, a, b, gamma, m, N, (double*)r);
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((lbfgs_combine_kernel<T>), dim3((unsigned)nchunks), dim3(LB_THREADS), 0, as_stream(stream),
+                           (const T* const*)s_rows, (const T* const*)y_rows, (const T*)v, (const T*)d, a, b, gamma, m, N, (T*)r);
+        return check_launch();
+    });
 }

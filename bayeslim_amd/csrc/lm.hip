@@ -332,6 +332,6 @@ extern "C" int rime_lm_apply(int dtype, int xcplx, int mcplx, int out_real, cons
     LmArgs a;
     a.x = x; a.M = M; a.pre = pre; a.post = post; a.idx = idx; a.y = y;
     a.O = O; a.I = I; a.m_rs = m_rs; a.m_ks = m_ks; a.K = K; a.K_in = K_in; a.R = R;
-    a.st = reinterpret_cast<hipStream_t>(stream);
-    return dtype == RIME_F32 ? lm_dispatch<float>(a, xcplx, mcplx, out_real) : lm_dispatch<double>(a, xcplx, mcplx, out_real);
+    a.st = as_stream(stream);
+    return with_real(dtype, [&](auto t) { return lm_dispatch<decltype(t)>(a, xcplx, mcplx, out_real); });
 }

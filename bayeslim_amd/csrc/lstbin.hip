@@ -284,17 +284,13 @@ extern "C" int rime_vis_timeavg_fwd(int dtype, const void* data, const void* wgt
     A.bin_ptr = bin_ptr; A.members = members; A.avg = avg; A.sum_w = sum_w; A.avg_cov = avg_cov;
     A.avg_flag = (unsigned char*)avg_flag; A.by_member = tau_by_member;
     A.Npp = Npp; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nbin = Nbin; A.Nmem = Nmem;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool vec = ta_vec(dtype, Nf, {data, wgts, cov, avg, sum_w, avg_cov});
-    const dim3 grid((unsigned)nb), block(TA_THREADS);
-    if (dtype == RIME_F32) {
-        if (vec) hipLaunchKernelGGL((vis_timeavg_fwd_kernel<float, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((vis_timeavg_fwd_kernel<float, false>), grid, block, 0, st, A);
-    } else {
-        if (vec) hipLaunchKernelGGL((vis_timeavg_fwd_kernel<double, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((vis_timeavg_fwd_kernel<double, false>), grid, block, 0, st, A);
-    }
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        with_bool(vec, [&](auto v) {
+            hipLaunchKernelGGL((vis_timeavg_fwd_kernel<decltype(t), v.value>), dim3(nb), dim3(TA_THREADS), 0, as_stream(stream), A);
+        });
+        return check_launch();
+    });
 }
 
 extern "C" int rime_vis_timeavg_bwd(int dtype, const void* gavg, const void* wgts, const void* sum_w, const double* tau,
@@ -317,15 +313,11 @@ extern "C" int rime_vis_timeavg_bwd(int dtype, const void* gavg, const void* wgt
     A.gavg = gavg; A.wgts = wgts; A.sum_w = const_cast<void*>(sum_w); A.tau = tau; A.freqs = freqs;
     A.t_ptr = t_ptr; A.t_pos = t_pos; A.pos_bin = pos_bin; A.gdata = gdata; A.by_member = tau_by_member;
     A.Npp = Npp; A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nbin = Nbin; A.Nmem = Nmem;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool vec = ta_vec(dtype, Nf, {gavg, wgts, sum_w, gdata});
-    const dim3 grid((unsigned)nb), block(TA_THREADS);
-    if (dtype == RIME_F32) {
-        if (vec) hipLaunchKernelGGL((vis_timeavg_bwd_kernel<float, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((vis_timeavg_bwd_kernel<float, false>), grid, block, 0, st, A);
-    } else {
-        if (vec) hipLaunchKernelGGL((vis_timeavg_bwd_kernel<double, true>), grid, block, 0, st, A);
-        else hipLaunchKernelGGL((vis_timeavg_bwd_kernel<double, false>), grid, block, 0, st, A);
-    }
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        with_bool(vec, [&](auto v) {
+            hipLaunchKernelGGL((vis_timeavg_bwd_kernel<decltype(t), v.value>), dim3(nb), dim3(TA_THREADS), 0, as_stream(stream), A);
+        });
+        return check_launch();
+    });
 }

@@ -200,9 +200,10 @@ static int rc_row_launch(int dtype, const RcArgs& A, hipStream_t st)
 {
     const size_t ntile = ((size_t)A.Nt * A.Nf + RC_COLS - 1) / RC_COLS;
     const int nb = rc_blocks((size_t)(BWD ? A.Nin : A.Nout) * ntile, RC_WAVES);
-    if (dtype == RIME_F32) hipLaunchKernelGGL((redcoupling_row_kernel<float, BWD>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
-    else hipLaunchKernelGGL((redcoupling_row_kernel<double, BWD>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        hipLaunchKernelGGL((redcoupling_row_kernel<decltype(t), BWD>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
+        return check_launch();
+    });
 }
 
 } // namespace rime
@@ -223,7 +224,7 @@ extern "C" int rime_redcoupling_fwd(int dtype, const void* x, const void* dly, c
     RcArgs A{};
     A.x = x; A.dly = dly; A.data = data; A.ent = ent; A.off = roff; A.out = out;
     A.Nout = Nout; A.Nin = Nin; A.Nterms = Nterms; A.Nent = Nent; A.Nt = Nt; A.Nf = Nf; A.Tm = Tm; A.Fm = Fm;
-    return rc_row_launch<0>(dtype, A, reinterpret_cast<hipStream_t>(stream));
+    return rc_row_launch<0>(dtype, A, as_stream(stream));
 }
 
 extern "C" int rime_redcoupling_bwd_data(int dtype, const void* x, const void* dly, const void* gout, const int* ent,
@@ -235,7 +236,7 @@ extern "C" int rime_redcoupling_bwd_data(int dtype, const void* x, const void* d
     RcArgs A{};
     A.x = x; A.dly = dly; A.gout = gout; A.ent = ent; A.off = coff; A.mem = cmem; A.out = gdata;
     A.Nout = Nout; A.Nin = Nin; A.Nterms = Nterms; A.Nent = Nent; A.Nt = Nt; A.Nf = Nf; A.Tm = Tm; A.Fm = Fm;
-    return rc_row_launch<1>(dtype, A, reinterpret_cast<hipStream_t>(stream));
+    return rc_row_launch<1>(dtype, A, as_stream(stream));
 }
 
 extern "C" int rime_redcoupling_bwd_coupling(int dtype, const void* x, const void* dly, const void* data, const void* gout,
@@ -250,7 +251,7 @@ extern "C" int rime_redcoupling_bwd_coupling(int dtype, const void* x, const voi
     if ((Nmem > 0) != (Nseg > 0) || (Nseg > 0 && (!tmem || !segterm || !segstart))) return RIME_EINVAL;
     const size_t need = rime_redcoupling_workspace(dtype, Nseg, Nt, Nf);
     if (need && (!workspace || workspace_bytes < need)) return RIME_EWORKSPACE;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = as_stream(stream);
     RcArgs A{};
     A.x = x; A.dly = dly; A.data = data; A.gout = gout; A.ent = ent; A.off = toff; A.mem = tmem;
     A.segterm = segterm; A.segstart = segstart; A.tsoff = tsoff; A.out = gx; A.ws = workspace;
@@ -259,14 +260,16 @@ extern "C" int rime_redcoupling_bwd_coupling(int dtype, const void* x, const voi
     if (Nseg > 0) {
         const size_t ntile = ((size_t)Nt * Nf + RC_COLS - 1) / RC_COLS;
         const int nb = rc_blocks((size_t)Nseg * ntile, RC_WAVES);
-        if (dtype == RIME_F32) hipLaunchKernelGGL((redcoupling_seg_kernel<float>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
-        else hipLaunchKernelGGL((redcoupling_seg_kernel<double>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
-        const int rc = check_launch();
+        const int rc = with_real(dtype, [&](auto t) {
+            hipLaunchKernelGGL((redcoupling_seg_kernel<decltype(t)>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
+            return check_launch();
+        });
         if (rc != RIME_OK) return rc;
     }
     const int nft = Fm == 1 ? 1 : (Nf + RC_COLS - 1) / RC_COLS;
     const int nb = rc_blocks((size_t)Nterms * Tm * nft, 1);
-    if (dtype == RIME_F32) hipLaunchKernelGGL((redcoupling_combine_kernel<float>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
-    else hipLaunchKernelGGL((redcoupling_combine_kernel<double>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        hipLaunchKernelGGL((redcoupling_combine_kernel<decltype(t)>), dim3(nb), dim3(RC_WAVES * RC_COLS), 0, st, A);
+        return check_launch();
+    });
 }

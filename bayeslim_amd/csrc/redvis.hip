@@ -145,10 +145,7 @@ extern "C" int rime_redvis_fwd(int dtype, int NP, const void* vis, const void* m
     A.vis = vis; A.model = model; A.red = red; A.tmap = tmap; A.out = out;
     A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nred = Nred; A.Ntm = Ntm;
     A.mst_p = mst_p; A.mst_r = mst_r; A.mst_t = mst_t; A.mst_f = mst_f; A.sign = sign;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32) return redvis_fwd_launch<float>(A, NP, st);
-    if (dtype == RIME_F64) return redvis_fwd_launch<double>(A, NP, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) { return redvis_fwd_launch<decltype(t)>(A, NP, as_stream(stream)); });
 }
 
 extern "C" int rime_redvis_bwd(int dtype, int NP, const void* gout, const int* goff, const int* gmem, const int* toff,
@@ -160,8 +157,5 @@ extern "C" int rime_redvis_bwd(int dtype, int NP, const void* gout, const int* g
     RedVisArgs A{};
     A.gout = gout; A.goff = goff; A.gmem = gmem; A.toff = toff; A.tmem = tmem; A.gmodel = gmodel;
     A.Nbl = Nbl; A.Nt = Nt; A.Nf = Nf; A.Nred = Nred; A.Ntm = Ntm; A.sign = sign;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32) return redvis_bwd_launch<float>(A, NP, st);
-    if (dtype == RIME_F64) return redvis_bwd_launch<double>(A, NP, st);
-    return RIME_EINVAL;
+    return with_real(dtype, [&](auto t) { return redvis_bwd_launch<decltype(t)>(A, NP, as_stream(stream)); });
 }

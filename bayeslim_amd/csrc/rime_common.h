@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include "../../include/rime_hip.h"
 
 namespace rime {
@@ -23,6 +24,30 @@ inline int check_launch()
 // The real working types of the C ABI: whether dtype names one, and its size in bytes (8 for anything but RIME_F32).
 inline bool real_dtype_ok(int dtype) { return dtype == RIME_F32 || dtype == RIME_F64; }
 inline int real_bytes(int dtype) { return dtype == RIME_F32 ? 4 : 8; }
+
+// ---- host: from the run-time arguments of an entry point to the template arguments of its kernels ----
+inline hipStream_t as_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+// f(float{}) for RIME_F32, f(double{}) for RIME_F64, and what f returns; RIME_EINVAL for any other dtype, f not called.
+// Inside f: `using T = decltype(t);`
+template <class F>
+inline int with_real(int dtype, F&& f)
+{
+    if (dtype == RIME_F32) return f(float{});
+    if (dtype == RIME_F64) return f(double{});
+    return RIME_EINVAL;
+}
+
+// f(std::true_type) or f(std::false_type): a run-time flag as a template argument of the kernel f launches
+template <class F>
+inline void with_bool(bool flag, F&& f)
+{
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// an int as an argument of a generic lambda: the cases of a switch over a run-time count call go(int_c<4>{})
+template <int N> using int_c = std::integral_constant<int, N>;
 
 // Reads of matrix-core results by the vector ALU.  hipcc (ROCm 7.2) places the wait states of the ISA hazard table
 // between an MFMA and the first VALU read of its destination.  Observed on gfx950 (round 2, complex-psky backward of

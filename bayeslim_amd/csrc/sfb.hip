@@ -145,14 +145,15 @@ static int sfb_launch(int dtype, int cplx, const void* X, const void* g, const i
     if ((long long)Ntile * (long long)B > 0x7fffffffLL) return RIME_EINVAL;
     if (Ntile == 0 || B == 0) return RIME_OK;                 // nothing to write
     if (!X || !g || !res) return RIME_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)(Ntile * B)), block(256);
-#define SFB_GO(T, V) hipLaunchKernelGGL((sfb_kernel<T, V, BWD>), grid, block, 0, st, (const T*)X, (const T*)g, blocks, cols, \
-                                        tiles, Nblk, Ntile, Nlmn, Nr, Nlm, (T*)res)
-    if (dtype == RIME_F32) { if (cplx) SFB_GO(float, 2); else SFB_GO(float, 1); }
-    else { if (cplx) SFB_GO(double, 2); else SFB_GO(double, 1); }
-#undef SFB_GO
-    return check_launch();
+    return with_real(dtype, [&](auto t) {
+        using T = decltype(t);
+        with_bool(cplx != 0, [&](auto c) {
+            hipLaunchKernelGGL((sfb_kernel<T, c.value ? 2 : 1, BWD>), dim3((unsigned)(Ntile * B)), dim3(256), 0,
+                               as_stream(stream), (const T*)X, (const T*)g, blocks, cols, tiles, Nblk, Ntile, Nlmn, Nr, Nlm,
+                               (T*)res);
+        });
+        return check_launch();
+    });
 }
 
 } // namespace rime
