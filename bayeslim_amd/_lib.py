@@ -51,6 +51,7 @@ SIGNATURES = {
                                         _vp, _sz, _vp]),
     'rime_fringe_pair_bwd_block': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i, _i,
                                         _vp, _vp, _sz, _vp]),
+    'rime_fringe_pair_bwd_splits': (_i, [_i, _i, _i]),
     'rime_fringe_pair_cross_fwd_block': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i,
                                               _vp, _sz, _vp]),
     'rime_fringe_pair_cross_bwd_block': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i, _i,

@@ -2709,7 +2709,7 @@ extern "C" int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const
     if (!workspace || workspace_bytes < rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)) return RIME_EWORKSPACE;
     PairBwdArgs A{};
     fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
-    const dim3 grid = fill_backward(A, gscale, gpsky, workspace, accumulate);
+    const dim3 grid = fill_backward(A, gscale, gpsky, workspace, accumulate, pair_bwd_launch_plan);
     A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
     // RIME_PAIR_AP=0: the pair backward evaluates every phasor (no rotation within progressions; A/B measurements; ops.py reads the
     // same variable and keeps the plain row order)
@@ -2724,4 +2724,11 @@ extern "C" int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const
         });
     });
     return check_launch();
+}
+
+// Pixel splits of a rime_fringe_pair_bwd_block launch (grid = Nt x splits x Nf); 0 for shapes the entry refuses
+extern "C" int rime_fringe_pair_bwd_splits(int Nt, int Nf, int Pstride)
+{
+    if (Nt <= 0 || Nt > 65535 || Nf <= 0 || Pstride <= 0 || Pstride % 64 != 0) return 0;
+    return pair_bwd_launch_plan(Nt, Nf, Pstride).S;
 }

@@ -121,6 +121,29 @@ inline PixelSplit bwd_split_plan(int Nt, int Nf, int Pstride)
     return {(ntile + per - 1) / per, per};
 }
 
+// Conjugate-pair backward: every block of a (t, f) row builds the same eight G planes from ~250 scattered loads per thread
+// before its pixel loop, and its waves issue nothing else meanwhile (three blocks share a CU).  Where the grid is large the
+// splits widen -- up to 1024 tiles, while 8 rounds of 3 blocks x 256 CUs remain to level the tail: the C4 diffuse launch
+// (2048 rows x 3072 tiles) stages 3 times per row instead of 12 (12.72 -> 12.28 ms per step, profiles/r14/pair_bwd_stage.txt).
+// Below 12 288 blocks of 256 tiles this is bwd_split_plan.  Pixel tiles are independent outputs: same bits for every split.
+// The threshold is calibrated on ONE shape, the C4 diffuse launch of the two-tile kernel (3 blocks per CU on the 256 CUs of
+// an MI355X; 6 and 3 stagings measured there): other shapes that widen (say 1024 rows x 98 304 pixels) follow the rule, not
+// a measurement of their own.  RIME_PAIR_BWD_WIDE=0 keeps bwd_split_plan (A/B measurements, tests/test_pair_bwd_wide_gpu.py).
+constexpr long PAIR_BWD_MIN_GRID = 8 * 3 * 256;
+inline PixelSplit pair_bwd_split_plan(int Nt, int Nf, int Pstride)
+{
+    const int ntile = Pstride / 32;
+    int per = bwd_split_plan(Nt, Nf, Pstride).per;
+    while (per >= 256 && per < 1024 && (long)Nt * Nf * ((ntile + 2 * per - 1) / (2 * per)) >= PAIR_BWD_MIN_GRID) per *= 2;
+    return {(ntile + per - 1) / per, per};
+}
+// the plan the pair backward launches with (the switch is read once)
+inline PixelSplit pair_bwd_launch_plan(int Nt, int Nf, int Pstride)
+{
+    static const bool wide = env_flag("RIME_PAIR_BWD_WIDE", 1);
+    return wide ? pair_bwd_split_plan(Nt, Nf, Pstride) : bwd_split_plan(Nt, Nf, Pstride);
+}
+
 // The fields every argument struct of these kernels has, under the same names
 template <class Args>
 inline void fill_geometry(Args& A, const double* antpos, const double* sdir, const double* freqs, const int* pair_direct,
@@ -144,10 +167,11 @@ inline dim3 fill_forward(Args& A, const float* psky, const float* scale, const f
 
 // ... and of a backward block: transposed gradient (the workspace rime_fringe_ant_bwd_prepare wrote), output plane, pixel split
 template <class Args>
-inline dim3 fill_backward(Args& A, const float* gscale, float* gpsky, const void* workspace, int accumulate)
+inline dim3 fill_backward(Args& A, const float* gscale, float* gpsky, const void* workspace, int accumulate,
+                          PixelSplit (*plan)(int, int, int) = bwd_split_plan)
 {
     A.gscale = gscale; A.gpsky = gpsky; A.gvt = (const float*)workspace; A.accumulate = accumulate ? 1 : 0;
-    const PixelSplit p = bwd_split_plan(A.Nt, A.Nf, A.Pstride);
+    const PixelSplit p = plan(A.Nt, A.Nf, A.Pstride);
     A.S = p.S; A.tiles_per_split = p.per;
     return dim3((unsigned)A.Nt * A.S * A.Nf, 1, 1);
 }

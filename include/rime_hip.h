@@ -222,6 +222,11 @@ int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const int* centr
                                const int* pair_conj, int Nbl, int Nt, int Nf, int Pstride,
                                long long st_t, long long st_f, long long st_p, int sign, int accumulate,
                                float* gpsky, const void* workspace, size_t workspace_bytes, void* stream);
+/* Pixel splits of a rime_fringe_pair_bwd_block launch (blocks = Nt x splits x Nf): 256 pixel tiles of 32 per block, fewer on
+ * a small grid, up to 1024 where at least 6144 blocks remain (every block stages the G planes of its row anew).  0 for a
+ * shape the block entry refuses.  RIME_PAIR_BWD_WIDE=0 (A/B measurements) keeps 256 at most; the answer is the plan in
+ * force.  Host only. */
+int rime_fringe_pair_bwd_splits(int Nt, int Nf, int Pstride);
 
 /* Conjugate-pair CROSS block, real psky (csrc/fringe_xpair.hip): the block between two groups I and J of ONE point-symmetric
  * array with more than 128 antennas.  Both groups are closed under the mirror (a group is a set of rows together with their
