@@ -96,6 +96,8 @@ SIGNATURES = {
     'rime_lbfgs_workspace': (_sz, [_i, _ll]),
     'rime_lbfgs_dots': (_i, [_i, _vp, _vp, _i, _ll, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     'rime_lbfgs_combine': (_i, [_i, _vp, _vp, _i, _ll, _vp, _vp, _vp, _vp, _d, _vp, _vp]),
+    'rime_bfgs_matvec': (_i, [_i, _vp, _ll, _ll, _vp, _i, _vp, _vp]),
+    'rime_bfgs_rank2': (_i, [_i, _vp, _ll, _ll, _vp, _vp, _d, _d, _vp]),
     'rime_hmc_workspace': (_sz, [_ll]),
     'rime_hmc_step': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _sz, _vp]),
     'rime_hmat_workspace': (_sz, [_i, _ll, _i]),

@@ -575,6 +575,28 @@ int rime_lbfgs_combine(int dtype, const void* const* s_rows, const void* const* 
                        const void* d, const double* a, const double* b, double gamma, void* r, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The two passes over the dense inverse Hessian of bfgs.BFGS (reference bfgs.py:169-235, where the update is the two matrix
+ * products V^T H V + rho s s^T) and of the dense replay of the factored form (bfgs.FactoredInvHessian.to_dense).
+ *   H   real T [N][ld], ld >= N; only columns 0 .. N - 1 of a row are read or written.  A base and an ld that are multiples of
+ *       16 bytes are served with 16-byte accesses, any other placement with element accesses of the same elements: same bits.
+ * rime_bfgs_matvec: r[i][c] = sum_j H[i][j] x[j][c], x and r T [N][nrhs], nrhs 1 or 2 (2: the interleaved real view of a complex
+ *   vector against the real H).  Summation order, per row and right-hand side, all in T: with W = 16 / sizeof(T), lane l of the
+ *   64 lanes of a wave runs one chain acc = fma(H[i][j], x[j], acc) from acc = 0 over its columns j in ascending order -- the
+ *   columns 64 W q + W l ... + W - 1 for q = 0, 1, ... -- and the 64 chains are then added pairwise by a butterfly, partners 32, 16,
+ *   8, 4, 2, 1 lanes apart.  A work-group owns whole rows; no atomics, no workspace: a row's bits depend on the row, x and N alone.
+ * rime_bfgs_rank2: in place, per element and in T with every operation rounded on its own,
+ *       H[i][j] = fma(T(b), x_i * x_j, fma(T(a), x_i * z_j + z_i * x_j, H[i][j]))
+ *   (the two products of the sum are rounded, then added; x_i * x_j is rounded, then scaled).  The expression is symmetric under
+ *   i <-> j, so a bit-symmetric H stays bit-symmetric.  BFGS update: x = s, z = H y, a = -rho, b = rho^2 (y . H y) + rho;
+ *   the shell (I + u v^T) H (I + v u^T) of a symmetric H: x = u, z = H v, a = 1, b = v . H v.
+ * x, z and r must not overlap the rows of H.  Checked before any HIP call: RIME_EINVAL for an unknown dtype, N < 1 (or above
+ * 2^31 - 1), ld < N, a null pointer, nrhs outside {1, 2}, a non-finite a or b, or a vector that overlaps H.
+ * ------------------------------------------------------------------------------------- */
+int rime_bfgs_matvec(int dtype, const void* H, long long ld, long long N, const void* x, int nrhs, void* r, void* stream);
+int rime_bfgs_rank2(int dtype, void* H, long long ld, long long N, const void* x, const void* z, double a, double b,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * One leapfrog stage of Hamiltonian Monte Carlo with a diagonal mass (sampler.leapfrog, sampler.HMC.K; reference
  * sampler.py:391-450, 1433-1583): momentum kick, position drift and kinetic energy in one pass over the flat parameter vector.
  *   q, p   T [N] updated in place;  g T [N] the potential's gradient;  eps T [N] step size per element or NULL (ones);
