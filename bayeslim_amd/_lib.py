@@ -113,6 +113,9 @@ SIGNATURES = {
     'rime_redcoupling_fwd': (_i, [_i] + [_vp] * 5 + [_i] * 8 + [_vp, _vp]),
     'rime_redcoupling_bwd_data': (_i, [_i] + [_vp] * 6 + [_i] * 8 + [_vp, _vp]),
     'rime_redcoupling_bwd_coupling': (_i, [_i] + [_vp] * 10 + [_i] * 11 + [_vp, _vp, _sz, _vp]),
+    'rime_partred_fwd': (_i, [_i, _i] + [_vp] * 4 + [_i] * 5 + [_ll] * 4 + [_vp, _vp]),
+    'rime_partred_bwd_data': (_i, [_i, _i] + [_vp] * 5 + [_i] * 5 + [_vp, _vp]),
+    'rime_partred_bwd_coeff': (_i, [_i, _i] + [_vp] * 4 + [_i] * 5 + [_ll] * 4 + [_vp, _vp]),
 }
 
 

@@ -31,6 +31,10 @@ fitted on a redundant array, Vc = A(eps) Vr + B(eps) conj(Vr) with one coefficie
 sums the non-zero first- and second-order terms from a flat entry list instead of the reference's two dense
 (Nbls_out, Nbls_in, Ntimes, Nfreqs) matrices; `gen_coupling_terms`, `configure_coupling_matrix_singlepath`, `cut_bl` and
 `CouplingInflate` (:2118-2175, 3047-3400) are its host side.
+
+Partly redundant arrays: `PartialRedVisInflate` (:2178-2344) mixes redundant model visibilities onto the physical baselines
+through a sparse matrix with one learnable real number per entry, on ops.partred_inflate: one pass forward and two reductions
+in a fixed order backward, in place of the CSR matrix, the transposed copy and the two torch.sparse.mm calls of the reference.
 """
 import copy
 
@@ -665,7 +669,7 @@ class VisCoupling(_CouplingTerm):
     come from the same kernel in a fixed summation order (bit-identical from run to run).  As in the reference the `double`
     keyword of forward decides, self.double only when None is passed.  Single polarisation only; no CPU implementation.
     The form fitted on a redundant array, with one coefficient per coupling vector (gen_coupling_terms), is RedVisCoupling;
-    CouplingInflate turns its parameters into the matrix used here.  Not built: PartialRedVisInflate, CouplingExpand.
+    CouplingInflate turns its parameters into the matrix used here.  Not built: CouplingExpand.
     """
     # a device push clears no cache here (_clear_on_push stays None)
     _push_names = ('flat_data_idx', 'flat_data_null', 'flat_conj_idx', 'flat_unconj_idx', 'bls_idx', 'I', 'dly', 'freqs')
@@ -1096,6 +1100,95 @@ class RedVisCoupling(_CouplingTerm):
         lists = [np.asarray(getattr(self, k)[1].cpu()) for k in _RVC_TUPLES] + \
                 [np.asarray(getattr(self, k)[2].cpu()) for k in _RVC_TUPLES[4:]]
         return {ct: int(sum((x == i).sum() for x in lists)) for i, ct in enumerate(self.coupling_terms)}
+
+
+# ---------------------------------------------------------------------------------------
+# partly redundant arrays: sparse learnable mixing of redundant models onto the physical baselines (calibration.py:2178-2344)
+# ---------------------------------------------------------------------------------------
+def _identity(x):
+    """the default response of PartialRedVisInflate (a module-level function, so that the module pickles)"""
+    return x
+
+
+class PartialRedVisInflate(_CalTerm):
+    """
+    Inflation of a redundant visibility model onto the physical baselines of an array that is only partly redundant
+    (calibration.py:2178-2344): out[p, q, i, t, f] = sum_e c_e V[p, q, col_e, t, f] over the non-zero entries e of row i of a
+    sparse mixing matrix A of shape `Ashape`, c = R(params + p0) real with one learnable number per entry.  bl2red maps every
+    baseline of new_bls to the indices along the Nbls axis of the input that sum to it (a list, or one Python / numpy integer).
+    The entries are listed in the order of new_bls and, within a baseline, of bl2red[bl]: `idx` (2, Nnz) holds their (row,
+    column), `Nred` the length of the list each belongs to, and params[k] belongs to entry idx[:, k], as the reference's
+    docstring and its dense path have it.  (The reference's CSR path sorts the columns of each row and so assigns the
+    parameters of an unsorted list to other entries; that is not reproduced.)  The default params, 1 / Nred, average the
+    contributing models; a baseline with an empty list gives a zero row.  `use_csr` is accepted for signature compatibility and
+    changes nothing: there is one path, ops.partred_inflate -- one pass forward, and both gradients by reductions in an order
+    the plan fixes (bit-identical from run to run), where the reference builds a CSR matrix on every forward, copies the data
+    with the baseline axis in front and calls torch.sparse.mm twice.
+    KeyError for a baseline missing from bl2red; ValueError for a negative column, the same column twice in one baseline, no
+    entry at all, params of another length than Nnz and, in forward, input whose baseline axis is not Ashape[1] long.
+    forward(vd, prior_cache=None) -> a new VisData of new_bls.  No CPU implementation.
+    """
+    _clear_on_push = None
+    _push_names = ('idx', 'Nred')
+
+    def __init__(self, bl2red, new_bls, params=None, p0=None, R=None, parameter=True, use_csr=True):
+        rows, cols, Nred = [], [], []
+        for i, bl in enumerate(new_bls):
+            red = bl2red[bl]
+            red = [int(red)] if isinstance(red, (int, np.integer)) else [int(r) for r in red]
+            if any(r < 0 for r in red):
+                raise ValueError('baseline %s: negative index %d' % (bl, min(red)))
+            if len(set(red)) != len(red):
+                raise ValueError('baseline %s names the same redundant visibility twice' % (bl,))
+            rows += [i] * len(red)
+            cols += red
+            Nred += [len(red)] * len(red)
+        if not rows:
+            raise ValueError('bl2red gives no entry for any baseline of new_bls')
+        idx = torch.as_tensor([rows, cols], dtype=torch.int64)
+        Nred = torch.as_tensor(Nred, dtype=torch.int64)
+        if params is None:
+            params = torch.ones(len(rows)) / Nred
+        if params.ndim != 1 or params.shape[0] != len(rows):
+            raise ValueError('params of shape %s, the mixing matrix has %d entries' % (tuple(params.shape), len(rows)))
+        super().__init__(params, R if R is not None else _identity, parameter=parameter, p0=p0)
+        self.idx, self.Nred = idx, Nred
+        self.Ashape = (len(new_bls), int(max(cols)) + 1)
+        self.new_bls = new_bls
+        self.use_csr = use_csr
+        self.device = None
+        self.plan = ops.PartRedPlan(rows, cols, *self.Ashape)
+
+    def _push_params(self, device):
+        """overloads utils.Module._push_params: R may be a plain callable without push"""
+        self.params = utils.push(self.params, device)
+        if hasattr(self.R, 'push'):
+            self.R.push(device)
+        self.p0 = utils.push(self.p0, device)
+        for prs in (self.priors_inp_params, self.priors_out_params):
+            for pr in (prs or []):
+                if pr is not None:
+                    pr.push(device)
+
+    def push(self, device):
+        """push params, p0 and the index tensors to a device (the plan's tables follow on their next use), or cast params and
+        p0 to a dtype"""
+        super().push(device)
+        if not isinstance(device, torch.dtype):
+            self.plan.tables(device)
+
+    def forward(self, vd, prior_cache=None, **kwargs):
+        """vd: VisData of shape (Npol, Npol, Ashape[1], Ntimes, Nfreqs); returns a new VisData of the baselines new_bls"""
+        if vd.data.shape[2] != self.Ashape[1]:
+            raise ValueError('input of %d baselines, the mixing matrix has %d columns' % (vd.data.shape[2], self.Ashape[1]))
+        _require_gpu(vd.data)
+        c = self._response(prior_cache)
+        real = torch.float32 if vd.data.dtype == torch.complex64 else torch.float64
+        data = ops.partred_inflate(vd.data, c.to(real), self.plan)
+        new_vis = dataset.VisData()
+        new_vis.setup_meta(telescope=vd.telescope, antpos=vd.antpos)
+        new_vis.setup_data(self.new_bls, vd.times, vd.freqs, pol=vd.pol, data=data, history=vd.history)
+        return new_vis
 
 
 # ---------------------------------------------------------------------------------------

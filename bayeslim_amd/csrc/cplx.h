@@ -6,7 +6,8 @@
 //                    cal.hip, jones.hip; coupling.hip where it builds E (cp_fetch) and applies conj(dly) to a dense result
 //   fixed form       cmul_fma, cmulc_fma, cfma, cfmac: explicit tfma, the re * re (re * im) product first, the im product fused
 //                    onto it.  redcoupling.hip throughout; coupling.hip in the tile product (cp_accumulate)
-// cadd, cconj and `s += a` are exact; redvis.hip uses only the last.  Some sites keep `{a.re, -a.im}` or `s.re += a.re; s.im +=
+// cadd, cconj and `s += a` are exact; redvis.hip uses only the last.  partred.hip takes the type alone: its coefficients are real,
+// so it writes one tfma per component.  Some sites keep `{a.re, -a.im}` or `s.re += a.re; s.im +=
 // a.im;` written out: through the call the compiler orders their kernel differently (same bits, other instructions) -- the
 // conjugates and the combine kernel of redcoupling.hip, the block sum of redvis.hip, the two sums of coupling.hip.
 #pragma once

@@ -543,6 +543,29 @@ def average_data(data, dim, index, N, wgts=None, cov=None, truncate=False):
     return avg_data, sum_wgts, avg_cov
 
 
+class RedVisAvg(utils.Module):
+    """VisData redundant-averaging block of a forward-model chain (dataset.py:3651-3696): VisData.bl_average with the
+    groups `reds`, the weights `wgts` (diagonal covariances only) and `inplace` fixed at construction; the counterpart of
+    RedVisInflate and of calibration.PartialRedVisInflate"""
+    def __init__(self, reds, wgts=None, inplace=False, device=None):
+        super().__init__()
+        self.reds = reds
+        self.wgts = wgts
+        self.inplace = inplace
+        self.device = device
+
+    def __call__(self, vd, **kwargs):
+        return vd.bl_average(reds=self.reds, wgts=self.wgts, inplace=self.inplace)
+
+    def forward(self, vd, **kwargs):
+        return self(vd, **kwargs)
+
+    def push(self, device):
+        self.wgts = utils.push(self.wgts, device)
+        if not isinstance(device, torch.dtype):
+            self.device = device
+
+
 class RedVisInflate(utils.Module):
     """VisData redundant-inflation block of a forward-model chain (dataset.py:3699-3735): the step that
     follows RIME when only one baseline per redundant group was simulated"""

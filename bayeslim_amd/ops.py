@@ -3186,3 +3186,113 @@ def redcoupling_apply(coupling, dly, data, plan):
     (bit-identical from run to run); columns that nothing reads and terms without an entry get zeros.  No CPU path.
     """
     return _RedCouplingApply.apply(coupling, dly, data, plan)
+
+
+# ---------------------------------------------------------------------------------------
+# sparse learnable mixing of a partly redundant array: out[i] = sum_e c[e] data[col[e]] (csrc/partred.hip)
+# ---------------------------------------------------------------------------------------
+class PartRedPlan(_IndexPlan):
+    """
+    Tables of rime_partred_fwd / _bwd_data / _bwd_coeff, built and checked with numpy on the host (no GPU needed) and cached
+    per device as int32 tensors.  Entry e adds c[e] * data[cols[e]] to output row rows[e]; the entries of a row are consecutive
+    (rows is non-decreasing) and are added in the order given.  `roff` [Nout + 1]: the entries of every row; `col`, `row`
+    [Nnz]; `coff` [Nin + 1] / `cmem` [Nnz]: the entries of every column, ascending entry number (the order of the gradient of
+    the data).  A row or a column may have no entry.  ValueError for arrays of different lengths or of another kind than
+    integer, no entry, a decreasing row, a row outside [0, Nout), a column outside [0, Nin) (a negative one included), the
+    same column twice in one row.
+    """
+    _TABLES = ('roff', 'col', 'row', 'coff', 'cmem')
+
+    def __init__(self, rows, cols, Nout, Nin):
+        rows = _host_array(rows, flat=True, integer='rows must be integers').astype(np.int64)
+        cols = _host_array(cols, flat=True, integer='cols must be integers').astype(np.int64)
+        self.Nout, self.Nin, self.Nnz = int(Nout), int(Nin), int(rows.size)
+        if cols.size != self.Nnz:
+            raise ValueError('rows and cols must have one length')
+        if self.Nnz < 1 or self.Nnz >= 2 ** 31 or min(self.Nout, self.Nin) < 1:
+            raise ValueError('the plan needs at least one entry (and fewer than 2^31), one row and one column')
+        if rows.min() < 0 or rows.max() >= self.Nout:
+            raise ValueError('entry row outside [0, %d)' % self.Nout)
+        if cols.min() < 0 or cols.max() >= self.Nin:
+            raise ValueError('entry column outside [0, %d)' % self.Nin)
+        if (np.diff(rows) < 0).any():
+            raise ValueError('the entries of a row must be consecutive: rows must not decrease')
+        if np.unique(rows * self.Nin + cols).size != self.Nnz:
+            raise ValueError('the same column twice in one row')
+        self.row, self.col = rows.astype(np.int32), cols.astype(np.int32)
+        self.roff = _csr(rows, self.Nout)[0]
+        self.coff, self.cmem = _csr(cols, self.Nin)
+        self.max_row, self.max_col = int(np.diff(self.roff).max()), int(np.diff(self.coff).max())
+
+
+def _partred_view(data, NP):
+    """data detached as the kernels read it: any view with non-negative strides whose two pol axes fold into one"""
+    v = data.detach().resolve_conj()
+    st = v.stride()
+    if min(st) < 0 or (NP == 2 and st[0] != 2 * st[1]):
+        v = v.contiguous()
+    return v
+
+
+class _PartRed(torch.autograd.Function):
+    """out = sum of the plan's entries; saves the data (as the view it came in) and the coefficients"""
+    @staticmethod
+    def forward(ctx, data, coeff, plan):
+        _require_cuda(data, coeff)
+        assert data.is_complex() and data.ndim == 5, 'complex data of shape (Npol, Npol, Nin, Ntimes, Nfreqs)'
+        NP, _, Nin, Nt, Nf = data.shape
+        assert NP in (1, 2) and data.shape[1] == NP, 'Npol must be 1 or 2'
+        if Nin != plan.Nin:
+            raise ValueError('data of %d baselines, the plan has %d columns' % (Nin, plan.Nin))
+        if coeff.is_complex() or tuple(coeff.shape) != (plan.Nnz,):
+            raise ValueError('coeff must be real of shape (%d,), one number per entry' % plan.Nnz)
+        code, real = _real_dtype(data)
+        v, c = _partred_view(data, NP), _dense(coeff, real)
+        st = v.stride()
+        T = plan.tables(v.device)
+        out = torch.empty((NP, NP, plan.Nout, Nt, Nf), dtype=v.dtype, device=v.device)
+        rc = lib.rime_partred_fwd(code, NP, _cptr(v), _ptr(c), _ptr(T['roff']), _ptr(T['col']), plan.Nout, Nin, plan.Nnz,
+                                  Nt, Nf, st[1], st[2], st[3], st[4], _cptr(out), _stream())
+        check(rc, 'rime_partred_fwd')
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(v, c)
+            ctx.plan, ctx.cdtype = plan, coeff.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        v, c = ctx.saved_tensors
+        plan = ctx.plan
+        NP, _, Nin, Nt, Nf = v.shape
+        g = _dense(gout, v.dtype)
+        code, _ = _real_dtype(v)
+        T = plan.tables(v.device)
+        dims = (plan.Nout, Nin, plan.Nnz, Nt, Nf)
+        gd = gc = None
+        if ctx.needs_input_grad[0]:
+            gd = torch.empty(tuple(v.shape), dtype=v.dtype, device=v.device)
+            rc = lib.rime_partred_bwd_data(code, NP, _cptr(g), _ptr(c), _ptr(T['row']), _ptr(T['coff']), _ptr(T['cmem']), *dims,
+                                           _cptr(gd), _stream())
+            check(rc, 'rime_partred_bwd_data')
+        if ctx.needs_input_grad[1]:
+            st = v.stride()
+            gc = torch.empty_like(c)
+            rc = lib.rime_partred_bwd_coeff(code, NP, _cptr(v), _cptr(g), _ptr(T['roff']), _ptr(T['col']), *dims,
+                                            st[1], st[2], st[3], st[4], _ptr(gc), _stream())
+            check(rc, 'rime_partred_bwd_coeff')
+            if gc.dtype != ctx.cdtype:
+                gc = gc.to(ctx.cdtype)
+        return gd, gc, None
+
+
+def partred_inflate(data, coeff, plan):
+    """
+    out[p, q, i, t, f] = sum over the entries e of row i of the PartRedPlan, in their order, of coeff[e] * data[p, q, col[e], t, f]
+    in one launch of rime_partred_fwd: data (Npol, Npol, Nin, Nt, Nf) complex64 / complex128, any view with non-negative
+    strides (a sliced, transposed or expanded view is read in place), coeff (Nnz,) real, cast to the real dtype of the data
+    -> (Npol, Npol, Nout, Nt, Nf).  A row without entries gives zeros.  Differentiable once in data and coeff, each gradient
+    computed only where it is asked for, by a reduction whose order the plan fixes, without atomics (bit-identical from run to
+    run); a column that nothing reads gets zeros.  No CPU path.
+    """
+    return _PartRed.apply(data, coeff, plan)

@@ -790,6 +790,40 @@ int rime_redcoupling_bwd_coupling(int dtype, const void* x, const void* dly, con
                                   int Fm, void* gx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sparse learnable mixing of a partly redundant array (calibration.PartialRedVisInflate; reference calibration.py:2178-2344;
+ * csrc/partred.hip):
+ *     out[p, i, t, f] = sum over the entries e of row i, e = roff[i] ... roff[i + 1] - 1 in that order, of c[e] V[p, col[e], t, f]
+ *   V                complex T, element (p, j, t, f) at complex offset p*vst_p + j*vst_b + t*vst_t + f*vst_f (strides >= 0,
+ *                    0 broadcasts), p < NP*NP, j < Nin
+ *   c, gc            T [Nnz]  real: one coefficient per entry, and its gradient
+ *   out, G           T [NP*NP][Nout][Nt][Nf][2]  contiguous, interleaved complex;  gV  T [NP*NP][Nin][Nt][Nf][2]  contiguous
+ *   roff             int32 [Nout + 1] (device): the entries of every row are consecutive, in the caller's order
+ *   col, row         int32 [Nnz] (device): column and row of every entry
+ *   coff, cmem       int32 [Nin + 1], [Nnz] (device): the entries of every column, ascending entry number
+ * rime_partred_fwd: one pass, one FMA per real component and term, lanes along (i, t, f); a row without entries gets 0.
+ * rime_partred_bwd_data:   gV[p, j, t, f] = sum over the entries e of column j, ascending, of c[e] G[p, row[e], t, f]: a block
+ *   owns 64 (time, channel) columns of one (p, j), its 4 waves take the members w, w + 4, ... in ascending position and wave 0
+ *   adds the partial sums from LDS in wave order; a column without entries gets 0.
+ * rime_partred_bwd_coeff:  gc[e] = sum over (p, t, f) of Re V Re G + Im V Im G with V = V[p, col[e], t, f], G = G[p, row[e], t, f]:
+ *   one block of 256 threads per row, 4 entries per sweep of the row of G; thread k adds the elements k, k + 256, ... in T (the
+ *   real product first, the imaginary one fused onto it), then in float64 the butterfly across the wave (partners 32 ... 1) and
+ *   the 4 waves in order, rounded to T once.
+ * No atomics, no workspace, no prior memset; every element of out, gV and gc is written exactly once and every summation order
+ * is a function of the tables alone (bit-reproducible).  Checked before any launch (RIME_EINVAL): an unknown dtype, a null
+ * pointer, NP outside {1, 2}, Nout, Nin, Nnz, Nt or Nf < 1, a negative stride.  The tables live on the device and are checked by
+ * the caller where they are built (entries in range, offsets non-decreasing from 0 to Nnz, every entry once per list); the
+ * kernels clamp every table read and never read or write outside the tensors, but for such a table the result is undefined.
+ * ------------------------------------------------------------------------------------- */
+int rime_partred_fwd(int dtype, int NP, const void* V, const void* c, const int* roff, const int* col,
+                     int Nout, int Nin, int Nnz, int Nt, int Nf, long long vst_p, long long vst_b,
+                     long long vst_t, long long vst_f, void* out, void* stream);
+int rime_partred_bwd_data(int dtype, int NP, const void* G, const void* c, const int* row, const int* coff,
+                          const int* cmem, int Nout, int Nin, int Nnz, int Nt, int Nf, void* gV, void* stream);
+int rime_partred_bwd_coeff(int dtype, int NP, const void* V, const void* G, const int* roff, const int* col,
+                           int Nout, int Nin, int Nnz, int Nt, int Nf, long long vst_p, long long vst_b,
+                           long long vst_t, long long vst_f, void* gc, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
