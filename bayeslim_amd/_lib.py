@@ -88,6 +88,7 @@ SIGNATURES = {
     'rime_alm2pix_pack': (_i, [_vp, _d, _i, _i, _i, _vp, _vp]),
     'rime_alm2pix_fwd_packed': (_i, [_vp, _vp, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'rime_alm2pix_bwd_packed': (_i, [_vp, _vp, _d, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'rime_alm2pix_plan': (_i, [_i, _d, _i, _i, _i, _i, _i, _ip]),
     'rime_sfb_fwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rime_sfb_bwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'rime_filt_apply': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _ll, _d, _vp, _vp]),

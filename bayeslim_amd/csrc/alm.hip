@@ -1240,10 +1240,13 @@ __global__ void alm_reduce_kernel(const float* __restrict__ part, float* __restr
     }
 }
 
+// row tiles of 32 per block of every matrix-core kernel here
+static int row_mt(int R) { return R > 64 ? 4 : (R > 32 ? 2 : 1); }
+
 static int bwd_splits(int R, int Ncoeff, int Npix)
 {
     // enough blocks to keep Ylm streaming: >= ~2048 waves; each split covers a multiple of 64 pixels
-    const int MT = R > 64 ? 4 : (R > 32 ? 2 : 1);
+    const int MT = row_mt(R);
     const long blocks = (long)((Ncoeff + 15) / 16) * ((R + MT * 32 - 1) / (MT * 32));
     long S = (2048 + blocks * MT - 1) / (blocks * MT);
     const long maxS = std::max(1, Npix / 1024);
@@ -1307,7 +1310,7 @@ static SplitPlan split_plan(int R, int K, int Ncoeff, bool backward, int dma = -
     const bool use_dma = dma < 0 ? bwd_use_dma(K) : dma != 0;
     const bool wide = dma == 2 && R > 64;                          // 8-wave blocks of 256 coefficients, one K step per chunk
     SplitPlan p{};
-    p.MT = R > 64 ? 4 : (R > 32 ? 2 : 1);
+    p.MT = row_mt(R);
     p.Rpad = ((R + p.MT * 32 - 1) / (p.MT * 32)) * p.MT * 32;
     p.nsteps = (K + 15) / 16;
     p.img_bytes = (size_t)p.nsteps * 2 * p.Rpad * 16;
@@ -1348,6 +1351,12 @@ static SplitPlan split_plan(int R, int K, int Ncoeff, bool backward, int dma = -
     return p;
 }
 
+// long rows: scale per row (one block each), then the tiled transposing split (row_scale_alm_kernel, split_rows_tiled_kernel)
+static bool split_long_rows(const SplitPlan& p, int R, int L)
+{
+    return p.Rpad % 64 == 0 && (long)R * L >= (1L << 20);
+}
+
 static void launch_split_rows(const float* X, int R, int L, const SplitPlan& p, int neg_odd, void* workspace,
                               hipStream_t st, uint4*& hi, uint4*& lo, float*& inv)
 {
@@ -1356,8 +1365,8 @@ static void launch_split_rows(const float* X, int R, int L, const SplitPlan& p, 
     inv = (float*)((char*)workspace + 2 * p.img_bytes);
     unsigned int* rowmax = (unsigned int*)(inv + p.Rpad);
     const int nseg = (2 * p.nsteps * 8 + SPLIT_SEG - 1) / SPLIT_SEG;
-    if (p.Rpad % 64 == 0 && (long)R * L >= (1L << 20)) {
-        // long rows: scale per row (one block each), then the tiled transposing split; `rowmax` doubles as the scale array
+    if (split_long_rows(p, R, L)) {
+        // `rowmax` doubles as the scale array
         float* scale = reinterpret_cast<float*>(rowmax);
         (void)hipMemsetAsync((char*)rowmax + (size_t)p.Rpad * sizeof(unsigned int), 0, 64, st);     // the zero granule
         hipLaunchKernelGGL(row_scale_alm_kernel, dim3(p.Rpad), dim3(256), 0, st, X, R, L, scale, inv);
@@ -1423,9 +1432,98 @@ static size_t split_ws_bytes(const SplitPlan& p)
     return 2 * p.img_bytes + (size_t)p.Rpad * (sizeof(float) + sizeof(unsigned int)) + 64;    // 64: a zero granule
 }
 
+// RIME_ALM_BWD_WIDE=0 keeps the 4-wave ring kernel of the packed backward above 64 rows (read once)
+static bool bwd_packed_wide(int R)
+{
+    static int env = -1;
+    if (env < 0) { const char* e = getenv("RIME_ALM_BWD_WIDE"); env = (e && e[0] == '0') ? 0 : 1; }
+    return env == 1 && R > 64;
+}
+
+// The plan of one transform: what the four entry points below launch and what rime_alm2pix_plan reports.
+struct AlmPlan {
+    int family, MT, row_tiles, col_tiles, S, long_rows;
+    SplitPlan p;                     // the f16-split families only
+};
+
+static AlmPlan plan_fwd(int dtype, double y_scale, int R, int Ncoeff, int Npix)
+{
+    AlmPlan a{};
+    a.S = 1;
+    if (dtype == RIME_F32 && y_scale > 0) {
+        a.p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
+        a.family = RIME_ALM_F16_REG; a.MT = a.p.MT;
+        a.col_tiles = (Npix + 127) / 128; a.row_tiles = a.p.Rpad / (a.p.MT * 32);
+        a.long_rows = split_long_rows(a.p, R, 2 * Ncoeff);
+    } else if (dtype == RIME_F32) {
+        a.family = RIME_ALM_F32_MFMA; a.MT = row_mt(R);
+        a.col_tiles = (Npix + 127) / 128; a.row_tiles = (R + a.MT * 32 - 1) / (a.MT * 32);
+    } else {
+        a.family = RIME_ALM_F64_VALU; a.MT = 0;
+        a.col_tiles = (Npix + 255) / 256; a.row_tiles = (R + 15) / 16;
+    }
+    return a;
+}
+
+static AlmPlan plan_bwd(int dtype, double y_scale, int R, int Ncoeff, int Npix)
+{
+    AlmPlan a{};
+    a.S = 1;
+    if (dtype == RIME_F32 && y_scale > 0) {
+        a.p = split_plan(R, Npix, Ncoeff, true);
+        a.family = bwd_use_dma(Npix) ? RIME_ALM_F16_DMA : RIME_ALM_F16_REG; a.MT = a.p.MT;
+        a.col_tiles = (Ncoeff + 127) / 128; a.row_tiles = a.p.Rpad / (a.p.MT * 32);
+        a.S = a.p.S;
+        a.long_rows = split_long_rows(a.p, R, Npix);
+    } else if (dtype == RIME_F32) {
+        a.family = RIME_ALM_F32_MFMA; a.MT = row_mt(R);
+        a.col_tiles = (Ncoeff + 15) / 16; a.row_tiles = (R + a.MT * 32 - 1) / (a.MT * 32);
+        a.S = bwd_splits(R, Ncoeff, Npix);
+    } else {
+        a.family = RIME_ALM_F64_VALU; a.MT = 0;
+        a.col_tiles = (Ncoeff + 3) / 4; a.row_tiles = (R + 7) / 8;
+    }
+    return a;
+}
+
+static AlmPlan plan_fwd_packed(int R, int Ncoeff, int Npix)
+{
+    AlmPlan a{};
+    a.p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
+    a.family = RIME_ALM_PACKED4; a.MT = a.p.MT;
+    a.col_tiles = (Npix + 127) / 128; a.row_tiles = a.p.Rpad / (a.p.MT * 32);
+    a.S = fwd_packed_splits(R, Ncoeff, Npix, a.p.MT);
+    a.long_rows = split_long_rows(a.p, R, 2 * Ncoeff);
+    return a;
+}
+
+static AlmPlan plan_bwd_packed(int R, int Ncoeff, int Npix)
+{
+    AlmPlan a{};
+    const bool wide = bwd_packed_wide(R);
+    a.p = split_plan(R, Npix, Ncoeff, true, wide ? 2 : 1);
+    a.family = wide ? RIME_ALM_PACKED8 : RIME_ALM_PACKED4; a.MT = a.p.MT;
+    a.col_tiles = wide ? (Ncoeff + 255) / 256 : (Ncoeff + 127) / 128;
+    a.row_tiles = a.p.Rpad / (a.p.MT * 32);
+    a.S = a.p.S;
+    a.long_rows = split_long_rows(a.p, R, Npix);
+    return a;
+}
+
 } // namespace rime
 
 using namespace rime;
+
+extern "C" int rime_alm2pix_plan(int dtype, double y_scale, int R, int Ncoeff, int Npix, int direction, int packed, int* plan)
+{
+    if (!plan || (dtype != RIME_F32 && dtype != RIME_F64) || !(y_scale >= 0) || R <= 0 || Ncoeff <= 0 || Npix <= 0 ||
+        (direction != 0 && direction != 1) || (packed != 0 && packed != 1)) return RIME_EINVAL;
+    if (packed && (dtype != RIME_F32 || !(y_scale > 0))) return RIME_EINVAL;
+    const AlmPlan a = packed ? (direction ? plan_bwd_packed(R, Ncoeff, Npix) : plan_fwd_packed(R, Ncoeff, Npix))
+                             : (direction ? plan_bwd(dtype, y_scale, R, Ncoeff, Npix) : plan_fwd(dtype, y_scale, R, Ncoeff, Npix));
+    plan[0] = a.family; plan[1] = a.MT; plan[2] = a.row_tiles; plan[3] = a.col_tiles; plan[4] = a.S; plan[5] = a.long_rows;
+    return RIME_OK;
+}
 
 extern "C" size_t rime_alm2pix_fwd_workspace(int dtype, int R, int Ncoeff, int Npix)
 {
@@ -1441,30 +1539,30 @@ extern "C" int rime_alm2pix_fwd(int dtype, const void* alm, const void* Ylm, dou
 {
     if (!alm || !Ylm || !out || R <= 0 || Ncoeff <= 0 || Npix <= 0 || y_scale < 0) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32 && y_scale > 0) {
-        const SplitPlan p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
+    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    const AlmPlan pl = plan_fwd(dtype, y_scale, R, Ncoeff, Npix);
+    const dim3 grid(pl.col_tiles, pl.row_tiles);
+    if (pl.family == RIME_ALM_F16_REG) {
+        const SplitPlan& p = pl.p;
         if (!workspace || workspace_bytes < split_ws_bytes(p)) return RIME_EWORKSPACE;
         uint4 *hi, *lo; float* inv;
         launch_split_rows((const float*)alm, R, 2 * Ncoeff, p, 1, workspace, st, hi, lo, inv);
-        dim3 grid((Npix + 127) / 128, p.Rpad / (p.MT * 32));
         const float ys = (float)y_scale;
         const float* Y = (const float*)Ylm; float* o = (float*)out;
         if (p.MT == 4) hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<4>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, o);
         else if (p.MT == 2) hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<2>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, o);
         else hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<1>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, o);
-    } else if (dtype == RIME_F32) {
+    } else if (pl.family == RIME_ALM_F32_MFMA) {
         const float* a = (const float*)alm; const float* Y = (const float*)Ylm; float* o = (float*)out;
-        const int MT = R > 64 ? 4 : (R > 32 ? 2 : 1);
-        dim3 grid((Npix + 127) / 128, (R + MT * 32 - 1) / (MT * 32));
+        const int MT = pl.MT;
         if (MT == 4) hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<4>), grid, dim3(256), 0, st, a, Y, R, Ncoeff, Npix, o);
         else if (MT == 2) hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<2>), grid, dim3(256), 0, st, a, Y, R, Ncoeff, Npix, o);
         else hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<1>), grid, dim3(256), 0, st, a, Y, R, Ncoeff, Npix, o);
-    } else if (dtype == RIME_F64) {
-        constexpr int RTA = 16;
-        dim3 grid((Npix + 255) / 256, (R + RTA - 1) / RTA);
+    } else {
+        constexpr int RTA = 16;                        // plan_fwd: row_tiles
         hipLaunchKernelGGL((alm2pix_fwd_kernel<double, RTA>), grid, dim3(256), 0, st,
                            (const double*)alm, (const double*)Ylm, R, Ncoeff, Npix, (double*)out);
-    } else return RIME_EINVAL;
+    }
     return check_launch();
 }
 
@@ -1488,18 +1586,20 @@ extern "C" int rime_alm2pix_bwd(int dtype, const void* gout, const void* Ylm, do
 {
     if (!gout || !Ylm || !galm || R <= 0 || Ncoeff <= 0 || Npix <= 0 || y_scale < 0) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == RIME_F32 && y_scale > 0) {
-        const SplitPlan p = split_plan(R, Npix, Ncoeff, true);
+    if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
+    const AlmPlan pl = plan_bwd(dtype, y_scale, R, Ncoeff, Npix);
+    if (pl.family == RIME_ALM_F16_DMA || pl.family == RIME_ALM_F16_REG) {
+        const SplitPlan& p = pl.p;
         const size_t len = (size_t)R * Ncoeff * 2;
         const size_t need = split_ws_bytes(p) + (size_t)p.S * len * sizeof(float);
         if (!workspace || workspace_bytes < need) return RIME_EWORKSPACE;
         uint4 *hi, *lo; float* inv;
         launch_split_rows((const float*)gout, R, Npix, p, 0, workspace, st, hi, lo, inv);
         float* part = p.S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)galm;
-        dim3 grid(p.S, (Ncoeff + 127) / 128, p.Rpad / (p.MT * 32));
+        dim3 grid(pl.S, pl.col_tiles, pl.row_tiles);
         const float ys = (float)y_scale;
         const float* Y = (const float*)Ylm;
-        if (bwd_use_dma(Npix)) {
+        if (pl.family == RIME_ALM_F16_DMA) {
             const float* zero16 = (const float*)((char*)workspace + split_ws_bytes(p) - 64);
             hipError_t e = hipSuccess;
             // chunks of 2 K steps in a ring of 3 slots; 1 K step in 6 slots (more, smaller loads in flight) measured the same
@@ -1517,15 +1617,15 @@ extern "C" int rime_alm2pix_bwd(int dtype, const void* gout, const void* Ylm, do
         }
         return check_launch();
     }
-    if (dtype == RIME_F32) {
-        const int S = bwd_splits(R, Ncoeff, Npix);
+    if (pl.family == RIME_ALM_F32_MFMA) {
+        const int S = pl.S;
         const size_t len = (size_t)R * Ncoeff * 2;
         if (S > 1 && (!workspace || workspace_bytes < (size_t)S * len * sizeof(float))) return RIME_EWORKSPACE;
         float* part = S > 1 ? (float*)workspace : (float*)galm;
         int pps = (Npix + S - 1) / S;
         pps = ((pps + 63) / 64) * 64;
-        const int MT = R > 64 ? 4 : (R > 32 ? 2 : 1);
-        dim3 grid((Ncoeff + 15) / 16, S, (R + MT * 32 - 1) / (MT * 32));
+        const int MT = pl.MT;
+        dim3 grid(pl.col_tiles, S, pl.row_tiles);
         const float* g = (const float*)gout; const float* Y = (const float*)Ylm;
         if (MT == 4) hipLaunchKernelGGL((alm2pix_bwd_mfma_kernel<4>), grid, dim3(256), 0, st, g, Y, R, Ncoeff, Npix, pps, part);
         else if (MT == 2) hipLaunchKernelGGL((alm2pix_bwd_mfma_kernel<2>), grid, dim3(128), 0, st, g, Y, R, Ncoeff, Npix, pps, part);
@@ -1536,9 +1636,8 @@ extern "C" int rime_alm2pix_bwd(int dtype, const void* gout, const void* Ylm, do
         }
         return check_launch();
     }
-    if (dtype != RIME_F64) return RIME_EINVAL;
-    constexpr int CT = 4, RTB = 8;
-    dim3 grid((Ncoeff + CT - 1) / CT, (R + RTB - 1) / RTB);
+    constexpr int CT = 4, RTB = 8;                     // plan_bwd: col_tiles, row_tiles
+    dim3 grid(pl.col_tiles, pl.row_tiles);
     hipLaunchKernelGGL((alm2pix_bwd_kernel<double, CT, RTB>), grid, dim3(256), 0, st,
                        (const double*)gout, (const double*)Ylm, R, Ncoeff, Npix, (double*)galm);
     return check_launch();
@@ -1580,14 +1679,14 @@ extern "C" int rime_alm2pix_fwd_packed(const void* alm, const void* packed, doub
 {
     if (!alm || !packed || !out || R <= 0 || Ncoeff <= 0 || Npix <= 0 || !(y_scale > 0)) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const SplitPlan p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
-    if (!workspace || workspace_bytes < split_ws_bytes(p)) return RIME_EWORKSPACE;
+    const AlmPlan pl = plan_fwd_packed(R, Ncoeff, Npix);
+    const SplitPlan& p = pl.p;
+    const int S = pl.S;
+    const size_t len = (size_t)R * Npix;
+    if (!workspace || workspace_bytes < split_ws_bytes(p) + (S > 1 ? (size_t)S * len * sizeof(float) : 0)) return RIME_EWORKSPACE;
     uint4 *hi, *lo; float* inv;
     launch_split_rows((const float*)alm, R, 2 * Ncoeff, p, 1, workspace, st, hi, lo, inv);
-    const int S = fwd_packed_splits(R, Ncoeff, Npix, p.MT);
-    const size_t len = (size_t)R * Npix;
-    if (S > 1 && workspace_bytes < split_ws_bytes(p) + (size_t)S * len * sizeof(float)) return RIME_EWORKSPACE;
-    dim3 grid((Npix + 127) / 128, p.Rpad / (p.MT * 32), S);
+    dim3 grid(pl.col_tiles, pl.row_tiles, S);
     const float ys = (float)y_scale;
     const uint4* Y = (const uint4*)packed;
     float* o = S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)out;
@@ -1608,23 +1707,22 @@ extern "C" int rime_alm2pix_bwd_packed(const void* gout, const void* packed, dou
 {
     if (!gout || !packed || !galm || R <= 0 || Ncoeff <= 0 || Npix <= 0 || !(y_scale > 0)) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static int wide_env = -1;
-    if (wide_env < 0) { const char* ev = getenv("RIME_ALM_BWD_WIDE"); wide_env = (ev && ev[0] == '0') ? 0 : 1; }
-    const bool wide = wide_env == 1 && R > 64;
-    const SplitPlan p = split_plan(R, Npix, Ncoeff, true, wide ? 2 : 1);
+    const AlmPlan pl = plan_bwd_packed(R, Ncoeff, Npix);
+    const bool wide = pl.family == RIME_ALM_PACKED8;
+    const SplitPlan& p = pl.p;
     const size_t len = (size_t)R * Ncoeff * 2;
     const size_t need = split_ws_bytes(p) + (size_t)p.S * len * sizeof(float);
     if (!workspace || workspace_bytes < need) return RIME_EWORKSPACE;
     uint4 *hi, *lo; float* inv;
     launch_split_rows((const float*)gout, R, Npix, p, 0, workspace, st, hi, lo, inv);
     float* part = p.S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)galm;
-    dim3 grid(p.S, (Ncoeff + 127) / 128, p.Rpad / (p.MT * 32));
+    dim3 grid(pl.S, pl.col_tiles, pl.row_tiles);
     const float* zero16 = (const float*)((char*)workspace + split_ws_bytes(p) - 64);
     const uint4* Y = (const uint4*)packed;
     const int nsteps = pk_bwd_steps(Npix);
     hipError_t e;
     if (wide) {
-        const int CT2 = (Ncoeff + 255) / 256, RT = p.Rpad / 128, NB = p.S * CT2 * RT;
+        const int CT2 = pl.col_tiles, RT = pl.row_tiles, NB = p.S * CT2 * RT;
         static unsigned long long configured = 0ull;
         int devid = 0;
         if (hipGetDevice(&devid) != hipSuccess) devid = 0;

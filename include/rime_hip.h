@@ -392,6 +392,27 @@ int rime_alm2pix_fwd_packed(const void* alm, const void* packed, double y_scale,
 int rime_alm2pix_bwd_packed(const void* gout, const void* packed, double y_scale, int R, int Ncoeff, int Npix,
                             void* galm, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The plan in force for one transform: which kernel family the entry point above would launch for these arguments and on
+ * what grid.  `direction` 0 = forward, 1 = backward; `packed` 1 = rime_alm2pix_fwd_packed / _bwd_packed (float32 and
+ * y_scale > 0 only), 0 = rime_alm2pix_fwd / _bwd.  Fills plan[0 .. 5]:
+ *   plan[0] kernel family (RIME_ALM_*, below)
+ *   plan[1] MT: row tiles of 32 per block (1, 2 or 4; 0 for the float64 VALU kernels)
+ *   plan[2] row tiles of the grid (blocks along the rows)
+ *   plan[3] column tiles of the grid (blocks along the pixels in the forward, along the coefficients in the backward)
+ *   plan[4] S: pixel splits of the backward / K splits of the packed forward (1 = no partial planes, no reduction)
+ *   plan[5] 1 when the row operand takes the tiled long-row split (f16-split families), else 0
+ * Answered by the functions the launches themselves call, the switches RIME_ALM_BWD_DMA, RIME_ALM_BWD_WIDE (read once
+ * per process), RIME_ALM_BWD_SPLITS and RIME_ALM_FWD_SPLITS (read on every call) included.  Host only: no launch, no
+ * allocation.  RIME_EINVAL for a null plan, an unknown dtype, a negative or NaN y_scale, an extent <= 0, a direction or
+ * packed flag outside {0, 1}, and packed = 1 with float64 or y_scale == 0. */
+#define RIME_ALM_F64_VALU 0   /* float64, vector ALU                                                        */
+#define RIME_ALM_F32_MFMA 1   /* float32, y_scale == 0: exact-f32 matrix cores                              */
+#define RIME_ALM_F16_REG  2   /* f16 split, Ylm staged through registers (forward; backward at odd Npix)    */
+#define RIME_ALM_F16_DMA  3   /* f16 split, backward: LDS-DMA ring (even Npix)                              */
+#define RIME_ALM_PACKED4  4   /* packed Ylm, 4-wave blocks                                                  */
+#define RIME_ALM_PACKED8  5   /* packed Ylm, backward above 64 rows: 8-wave blocks of 256 coefficients      */
+int rime_alm2pix_plan(int dtype, double y_scale, int R, int Ncoeff, int Npix, int direction, int packed, int* plan);
+
 /* ---------------------------------------------------------------------------------------
  * Spherical Fourier-Bessel radial transform  a_lm(r) = sum_n g_l(k_ln r) t_lmn  for every degree l in ONE launch
  * (SFBModel.forward_gln, sph_harm.py:1979-1982: a Python loop of one small matmul per degree) and its adjoint.

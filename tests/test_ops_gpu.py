@@ -1209,8 +1209,9 @@ def test_alm2pix_larger_random(ops):
 
 @pytest.mark.parametrize('R,lmax,Npix', [(128, 24, 3000), (40, 12, 1111), (3, 40, 5000)])
 def test_alm2pix_mfma_shapes(ops, R, lmax, Npix):
-    """float32 path = f32 matrix cores: row-tile counts 4 / 2 / 1, ragged pixel and coefficient tails,
-    pixel-split backward"""
+    """float32 path = the f16-split kernels on the f16 matrix cores (ops.ALM_SPLIT_F16 is on by default; unpacked at these
+    sizes): row-tile counts 4 / 2 / 1, ragged pixel and coefficient tails, pixel-split backward.  The exact-f32
+    matrix-core kernels and an elementwise bound are in tests/test_alm_gpu.py."""
     rng = np.random.default_rng(R)
     l, m = orc.gen_lm(lmax)
     th, ph = np.arccos(rng.uniform(-1, 1, Npix)), rng.uniform(0, 2 * np.pi, Npix)
