@@ -14,6 +14,7 @@
 // pair per K-step), operands staged through LDS in fragment order, Ylm streamed once.
 // float64 (parity oracle precision) and tiny shapes: VALU register-tiled kernels.
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "rime_common.h"
 
 namespace rime {
@@ -114,6 +115,53 @@ alm2pix_bwd_kernel(const T* __restrict__ gout, const T* __restrict__ Ylm, int R,
 // ---------------------------------------------------------------------------------------
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+template <int MT> __device__ __forceinline__ void zero(f32x16 (&acc)[MT])
+{
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+}
+
+// the row of accumulator element e of a lane's row tile m (the D layout above), tiles from row r0 on
+__device__ __forceinline__ int tile_row(int r0, int m, int e, int lane)
+{
+    return r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
+}
+
+// forward epilogue: the lane's column `col` of MT row tiles into one output plane [R][Npix]; the f16-split kernels
+// undo the row scales and y_scale on the way
+template <int MT>
+__device__ __forceinline__ void store_fwd_tile(const f32x16 (&acc)[MT], float* plane, int r0, int R, int Npix,
+                                               int col, int lane)
+{
+    if (col < Npix) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = tile_row(r0, m, e, lane);
+                if (row < R) plane[(size_t)row * Npix + col] = acc[m][e];
+            }
+    }
+}
+
+template <int MT>
+__device__ __forceinline__ void store_fwd_tile(const f32x16 (&acc)[MT], float* plane, int r0, int R, int Npix,
+                                               int col, int lane, const float* __restrict__ inv_scale, float y_scale)
+{
+    if (col < Npix) {
+        const float iy = 1.0f / y_scale;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = tile_row(r0, m, e, lane);
+                if (row < R) plane[(size_t)row * Npix + col] = acc[m][e] * inv_scale[row] * iy;
+            }
+    }
+}
+
 // forward: out[r, j] = sum_c are[r,c] Yre[c,j] - aim[r,c] Yim[c,j].
 //   K-step = one coefficient c (k = re / im).  Block = 4 waves x 32 pixels; every wave keeps
 //   MT row tiles (MT*32 rows) of accumulators.  alm chunks [CT coeffs][re,-im][rows] are staged in
@@ -134,10 +182,7 @@ alm2pix_fwd_mfma_kernel(const float* __restrict__ alm, const float* __restrict__
     const int jl = min(j0 + (lane & 31), Npix - 1);
     const int ri = lane >> 5;
     f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    zero(acc);
 
     // Ylm fragments of one chunk live in registers and are fetched one chunk ahead, so the
     // 32 independent 256-B reads of chunk k+1 are in flight under the MFMAs of chunk k
@@ -175,16 +220,7 @@ alm2pix_fwd_mfma_kernel(const float* __restrict__ alm, const float* __restrict__
         for (int cc = 0; cc < CT; ++cc) bcur[cc] = bnxt[cc];
     }
     RIME_MFMA_SETTLE();
-    const int col = j0 + (lane & 31);
-    if (col < Npix) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) out[(size_t)row * Npix + col] = acc[m][e];
-            }
-    }
+    store_fwd_tile(acc, out, r0, R, Npix, j0 + (lane & 31), lane);
 }
 
 // backward: galm[r, (c,q)] = sum_j gout[r, j] * Y[c, j, q] * (q ? -1 : +1).
@@ -293,6 +329,86 @@ __device__ __forceinline__ void split2h(float a, float b, uint32_t& hi, uint32_t
 }
 #define ALM_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0)
 
+// eight consecutive K values -> the hi / lo granules of a fragment
+__device__ __forceinline__ void split8(const float (&v)[8], uint4& hi, uint4& lo)
+{
+    split2h(v[0], v[1], hi.x, lo.x); split2h(v[2], v[3], hi.y, lo.y);
+    split2h(v[4], v[5], hi.z, lo.z); split2h(v[6], v[7], hi.w, lo.w);
+}
+
+// eight pixels of one Ylm row (four float4 = 2 x (re, im) each) x y_scale -> the re and im B fragments of the backward
+__device__ __forceinline__ void split_y4(const float4 (&y)[4], float y_scale, uint4& rh, uint4& rl, uint4& ih, uint4& il)
+{
+    split2h(y[0].x * y_scale, y[0].z * y_scale, rh.x, rl.x);
+    split2h(y[1].x * y_scale, y[1].z * y_scale, rh.y, rl.y);
+    split2h(y[2].x * y_scale, y[2].z * y_scale, rh.z, rl.z);
+    split2h(y[3].x * y_scale, y[3].z * y_scale, rh.w, rl.w);
+    split2h(y[0].y * y_scale, y[0].w * y_scale, ih.x, il.x);
+    split2h(y[1].y * y_scale, y[1].w * y_scale, ih.y, il.y);
+    split2h(y[2].y * y_scale, y[2].w * y_scale, ih.z, il.z);
+    split2h(y[3].y * y_scale, y[3].w * y_scale, ih.w, il.w);
+}
+
+// the three cross products of one K step (lo x lo is below the f32 accumulation error), forward and backward
+__device__ __forceinline__ void mfma3(uint4 ah, uint4 al, uint4 bh, uint4 bl, f32x16& acc)
+{
+    acc = ALM_MFMA(ah, bh, acc);
+    acc = ALM_MFMA(ah, bl, acc);
+    acc = ALM_MFMA(al, bh, acc);
+}
+
+__device__ __forceinline__ void mfma6(uint4 ah, uint4 al, uint4 rh, uint4 rl, uint4 ih, uint4 il, f32x16& accr, f32x16& acci)
+{
+    accr = ALM_MFMA(ah, rh, accr);
+    acci = ALM_MFMA(ah, ih, acci);
+    accr = ALM_MFMA(ah, rl, accr);
+    acci = ALM_MFMA(ah, il, acci);
+    accr = ALM_MFMA(al, rh, accr);
+    acci = ALM_MFMA(al, ih, acci);
+}
+
+// backward epilogue: the lane's coefficient c of MT row tiles into one partial plane [R][Ncoeff][re, im], row scales and
+// y_scale undone, the imaginary part conjugated
+template <int MT>
+__device__ __forceinline__ void store_bwd_tile(const f32x16 (&accr)[MT], const f32x16 (&acci)[MT], float* __restrict__ plane,
+                                               int r0, int R, int Ncoeff, int c, int lane,
+                                               const float* __restrict__ inv_scale, float y_scale)
+{
+    if (c < Ncoeff) {
+        const float iy = 1.0f / y_scale;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int row = tile_row(r0, m, e, lane);
+                if (row < R) {
+                    const float sc = inv_scale[row] * iy;
+                    *reinterpret_cast<float2*>(plane + ((size_t)row * Ncoeff + c) * 2) =
+                        make_float2(accr[m][e] * sc, -acci[m][e] * sc);
+                }
+            }
+    }
+}
+
+// register-staged kernels: this thread's share of the pre-split row granules of KS K steps from s0 on, (ks * 2 + h) * ROWS
+// + row in block order, zero beyond the `nsteps` K steps the images hold
+template <int ROWS, int KS>
+__device__ __forceinline__ void fetch_granules(const uint4* __restrict__ img_hi, const uint4* __restrict__ img_lo, int Rpad,
+                                               int r0, int s0, int nsteps, int tid, uint4 (&ahq)[(2 * KS * ROWS + 255) / 256],
+                                               uint4 (&alq)[(2 * KS * ROWS + 255) / 256])
+{
+    constexpr int NG = 2 * KS * ROWS, PT = (NG + 255) / 256;
+#pragma unroll
+    for (int u = 0; u < PT; ++u) {
+        const int i = tid + u * 256;
+        const int row = i % ROWS, g = i / ROWS;        // g = ks * 2 + h
+        const int sg = s0 * 2 + g;
+        const bool ok = (NG % 256 == 0 || i < NG) && sg < nsteps * 2;
+        ahq[u] = ok ? img_hi[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
+        alq[u] = ok ? img_lo[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
+    }
+}
+
 // Row operand X [R][L] (f32) -> per-row power-of-two scale, f16 hi / lo images in A-fragment order:
 // granule ((s * 2 + h) * Rpad + r) holds k = 16 s + 8 h + 0..7 of row r (zero beyond L / R).
 // `neg_odd`: negate odd k (the imaginary parts of alm: out = are Yre - aim Yim).
@@ -335,8 +451,7 @@ split_rows_kernel(const float* __restrict__ X, int R, int L, int Rpad, int neg_o
             v[jj] = (neg_odd && (jj & 1)) ? -x : x;
         }
         uint4 hi, lo;
-        split2h(v[0], v[1], hi.x, lo.x); split2h(v[2], v[3], hi.y, lo.y);
-        split2h(v[4], v[5], hi.z, lo.z); split2h(v[6], v[7], hi.w, lo.w);
+        split8(v, hi, lo);
         img_hi[(size_t)g * Rpad + r] = hi;
         img_lo[(size_t)g * Rpad + r] = lo;
     }
@@ -401,8 +516,7 @@ split_rows_tiled_kernel(const float* __restrict__ X, int R, int L, int Rpad, int
 #pragma unroll
         for (int jj = 0; jj < 8; ++jj) { v[jj] *= sc; if (neg_odd && (jj & 1)) v[jj] = -v[jj]; }
         uint4 hi, lo;
-        split2h(v[0], v[1], hi.x, lo.x); split2h(v[2], v[3], hi.y, lo.y);
-        split2h(v[4], v[5], hi.z, lo.z); split2h(v[6], v[7], hi.w, lo.w);
+        split8(v, hi, lo);
         t_hi[gl * 65 + rr] = hi;
         t_lo[gl * 65 + rr] = lo;
     }
@@ -439,12 +553,9 @@ alm2pix_fwd_f16_kernel(const uint4* __restrict__ a_hi, const uint4* __restrict__
     const int h = lane >> 5;
     const int nsteps = (2 * Ncoeff + 15) / 16;
     f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    zero(acc);
 
-    float2 bcur[16], bnxt[16];                         // [ks * 4 + i]: coefficient c0 + 8 ks + 4 h + i
+    float2 bcur[16], bnxt[16];                        // [ks * 4 + i]: coefficient c0 + 8 ks + 4 h + i
     uint4 ahq[PT], alq[PT];
     auto load_b = [&](int c0, float2 (&b)[16]) {
 #pragma unroll
@@ -455,72 +566,34 @@ alm2pix_fwd_f16_kernel(const uint4* __restrict__ a_hi, const uint4* __restrict__
         }
     };
     auto fetch_a = [&](int s0) {                       // K steps s0 .. s0 + 3
-#pragma unroll
-        for (int u = 0; u < PT; ++u) {
-            const int i = tid + u * 256;
-            const int row = i % ROWS, g = i / ROWS;    // g = ks * 2 + h
-            const int sg = s0 * 2 + g;
-            const bool ok = sg < nsteps * 2;
-            ahq[u] = ok ? a_hi[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
-            alq[u] = ok ? a_lo[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
-        }
+        fetch_granules<ROWS, 4>(a_hi, a_lo, Rpad, r0, s0, nsteps, tid, ahq, alq);
     };
     load_b(0, bcur);
     fetch_a(0);
     for (int c0 = 0; c0 < Ncoeff; c0 += 32) {
-#if !defined(RIME_ALM_ABL) || RIME_ALM_ABL != 2
         __syncthreads();                               // previous chunk consumed
 #pragma unroll
         for (int u = 0; u < PT; ++u) { lds_hi[tid + u * 256] = ahq[u]; lds_lo[tid + u * 256] = alq[u]; }
         __syncthreads();
         if (c0 + 32 < Ncoeff) { load_b(c0 + 32, bnxt); fetch_a(c0 / 8 + 4); }
-#else
-        if (c0 + 32 < Ncoeff) { load_b(c0 + 32, bnxt); }
-#endif
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             uint4 bh, bl;
-#if defined(RIME_ALM_ABL) && RIME_ALM_ABL == 1
-            bh = make_uint4(__float_as_uint(bcur[ks * 4 + 0].x), __float_as_uint(bcur[ks * 4 + 1].x), __float_as_uint(bcur[ks * 4 + 2].x), __float_as_uint(bcur[ks * 4 + 3].x));
-            bl = make_uint4(__float_as_uint(bcur[ks * 4 + 0].y), __float_as_uint(bcur[ks * 4 + 1].y), __float_as_uint(bcur[ks * 4 + 2].y), __float_as_uint(bcur[ks * 4 + 3].y));
-#else
             split2h(bcur[ks * 4 + 0].x * y_scale, bcur[ks * 4 + 0].y * y_scale, bh.x, bl.x);
             split2h(bcur[ks * 4 + 1].x * y_scale, bcur[ks * 4 + 1].y * y_scale, bh.y, bl.y);
             split2h(bcur[ks * 4 + 2].x * y_scale, bcur[ks * 4 + 2].y * y_scale, bh.z, bl.z);
             split2h(bcur[ks * 4 + 3].x * y_scale, bcur[ks * 4 + 3].y * y_scale, bh.w, bl.w);
-#endif
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
-#if defined(RIME_ALM_ABL) && RIME_ALM_ABL == 2
-                const uint4 ah = make_uint4(m, ks, h, 1), al = make_uint4(ks, m, 2, h);
-#else
                 const int gi = (ks * 2 + h) * ROWS + m * 32 + (lane & 31);
-                const uint4 ah = lds_hi[gi], al = lds_lo[gi];
-#endif
-#if defined(RIME_ALM_ABL) && RIME_ALM_ABL == 3
-                acc[m][0] += __uint_as_float(ah.x ^ bh.x ^ al.y ^ bl.z ^ bh.w ^ bl.x ^ bh.y ^ bh.z ^ bl.y ^ bl.w);
-#else
-                acc[m] = ALM_MFMA(ah, bh, acc[m]);
-                acc[m] = ALM_MFMA(ah, bl, acc[m]);
-                acc[m] = ALM_MFMA(al, bh, acc[m]);
-#endif
+                mfma3(lds_hi[gi], lds_lo[gi], bh, bl, acc[m]);
             }
         }
 #pragma unroll
         for (int u = 0; u < 16; ++u) bcur[u] = bnxt[u];
     }
     RIME_MFMA_SETTLE();
-    const int col = j0 + (lane & 31);
-    if (col < Npix) {
-        const float iy = 1.0f / y_scale;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) out[(size_t)row * Npix + col] = acc[m][e] * inv_scale[row] * iy;
-            }
-    }
+    store_fwd_tile(acc, out, r0, R, Npix, j0 + (lane & 31), lane, inv_scale, y_scale);
 }
 
 // backward: galm[r, c, q] = sum_j gout[r, j] Y[c, j, q] (q ? -1 : +1).  K = pixels (16 per MFMA).
@@ -557,10 +630,8 @@ alm2pix_bwd_f16_kernel(const uint4* __restrict__ g_hi, const uint4* __restrict__
     const int nsteps = (Npix + 15) / 16;
     const int send = nsteps;
     f32x16 accr[MT], acci[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { accr[m][e] = 0.f; acci[m][e] = 0.f; }
+    zero(accr);
+    zero(acci);
 
     float4 yq[8];                                      // this thread's 8 x 16 B of the next Ylm tile
     uint4 ahq[PT], alq[PT];
@@ -583,15 +654,7 @@ alm2pix_bwd_f16_kernel(const uint4* __restrict__ g_hi, const uint4* __restrict__
         }
     };
     auto fetch_a = [&](int s0) {
-#pragma unroll
-        for (int u = 0; u < PT; ++u) {
-            const int i = tid + u * 256;
-            const int row = i % ROWS, g = i / ROWS;    // g = ks * 2 + h
-            const int sg = s0 * 2 + g;
-            const bool ok = i < NG && sg < send * 2;
-            ahq[u] = ok ? g_hi[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
-            alq[u] = ok ? g_lo[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
-        }
+        fetch_granules<ROWS, 2>(g_hi, g_lo, Rpad, r0, s0, send, tid, ahq, alq);
     };
     if (2 * split < send) { fetch_y(2 * split); fetch_a(2 * split); }
     const unsigned char* ymine = y_lds + (wave * 32 + (lane & 31)) * YROW + 64 * h;
@@ -613,43 +676,16 @@ alm2pix_bwd_f16_kernel(const uint4* __restrict__ g_hi, const uint4* __restrict__
 #pragma unroll
             for (int q = 0; q < 4; ++q) y[q] = *reinterpret_cast<const float4*>(ymine + 128 * ks + 16 * q);
             uint4 rh, rl, ih, il;
-            split2h(y[0].x * y_scale, y[0].z * y_scale, rh.x, rl.x);
-            split2h(y[1].x * y_scale, y[1].z * y_scale, rh.y, rl.y);
-            split2h(y[2].x * y_scale, y[2].z * y_scale, rh.z, rl.z);
-            split2h(y[3].x * y_scale, y[3].z * y_scale, rh.w, rl.w);
-            split2h(y[0].y * y_scale, y[0].w * y_scale, ih.x, il.x);
-            split2h(y[1].y * y_scale, y[1].w * y_scale, ih.y, il.y);
-            split2h(y[2].y * y_scale, y[2].w * y_scale, ih.z, il.z);
-            split2h(y[3].y * y_scale, y[3].w * y_scale, ih.w, il.w);
+            split_y4(y, y_scale, rh, rl, ih, il);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const int gi = (ks * 2 + h) * ROWS + m * 32 + (lane & 31);
-                const uint4 ah = lds_hi[gi], al = lds_lo[gi];
-                accr[m] = ALM_MFMA(ah, rh, accr[m]);
-                acci[m] = ALM_MFMA(ah, ih, acci[m]);
-                accr[m] = ALM_MFMA(ah, rl, accr[m]);
-                acci[m] = ALM_MFMA(ah, il, acci[m]);
-                accr[m] = ALM_MFMA(al, rh, accr[m]);
-                acci[m] = ALM_MFMA(al, ih, acci[m]);
+                mfma6(lds_hi[gi], lds_lo[gi], rh, rl, ih, il, accr[m], acci[m]);
             }
         }
     }
     RIME_MFMA_SETTLE();
-    if (c < Ncoeff) {
-        float* dst = part + (size_t)split * R * Ncoeff * 2;
-        const float iy = 1.0f / y_scale;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) {
-                    const float sc = inv_scale[row] * iy;
-                    *reinterpret_cast<float2*>(dst + ((size_t)row * Ncoeff + c) * 2) =
-                        make_float2(accr[m][e] * sc, -acci[m][e] * sc);
-                }
-            }
-    }
+    store_bwd_tile(accr, acci, part + (size_t)split * R * Ncoeff * 2, r0, R, Ncoeff, c, lane, inv_scale, y_scale);
 }
 
 // backward, LDS-DMA form (even Npix): the kernel above is bound by the Ylm bytes it keeps in flight (one 32-KB tile
@@ -699,9 +735,57 @@ template <int MT, int KS, int NSLOT> struct BwdDma {
     static constexpr int TI = KS * (16 + 2 * NGW);     // wave instructions per chunk
     static constexpr int NPW = (TI + 3) / 4;           // per wave
     static constexpr int LDS = NSLOT * SLOT + 1024;    // + the scratch KB of the padding loads
+    static constexpr int AHEAD = NSLOT - 1;            // chunks in flight ahead of the one being read
     static_assert(LDS <= 160 * 1024, "LDS ring too large");
     static_assert(NPW * (NSLOT - 2) < 64, "vmcnt range");
 };
+
+// Workgroups go to the 8 XCDs round-robin by linear id.  The blocks of one pixel split read the SAME gout chunks
+// (and, over row tiles, the same Ylm tile): each XCD takes a contiguous range of the (split, coefficient tile,
+// row tile) order, so the ~32 blocks an XCD holds at a time share a split and the gout stream is served by that
+// XCD's L2 instead of crossing the fabric once per coefficient tile (it was half as many bytes as Ylm itself).
+// The grid is ring_grid() blocks; `valid` is false for the whole of a surplus block, which returns before any barrier.
+struct XcdBlock { bool valid; int split, row_tile, col_tile; };
+
+__device__ __forceinline__ XcdBlock xcd_block(int S, int CT, int RT)
+{
+    const int NB = S * CT * RT, per_xcd = (NB + 7) / 8;
+    const int q = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
+    return {(int)(blockIdx.x / 8) < per_xcd && q < NB, q / (CT * RT), q % RT, (q / RT) % CT};
+}
+
+// ring kernels: wave instruction tg of the chunk's pre-split gout granules, (K step, hi | lo image, KB) = tg, into the
+// slot's granule area at LDS address `gbase`; K steps from `send` on read the zero block.  C: the ring's constants
+template <typename C, int KS>
+__device__ __forceinline__ void issue_gout(int tg, int lane, int s0, int send, const uint4* __restrict__ g_hi,
+                                           const uint4* __restrict__ g_lo, const float* __restrict__ zero16, int Rpad, int r0,
+                                           unsigned gbase)
+{
+    const int ks = KS == 1 ? 0 : tg / (2 * C::NGW), r = KS == 1 ? tg : tg % (2 * C::NGW);    // (one K step: tg < 2 NGW)
+    const int img = r / C::NGW, k = r % C::NGW;
+    const int i = k * 64 + lane;
+    const int row = i % C::ROWS, hh = i / C::ROWS;
+    const int qq = (s0 + ks) * 2 + hh;
+    const uint4* g = img ? g_lo : g_hi;
+    const void* src = s0 + ks < send ? (const void*)&g[(size_t)qq * Rpad + r0 + row] : (const void*)zero16;
+    glds16(src, gbase + (ks * 2 + img) * C::GB + k * 1024);
+}
+
+// A ring step.  C::AHEAD chunks (C::NPW wave instructions per wave each) are in flight; per chunk ONE raw barrier behind a
+// counted wait that leaves the `younger` chunks in flight across it.  After ring_wait the oldest chunk of every wave has
+// landed and everyone is done with the chunk before it, whose slot (`nslot`) the next issue fills; `slot` is the one to read.
+template <typename C> __device__ __forceinline__ void ring_wait(int younger)
+{
+    wait_chunks<C::NPW, C::AHEAD - 1>(younger);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+}
+
+template <typename C> __device__ __forceinline__ void ring_advance(int& slot, int& nslot)
+{
+    slot = slot == C::AHEAD ? 0 : slot + 1;
+    nslot = nslot == C::AHEAD ? 0 : nslot + 1;
+}
 
 template <int MT, int KS, int NSLOT>
 __global__ void __launch_bounds__(256, 1)
@@ -711,20 +795,15 @@ alm2pix_bwd_f16_dma_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
                            int R, int Rpad, int Ncoeff, int Npix, int S, int CT, int RT, float* __restrict__ part)
 {
     using C = BwdDma<MT, KS, NSLOT>;
-    constexpr int ROWS = C::ROWS, AHEAD = NSLOT - 1;
+    constexpr int ROWS = C::ROWS;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned smem_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    // Workgroups go to the 8 XCDs round-robin by linear id.  The blocks of one pixel split read the SAME gout chunks
-    // (and, over row tiles, the same Ylm tile): each XCD takes a contiguous range of the (split, coefficient tile,
-    // row tile) order, so the ~32 blocks an XCD holds at a time share a split and the gout stream is served by that
-    // XCD's L2 instead of crossing the fabric once per coefficient tile (it was half as many bytes as Ylm itself).
-    const int NB = S * CT * RT, per_xcd = (NB + 7) / 8;
-    const int q = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
-    if ((int)(blockIdx.x / 8) >= per_xcd || q >= NB) return;      // whole block, before any barrier
-    const int split = q / (CT * RT);
-    const int r0 = (q % RT) * ROWS;
-    const int cblk = ((q / RT) % CT) * 128;
+    const XcdBlock blk = xcd_block(S, CT, RT);
+    if (!blk.valid) return;                            // whole block, before any barrier
+    const int split = blk.split;
+    const int r0 = blk.row_tile * ROWS;
+    const int cblk = blk.col_tile * 128;
     const int cl = wave * 32 + (lane & 31);            // this lane's coefficient row of the tile
     const int c = cblk + cl;
     const int h = lane >> 5;
@@ -732,10 +811,8 @@ alm2pix_bwd_f16_dma_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
     const int nchunk = (send + KS - 1) / KS;
     const int niter = split < nchunk ? (nchunk - split + S - 1) / S : 0;      // chunks split, split + S, ...
     f32x16 accr[MT], acci[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { accr[m][e] = 0.f; acci[m][e] = 0.f; }
+    zero(accr);
+    zero(acci);
 
     auto issue = [&](int it, int slot) {
         const int s0 = KS * (split + it * S);
@@ -750,30 +827,21 @@ alm2pix_bwd_f16_dma_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
                 const float* src = (cc < Ncoeff && j < Npix) ? Ylm + ((size_t)cc * Npix + j) * 2 : zero16;
                 glds16(src, base + t * 1024);
             } else if (t < C::TI) {
-                const int tg = t - 16 * KS;
-                const int ks = tg / (2 * C::NGW), r = tg % (2 * C::NGW), img = r / C::NGW, k = r % C::NGW;
-                const int i = k * 64 + lane;
-                const int row = i % ROWS, hh = i / ROWS;
-                const int qq = (s0 + ks) * 2 + hh;
-                const uint4* g = img ? g_lo : g_hi;
-                const void* src = s0 + ks < send ? (const void*)&g[(size_t)qq * Rpad + r0 + row] : (const void*)zero16;
-                glds16(src, base + C::YB + (ks * 2 + img) * C::GB + k * 1024);
+                issue_gout<C, KS>(t - 16 * KS, lane, s0, send, g_hi, g_lo, zero16, Rpad, r0, base + C::YB);
             } else {
                 glds16(zero16, smem_addr + NSLOT * C::SLOT);
             }
         }
     };
 #pragma unroll
-    for (int a = 0; a < AHEAD; ++a)
+    for (int a = 0; a < C::AHEAD; ++a)
         if (a < niter) issue(a, a);
     const uint32_t ybase = (uint32_t)cl * (C::GR * 16u);
     const uint32_t sw = (uint32_t)((cl >> (KS == 1 ? 1 : 0)) & (C::GR - 1));
-    int slot = 0, nslot = AHEAD;                       // slot being read; slot the next issue fills
+    int slot = 0, nslot = C::AHEAD;
     for (int it = 0; it < niter; ++it) {
-        wait_chunks<C::NPW, AHEAD - 1>(niter - 1 - it);          // chunk `it` of this wave has landed
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();                  // every wave's part has landed; everyone is done with chunk it - 1
-        if (it + AHEAD < niter) issue(it + AHEAD, nslot);        // into the slot chunk it - 1 occupied
+        ring_wait<C>(niter - 1 - it);
+        if (it + C::AHEAD < niter) issue(it + C::AHEAD, nslot);
         const unsigned char* sl = smem + slot * C::SLOT;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -784,45 +852,17 @@ alm2pix_bwd_f16_dma_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
             for (int qd = 0; qd < 4; ++qd)
                 y[qd] = *reinterpret_cast<const float4*>(sl + ybase + ((((uint32_t)(8 * ks + 4 * h + qd)) ^ sw) * 16u));
             uint4 rh, rl, ih, il;
-            split2h(y[0].x * y_scale, y[0].z * y_scale, rh.x, rl.x);
-            split2h(y[1].x * y_scale, y[1].z * y_scale, rh.y, rl.y);
-            split2h(y[2].x * y_scale, y[2].z * y_scale, rh.z, rl.z);
-            split2h(y[3].x * y_scale, y[3].z * y_scale, rh.w, rl.w);
-            split2h(y[0].y * y_scale, y[0].w * y_scale, ih.x, il.x);
-            split2h(y[1].y * y_scale, y[1].w * y_scale, ih.y, il.y);
-            split2h(y[2].y * y_scale, y[2].w * y_scale, ih.z, il.z);
-            split2h(y[3].y * y_scale, y[3].w * y_scale, ih.w, il.w);
+            split_y4(y, y_scale, rh, rl, ih, il);
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const int gi = h * ROWS + m * 32 + (lane & 31);
-                const uint4 ah = lds_hi[gi], al = lds_lo[gi];
-                accr[m] = ALM_MFMA(ah, rh, accr[m]);
-                acci[m] = ALM_MFMA(ah, ih, acci[m]);
-                accr[m] = ALM_MFMA(ah, rl, accr[m]);
-                acci[m] = ALM_MFMA(ah, il, acci[m]);
-                accr[m] = ALM_MFMA(al, rh, accr[m]);
-                acci[m] = ALM_MFMA(al, ih, acci[m]);
+                mfma6(lds_hi[gi], lds_lo[gi], rh, rl, ih, il, accr[m], acci[m]);
             }
         }
-        slot = slot + 1 == NSLOT ? 0 : slot + 1;
-        nslot = nslot + 1 == NSLOT ? 0 : nslot + 1;
+        ring_advance<C>(slot, nslot);
     }
     RIME_MFMA_SETTLE();
-    if (c < Ncoeff) {
-        float* dst = part + (size_t)split * R * Ncoeff * 2;
-        const float iy = 1.0f / y_scale;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) {
-                    const float sc = inv_scale[row] * iy;
-                    *reinterpret_cast<float2*>(dst + ((size_t)row * Ncoeff + c) * 2) =
-                        make_float2(accr[m][e] * sc, -acci[m][e] * sc);
-                }
-            }
-    }
+    store_bwd_tile(accr, acci, part + (size_t)split * R * Ncoeff * 2, r0, R, Ncoeff, c, lane, inv_scale, y_scale);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -866,8 +906,7 @@ alm_pack_fwd_kernel(const float* __restrict__ Ylm, float y_scale, int Ncoeff, in
         v[2 * q] = y.x * y_scale; v[2 * q + 1] = y.y * y_scale;
     }
     uint4 hi, lo;
-    split2h(v[0], v[1], hi.x, lo.x); split2h(v[2], v[3], hi.y, lo.y);
-    split2h(v[4], v[5], hi.z, lo.z); split2h(v[6], v[7], hi.w, lo.w);
+    split8(v, hi, lo);
     uint4* dst = Yf + ((jt * nsteps + s) * 2) * 64 + lane;
     dst[0] = hi;
     dst[64] = lo;
@@ -889,10 +928,8 @@ alm_pack_bwd_kernel(const float* __restrict__ Ylm, float y_scale, int Ncoeff, in
         re[q] = y.x * y_scale; im[q] = y.y * y_scale;
     }
     uint4 rh, rl, ih, il;
-    split2h(re[0], re[1], rh.x, rl.x); split2h(re[2], re[3], rh.y, rl.y);
-    split2h(re[4], re[5], rh.z, rl.z); split2h(re[6], re[7], rh.w, rl.w);
-    split2h(im[0], im[1], ih.x, il.x); split2h(im[2], im[3], ih.y, il.y);
-    split2h(im[4], im[5], ih.z, il.z); split2h(im[6], im[7], ih.w, il.w);
+    split8(re, rh, rl);
+    split8(im, ih, il);
     uint4* dst = Yb + ((((size_t)ct * nsteps + s) * 4 + w) * 4) * 64 + lane;
     dst[0] = rh; dst[64] = rl; dst[128] = ih; dst[192] = il;
 }
@@ -921,10 +958,7 @@ alm2pix_fwd_packed_kernel(const uint4* __restrict__ a_hi, const uint4* __restric
     const int j0 = (int)(jt * 32);
     const int asteps = (2 * Ncoeff + 15) / 16;         // K steps the A images hold
     f32x16 acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    zero(acc);
     const uint4* ysrc = Yf + (jt * nsteps * 2) * 64 + lane;            // this wave's stream: 2 KB per K step
     uint4 b0[8], b1[8];                                // even / odd chunk: [ks * 2 + (hi | lo)]
     uint4 ahq[PT], alq[PT];
@@ -933,15 +967,7 @@ alm2pix_fwd_packed_kernel(const uint4* __restrict__ a_hi, const uint4* __restric
         for (int u = 0; u < 8; ++u) b[u] = ysrc[(size_t)(s0 * 2 + u) * 64];
     };
     auto fetch_a = [&](int s0) {
-#pragma unroll
-        for (int u = 0; u < PT; ++u) {
-            const int i = tid + u * 256;
-            const int row = i % ROWS, g = i / ROWS;
-            const int sg = s0 * 2 + g;
-            const bool ok = sg < asteps * 2;
-            ahq[u] = ok ? a_hi[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
-            alq[u] = ok ? a_lo[(size_t)sg * Rpad + r0 + row] : make_uint4(0, 0, 0, 0);
-        }
+        fetch_granules<ROWS, 4>(a_hi, a_lo, Rpad, r0, s0, asteps, tid, ahq, alq);
     };
     auto compute = [&](uint4 (&b)[8], int buf, int s_next) {
 #pragma unroll
@@ -949,10 +975,7 @@ alm2pix_fwd_packed_kernel(const uint4* __restrict__ a_hi, const uint4* __restric
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const int gi = (ks * 2 + (lane >> 5)) * ROWS + m * 32 + (lane & 31);
-                const uint4 ah = lds_hi[buf][gi], al = lds_lo[buf][gi];
-                acc[m] = ALM_MFMA(ah, b[2 * ks], acc[m]);
-                acc[m] = ALM_MFMA(ah, b[2 * ks + 1], acc[m]);
-                acc[m] = ALM_MFMA(al, b[2 * ks], acc[m]);
+                mfma3(lds_hi[buf][gi], lds_lo[buf][gi], b[2 * ks], b[2 * ks + 1], acc[m]);
             }
             if (s_next >= 0) {                         // uniform
                 b[2 * ks] = ysrc[(size_t)((s_next + ks) * 2) * 64];
@@ -980,36 +1003,7 @@ alm2pix_fwd_packed_kernel(const uint4* __restrict__ a_hi, const uint4* __restric
         }
     }
     RIME_MFMA_SETTLE();
-    const int col = j0 + (lane & 31);
-    if (col < Npix) {
-        const float iy = 1.0f / y_scale;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) out[((size_t)blockIdx.z * R + row) * Npix + col] = acc[m][e] * inv_scale[row] * iy;
-            }
-    }
-}
-
-// K splits of the packed forward (two 4-wave blocks per CU are resident), each split >= 16 chunks
-static int fwd_packed_splits(int R, int Ncoeff, int Npix, int MT)
-{
-    static long resident = 0;
-    if (resident == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        resident = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? 2L * prop.multiProcessorCount : 512;
-        (void)hipGetLastError();
-    }
-    const long blocks = (long)((Npix + 127) / 128) * ((R + MT * 32 - 1) / (MT * 32));
-    const int nchunk = pk_fwd_steps(Ncoeff) / PK_FWD_CHUNK;
-    // measured at the C3 shape (384 blocks of 263 chunks, 512 resident): S 1 / 2 / 3 / 4 / 6 -> 0.911 / 0.853 / 0.890 /
-    // 0.871 / 0.898 ms including the reduction of the partial planes: enough blocks for 1.5 resident grids, no more
-    int best = (int)std::min<long>(4, std::max<long>(1, (3 * resident / 2 + blocks - 1) / blocks));
-    while (best > 1 && nchunk / best < 16) --best;
-    if (const char* e = getenv("RIME_ALM_FWD_SPLITS")) { const int v = atoi(e); if (v >= 1 && v <= 8 && nchunk / v >= 1) best = v; }   // lab
-    return best;
+    store_fwd_tile(acc, out + (size_t)blockIdx.z * R * Npix, r0, R, Npix, j0 + (lane & 31), lane, inv_scale, y_scale);
 }
 
 // backward on the packed copy: the LDS-DMA ring of alm2pix_bwd_f16_dma_kernel with the chunk's Ylm tile replaced by
@@ -1025,26 +1019,23 @@ alm2pix_bwd_packed_kernel(const uint4* __restrict__ g_hi, const uint4* __restric
 {
     constexpr int KS = PK_BWD_KS;
     using C = BwdDma<MT, KS, NSLOT>;
-    constexpr int ROWS = C::ROWS, AHEAD = NSLOT - 1;
+    constexpr int ROWS = C::ROWS;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned smem_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    const int NB = S * CT * RT, per_xcd = (NB + 7) / 8;
-    const int q = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
-    if ((int)(blockIdx.x / 8) >= per_xcd || q >= NB) return;      // whole block, before any barrier
-    const int split = q / (CT * RT);
-    const int r0 = (q % RT) * ROWS;
-    const int ct = (q / RT) % CT;
+    const XcdBlock blk = xcd_block(S, CT, RT);
+    if (!blk.valid) return;                            // whole block, before any barrier
+    const int split = blk.split;
+    const int r0 = blk.row_tile * ROWS;
+    const int ct = blk.col_tile;
     const int c = ct * 128 + wave * 32 + (lane & 31);
     const int h = lane >> 5;
     const int send = (Npix + 15) / 16;                 // K steps the gout images hold
     const int nchunk = nsteps / KS;
     const int niter = split < nchunk ? (nchunk - split + S - 1) / S : 0;
     f32x16 accr[MT], acci[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { accr[m][e] = 0.f; acci[m][e] = 0.f; }
+    zero(accr);
+    zero(acci);
 
     const uint4* ytile = Yb + (size_t)ct * nsteps * 16 * 64 + lane;
     auto issue = [&](int it, int slot) {
@@ -1056,28 +1047,19 @@ alm2pix_bwd_packed_kernel(const uint4* __restrict__ g_hi, const uint4* __restric
             if (t < 16 * KS) {                         // KB number t of the chunk's 32-KB run: (ks, w, plane) = t
                 glds16(ytile + ((size_t)s0 * 16 + t) * 64, base + t * 1024);
             } else if (t < C::TI) {
-                const int tg = t - 16 * KS;
-                const int ks = tg / (2 * C::NGW), r = tg % (2 * C::NGW), img = r / C::NGW, k = r % C::NGW;
-                const int i = k * 64 + lane;
-                const int row = i % ROWS, hh = i / ROWS;
-                const int qq = (s0 + ks) * 2 + hh;
-                const uint4* g = img ? g_lo : g_hi;
-                const void* src = s0 + ks < send ? (const void*)&g[(size_t)qq * Rpad + r0 + row] : (const void*)zero16;
-                glds16(src, base + C::YB + (ks * 2 + img) * C::GB + k * 1024);
+                issue_gout<C, KS>(t - 16 * KS, lane, s0, send, g_hi, g_lo, zero16, Rpad, r0, base + C::YB);
             } else {
                 glds16(zero16, smem_addr + NSLOT * C::SLOT);
             }
         }
     };
 #pragma unroll
-    for (int a = 0; a < AHEAD; ++a)
+    for (int a = 0; a < C::AHEAD; ++a)
         if (a < niter) issue(a, a);
-    int slot = 0, nslot = AHEAD;
+    int slot = 0, nslot = C::AHEAD;
     for (int it = 0; it < niter; ++it) {
-        wait_chunks<C::NPW, AHEAD - 1>(niter - 1 - it);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (it + AHEAD < niter) issue(it + AHEAD, nslot);
+        ring_wait<C>(niter - 1 - it);
+        if (it + C::AHEAD < niter) issue(it + C::AHEAD, nslot);
         const unsigned char* sl = smem + slot * C::SLOT;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -1088,34 +1070,13 @@ alm2pix_bwd_packed_kernel(const uint4* __restrict__ g_hi, const uint4* __restric
 #pragma unroll
             for (int m = 0; m < MT; ++m) {
                 const int gi = h * ROWS + m * 32 + (lane & 31);
-                const uint4 ah = lds_hi[gi], al = lds_lo[gi];
-                accr[m] = ALM_MFMA(ah, rh, accr[m]);
-                acci[m] = ALM_MFMA(ah, ih, acci[m]);
-                accr[m] = ALM_MFMA(ah, rl, accr[m]);
-                acci[m] = ALM_MFMA(ah, il, acci[m]);
-                accr[m] = ALM_MFMA(al, rh, accr[m]);
-                acci[m] = ALM_MFMA(al, ih, acci[m]);
+                mfma6(lds_hi[gi], lds_lo[gi], rh, rl, ih, il, accr[m], acci[m]);
             }
         }
-        slot = slot + 1 == NSLOT ? 0 : slot + 1;
-        nslot = nslot + 1 == NSLOT ? 0 : nslot + 1;
+        ring_advance<C>(slot, nslot);
     }
     RIME_MFMA_SETTLE();
-    if (c < Ncoeff) {
-        float* dst = part + (size_t)split * R * Ncoeff * 2;
-        const float iy = 1.0f / y_scale;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) {
-                    const float sc = inv_scale[row] * iy;
-                    *reinterpret_cast<float2*>(dst + ((size_t)row * Ncoeff + c) * 2) =
-                        make_float2(accr[m][e] * sc, -acci[m][e] * sc);
-                }
-            }
-    }
+    store_bwd_tile(accr, acci, part + (size_t)split * R * Ncoeff * 2, r0, R, Ncoeff, c, lane, inv_scale, y_scale);
 }
 
 // Backward on the packed copy, 8-wave form (MT = 4): one block = 256 coefficients (two packed coefficient tiles) x 128 rows.
@@ -1132,6 +1093,7 @@ struct BwdDma8 {
     static constexpr int TI = 4 * NW + 2 * NGW;        // 40
     static constexpr int NPW = TI / NW;                // 5
     static constexpr int LDS = NSLOT * SLOT;
+    static constexpr int AHEAD = NSLOT - 1;
     static_assert(TI % NW == 0 && LDS <= 160 * 1024 && NPW * (NSLOT - 2) < 64, "ring shape");
 };
 
@@ -1142,26 +1104,23 @@ alm2pix_bwd_packed8_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
                            int R, int Rpad, int Ncoeff, int Npix, int nsteps, int S, int CT2, int RT, float* __restrict__ part)
 {
     using C = BwdDma8;
-    constexpr int MT = 4, ROWS = C::ROWS, AHEAD = C::NSLOT - 1;
+    constexpr int MT = 4, ROWS = C::ROWS;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned smem_addr = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-    const int NB = S * CT2 * RT, per_xcd = (NB + 7) / 8;
-    const int q = (int)(blockIdx.x % 8) * per_xcd + (int)(blockIdx.x / 8);
-    if ((int)(blockIdx.x / 8) >= per_xcd || q >= NB) return;
-    const int split = q / (CT2 * RT);
-    const int r0 = (q % RT) * ROWS;
-    const int ct0 = 2 * ((q / RT) % CT2);              // first of this block's two packed coefficient tiles
+    const XcdBlock blk = xcd_block(S, CT2, RT);
+    if (!blk.valid) return;                            // whole block, before any barrier
+    const int split = blk.split;
+    const int r0 = blk.row_tile * ROWS;
+    const int ct0 = 2 * blk.col_tile;                  // first of this block's two packed coefficient tiles
     const int c = ct0 * 128 + wave * 32 + (lane & 31);
     const int h = lane >> 5;
     const int send = (Npix + 15) / 16;
     const int nchunk = nsteps;                         // one K step per chunk
     const int niter = split < nchunk ? (nchunk - split + S - 1) / S : 0;
     f32x16 accr[MT], acci[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { accr[m][e] = 0.f; acci[m][e] = 0.f; }
+    zero(accr);
+    zero(acci);
 
     const uint4* ytile = Yb + (size_t)ct0 * nsteps * 16 * 64 + lane;
     const size_t ct_stride = (size_t)nsteps * 16 * 64;                 // uint4 elements between packed coefficient tiles
@@ -1174,26 +1133,17 @@ alm2pix_bwd_packed8_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
             if (t < 4 * C::NW) {                       // KB number t of the chunk's Ylm: (tile half, wave, plane)
                 glds16(ytile + (size_t)(t >> 4) * ct_stride + ((size_t)s0 * 16 + (t & 15)) * 64, base + t * 1024);
             } else {
-                const int tg = t - 4 * C::NW;
-                const int img = tg / C::NGW, k = tg % C::NGW;
-                const int i = k * 64 + lane;
-                const int row = i % ROWS, hh = i / ROWS;
-                const int qq = s0 * 2 + hh;
-                const uint4* g = img ? g_lo : g_hi;
-                const void* src = s0 < send ? (const void*)&g[(size_t)qq * Rpad + r0 + row] : (const void*)zero16;
-                glds16(src, base + C::YB + img * C::GB + k * 1024);
+                issue_gout<C, 1>(t - 4 * C::NW, lane, s0, send, g_hi, g_lo, zero16, Rpad, r0, base + C::YB);
             }
         }
     };
 #pragma unroll
-    for (int a = 0; a < AHEAD; ++a)
+    for (int a = 0; a < C::AHEAD; ++a)
         if (a < niter) issue(a, a);
-    int slot = 0, nslot = AHEAD;
+    int slot = 0, nslot = C::AHEAD;
     for (int it = 0; it < niter; ++it) {
-        wait_chunks<C::NPW, AHEAD - 1>(niter - 1 - it);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (it + AHEAD < niter) issue(it + AHEAD, nslot);
+        ring_wait<C>(niter - 1 - it);
+        if (it + C::AHEAD < niter) issue(it + C::AHEAD, nslot);
         const unsigned char* sl = smem + slot * C::SLOT;
         const uint4* lds_hi = reinterpret_cast<const uint4*>(sl + C::YB);
         const uint4* lds_lo = reinterpret_cast<const uint4*>(sl + C::YB + C::GB);
@@ -1202,33 +1152,12 @@ alm2pix_bwd_packed8_kernel(const uint4* __restrict__ g_hi, const uint4* __restri
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             const int gi = h * ROWS + m * 32 + (lane & 31);
-            const uint4 ah = lds_hi[gi], al = lds_lo[gi];
-            accr[m] = ALM_MFMA(ah, rh, accr[m]);
-            acci[m] = ALM_MFMA(ah, ih, acci[m]);
-            accr[m] = ALM_MFMA(ah, rl, accr[m]);
-            acci[m] = ALM_MFMA(ah, il, acci[m]);
-            accr[m] = ALM_MFMA(al, rh, accr[m]);
-            acci[m] = ALM_MFMA(al, ih, acci[m]);
+            mfma6(lds_hi[gi], lds_lo[gi], rh, rl, ih, il, accr[m], acci[m]);
         }
-        slot = slot + 1 == C::NSLOT ? 0 : slot + 1;
-        nslot = nslot + 1 == C::NSLOT ? 0 : nslot + 1;
+        ring_advance<C>(slot, nslot);
     }
     RIME_MFMA_SETTLE();
-    if (c < Ncoeff) {
-        float* dst = part + (size_t)split * R * Ncoeff * 2;
-        const float iy = 1.0f / y_scale;
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = r0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                if (row < R) {
-                    const float sc = inv_scale[row] * iy;
-                    *reinterpret_cast<float2*>(dst + ((size_t)row * Ncoeff + c) * 2) =
-                        make_float2(accr[m][e] * sc, -acci[m][e] * sc);
-                }
-            }
-    }
+    store_bwd_tile(accr, acci, part + (size_t)split * R * Ncoeff * 2, r0, R, Ncoeff, c, lane, inv_scale, y_scale);
 }
 
 __global__ void alm_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, size_t len, int S)
@@ -1242,6 +1171,65 @@ __global__ void alm_reduce_kernel(const float* __restrict__ part, float* __restr
 
 // row tiles of 32 per block of every matrix-core kernel here
 static int row_mt(int R) { return R > 64 ? 4 : (R > 32 ? 2 : 1); }
+
+// f(std::integral_constant<int, MT>): the one place a run-time MT picks a kernel instantiation
+template <typename F> static auto with_mt(int MT, F f)
+{
+    if (MT == 4) return f(std::integral_constant<int, 4>{});
+    if (MT == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 1>{});
+}
+
+// compute units of the calling thread's device (read once); 0 without a device: every planner has its own fallback
+static long cu_count()
+{
+    static long cache = -1;
+    if (cache < 0) {
+        int dev = 0; hipDeviceProp_t prop;
+        cache = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
+        (void)hipGetLastError();
+    }
+    return cache;
+}
+
+// Launch of a kernel with more dynamic LDS than the default limit.  The attribute belongs to the (function, device)
+// pair: remembered per kernel instantiation and device of the calling thread.
+template <auto Kernel, typename... Args>
+static hipError_t launch_dynamic_lds(dim3 grid, dim3 block, int lds, hipStream_t st, Args... args)
+{
+    static unsigned long long configured = 0ull;
+    int devid = 0;
+    if (hipGetDevice(&devid) != hipSuccess) devid = 0;
+    const unsigned long long bit = 1ull << (devid & 63);
+    if (!(configured & bit)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) return e;
+        configured |= bit;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return hipSuccess;
+}
+
+static void reduce_planes(const float* part, float* out, size_t len, int S, hipStream_t st)
+{
+    if (S <= 1) return;
+    int nb = (int)std::min<size_t>((len + 255) / 256, 2048);
+    hipLaunchKernelGGL(alm_reduce_kernel, dim3(nb), dim3(256), 0, st, part, out, len, S);
+}
+
+// K splits of the packed forward (two 4-wave blocks per CU are resident), each split >= 16 chunks
+static int fwd_packed_splits(int R, int Ncoeff, int Npix, int MT)
+{
+    const long resident = cu_count() ? 2 * cu_count() : 512;
+    const long blocks = (long)((Npix + 127) / 128) * ((R + MT * 32 - 1) / (MT * 32));
+    const int nchunk = pk_fwd_steps(Ncoeff) / PK_FWD_CHUNK;
+    // measured at the C3 shape (384 blocks of 263 chunks, 512 resident): S 1 / 2 / 3 / 4 / 6 -> 0.911 / 0.853 / 0.890 /
+    // 0.871 / 0.898 ms including the reduction of the partial planes: enough blocks for 1.5 resident grids, no more
+    int best = (int)std::min<long>(4, std::max<long>(1, (3 * resident / 2 + blocks - 1) / blocks));
+    while (best > 1 && nchunk / best < 16) --best;
+    if (const char* e = getenv("RIME_ALM_FWD_SPLITS")) { const int v = atoi(e); if (v >= 1 && v <= 8 && nchunk / v >= 1) best = v; }   // lab
+    return best;
+}
 
 static int bwd_splits(int R, int Ncoeff, int Npix)
 {
@@ -1261,24 +1249,16 @@ struct SplitPlan {
     int S, steps_per_split;          // backward only: pixel splits
 };
 
-template <int MT> __global__ void alm2pix_bwd_f16_kernel(const uint4*, const uint4*, const float*, const float*, float,
-                                                         int, int, int, int, int, float*);
-
 // blocks of the f16-split backward kernel the chip holds at once (occupancy query, cached per shape)
 static long bwd_resident_blocks(int MT)
 {
     static long cache[5] = {0, 0, 0, 0, 0};
     if (cache[MT] == 0) {
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipGetDeviceProperties(&prop, dev);
-        if (e == hipSuccess) {
-            if (MT == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alm2pix_bwd_f16_kernel<4>, 256, 0);
-            else if (MT == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alm2pix_bwd_f16_kernel<2>, 256, 0);
-            else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alm2pix_bwd_f16_kernel<1>, 256, 0);
-        }
-        cache[MT] = (e == hipSuccess && per_cu > 0) ? (long)per_cu * prop.multiProcessorCount : 512;
+        int per_cu = 0;
+        const bool ok = cu_count() && with_mt(MT, [&](auto mt) {
+            return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, alm2pix_bwd_f16_kernel<decltype(mt)::value>, 256, 0);
+        }) == hipSuccess;
+        cache[MT] = (ok && per_cu > 0) ? (long)per_cu * cu_count() : 512;
         (void)hipGetLastError();
     }
     return cache[MT];
@@ -1294,16 +1274,7 @@ static bool bwd_use_dma(int Npix)
 }
 
 // the LDS-DMA kernel's ring (3 slots of 32 KB Ylm + the gout granules) leaves room for one block per CU
-static long bwd_dma_resident_blocks()
-{
-    static long cache = 0;
-    if (cache == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        cache = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-        (void)hipGetLastError();
-    }
-    return cache;
-}
+static long bwd_dma_resident_blocks() { return cu_count() ? cu_count() : 256; }
 
 static SplitPlan split_plan(int R, int K, int Ncoeff, bool backward, int dma = -1)      // dma: -1 auto, 1 the ring kernels
 {
@@ -1357,157 +1328,112 @@ static bool split_long_rows(const SplitPlan& p, int R, int L)
     return p.Rpad % 64 == 0 && (long)R * L >= (1L << 20);
 }
 
-static void launch_split_rows(const float* X, int R, int L, const SplitPlan& p, int neg_odd, void* workspace,
-                              hipStream_t st, uint4*& hi, uint4*& lo, float*& inv)
-{
-    hi = (uint4*)workspace;
-    lo = (uint4*)((char*)workspace + p.img_bytes);
-    inv = (float*)((char*)workspace + 2 * p.img_bytes);
-    unsigned int* rowmax = (unsigned int*)(inv + p.Rpad);
-    const int nseg = (2 * p.nsteps * 8 + SPLIT_SEG - 1) / SPLIT_SEG;
-    if (split_long_rows(p, R, L)) {
-        // `rowmax` doubles as the scale array
-        float* scale = reinterpret_cast<float*>(rowmax);
-        (void)hipMemsetAsync((char*)rowmax + (size_t)p.Rpad * sizeof(unsigned int), 0, 64, st);     // the zero granule
-        hipLaunchKernelGGL(row_scale_alm_kernel, dim3(p.Rpad), dim3(256), 0, st, X, R, L, scale, inv);
-        hipLaunchKernelGGL(split_rows_tiled_kernel, dim3((2 * p.nsteps + 31) / 32, p.Rpad / 64), dim3(256), 0, st, X, R, L,
-                           p.Rpad, neg_odd, scale, hi, lo);
-        return;
-    }
-    (void)hipMemsetAsync(rowmax, 0, (size_t)p.Rpad * sizeof(unsigned int) + 64, st);     // + the zero granule behind it
-    hipLaunchKernelGGL(row_absmax_kernel, dim3(R, (L + SPLIT_SEG - 1) / SPLIT_SEG), dim3(256), 0, st, X, R, L, rowmax);
-    hipLaunchKernelGGL(split_rows_kernel, dim3(p.Rpad, std::max(1, nseg)), dim3(256), 0, st, X, R, L, p.Rpad,
-                       neg_odd, rowmax, hi, lo, inv);
-}
-
-template <int MT, int KS, int NSLOT>
-static hipError_t launch_bwd_dma(dim3 grid, hipStream_t st, const uint4* hi, const uint4* lo, const float* inv, const float* Y,
-                                 const float* zero16, float ys, int R, int Rpad, int Ncoeff, int Npix, int S, float* part)
-{
-    const int CT = (int)grid.y, RT = (int)grid.z;
-    const int NB = S * CT * RT;
-    grid = dim3(8 * ((NB + 7) / 8));
-    constexpr int LDS = BwdDma<MT, KS, NSLOT>::LDS;
-    // the attribute belongs to the (function, device) pair: remembered per device of the calling thread
-    static unsigned long long configured = 0ull;
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess) devid = 0;
-    const unsigned long long bit = 1ull << (devid & 63);
-    if (!(configured & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&alm2pix_bwd_f16_dma_kernel<MT, KS, NSLOT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        configured |= bit;
-    }
-    hipLaunchKernelGGL((alm2pix_bwd_f16_dma_kernel<MT, KS, NSLOT>), grid, dim3(256), LDS, st, hi, lo, inv, Y, zero16, ys, R, Rpad,
-                       Ncoeff, Npix, S, CT, RT, part);
-    return hipSuccess;
-}
-
-template <int MT, int NSLOT>
-static hipError_t launch_bwd_packed(dim3 grid, hipStream_t st, const uint4* hi, const uint4* lo, const float* inv, const uint4* Yb,
-                                    const float* zero16, float ys, int R, int Rpad, int Ncoeff, int Npix, int nsteps, int S, float* part)
-{
-    const int CT = (int)grid.y, RT = (int)grid.z;
-    const int NB = S * CT * RT;
-    grid = dim3(8 * ((NB + 7) / 8));
-    constexpr int LDS = BwdDma<MT, PK_BWD_KS, NSLOT>::LDS;
-    static unsigned long long configured = 0ull;
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess) devid = 0;
-    const unsigned long long bit = 1ull << (devid & 63);
-    if (!(configured & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&alm2pix_bwd_packed_kernel<MT, NSLOT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        configured |= bit;
-    }
-    hipLaunchKernelGGL((alm2pix_bwd_packed_kernel<MT, NSLOT>), grid, dim3(256), LDS, st, hi, lo, inv, Yb, zero16, ys, R, Rpad,
-                       Ncoeff, Npix, nsteps, S, CT, RT, part);
-    return hipSuccess;
-}
-
 static size_t split_ws_bytes(const SplitPlan& p)
 {
     return 2 * p.img_bytes + (size_t)p.Rpad * (sizeof(float) + sizeof(unsigned int)) + 64;    // 64: a zero granule
 }
 
 // RIME_ALM_BWD_WIDE=0 keeps the 4-wave ring kernel of the packed backward above 64 rows (read once)
-static bool bwd_packed_wide(int R)
+static bool bwd_packed_wide()
 {
     static int env = -1;
     if (env < 0) { const char* e = getenv("RIME_ALM_BWD_WIDE"); env = (e && e[0] == '0') ? 0 : 1; }
-    return env == 1 && R > 64;
+    return env == 1;
 }
 
-// The plan of one transform: what the four entry points below launch and what rime_alm2pix_plan reports.
+// The plan of one transform: what the four entry points below launch and check their workspace against, and what
+// rime_alm2pix_plan and the two workspace queries report.
 struct AlmPlan {
     int family, MT, row_tiles, col_tiles, S, long_rows;
+    size_t ws_bytes;                 // workspace: the split images (f16-split families) + the partial planes
     SplitPlan p;                     // the f16-split families only
 };
 
-static AlmPlan plan_fwd(int dtype, double y_scale, int R, int Ncoeff, int Npix)
+// the families without a row split: `rows` x `cols` of the output per block
+static AlmPlan plan_plain(int family, int MT, int R, int rows, int N, int cols)
 {
     AlmPlan a{};
-    a.S = 1;
-    if (dtype == RIME_F32 && y_scale > 0) {
-        a.p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
-        a.family = RIME_ALM_F16_REG; a.MT = a.p.MT;
-        a.col_tiles = (Npix + 127) / 128; a.row_tiles = a.p.Rpad / (a.p.MT * 32);
-        a.long_rows = split_long_rows(a.p, R, 2 * Ncoeff);
-    } else if (dtype == RIME_F32) {
-        a.family = RIME_ALM_F32_MFMA; a.MT = row_mt(R);
-        a.col_tiles = (Npix + 127) / 128; a.row_tiles = (R + a.MT * 32 - 1) / (a.MT * 32);
-    } else {
-        a.family = RIME_ALM_F64_VALU; a.MT = 0;
-        a.col_tiles = (Npix + 255) / 256; a.row_tiles = (R + 15) / 16;
+    a.family = family; a.MT = MT; a.S = 1;
+    a.row_tiles = (R + rows - 1) / rows; a.col_tiles = (N + cols - 1) / cols;
+    return a;
+}
+
+// the f16-split families: K = 2 Ncoeff (forward) or Npix (backward), `cols` output columns per block; `dma` as in split_plan
+static AlmPlan plan_f16(int family, int R, int Ncoeff, int Npix, bool backward, int dma, int cols)
+{
+    AlmPlan a{};
+    const int K = backward ? Npix : 2 * Ncoeff;
+    a.p = split_plan(R, K, Ncoeff, backward, dma);
+    a.family = family; a.MT = a.p.MT; a.S = a.p.S;
+    a.row_tiles = a.p.Rpad / (a.p.MT * 32); a.col_tiles = ((backward ? Ncoeff : Npix) + cols - 1) / cols;
+    a.long_rows = split_long_rows(a.p, R, K);
+    a.ws_bytes = split_ws_bytes(a.p) + (backward ? (size_t)a.S * R * Ncoeff * 2 * sizeof(float) : 0);
+    return a;
+}
+
+// packed: 0 Ylm as it is, 1 the packed copy
+static AlmPlan plan_fwd(int dtype, double y_scale, int packed, int R, int Ncoeff, int Npix)
+{
+    if (dtype != RIME_F32) return plan_plain(RIME_ALM_F64_VALU, 0, R, 16, Npix, 256);
+    if (!(y_scale > 0)) return plan_plain(RIME_ALM_F32_MFMA, row_mt(R), R, row_mt(R) * 32, Npix, 128);
+    AlmPlan a = plan_f16(packed ? RIME_ALM_PACKED4 : RIME_ALM_F16_REG, R, Ncoeff, Npix, false, -1, 128);
+    if (packed) {
+        a.S = fwd_packed_splits(R, Ncoeff, Npix, a.MT);
+        if (a.S > 1) a.ws_bytes += (size_t)a.S * R * Npix * sizeof(float);
     }
     return a;
 }
 
-static AlmPlan plan_bwd(int dtype, double y_scale, int R, int Ncoeff, int Npix)
+// wide8: the packed copy goes to the 8-wave ring where it applies (above 64 rows)
+static AlmPlan plan_bwd(int dtype, double y_scale, int packed, int R, int Ncoeff, int Npix, bool wide8 = bwd_packed_wide())
 {
-    AlmPlan a{};
-    a.S = 1;
-    if (dtype == RIME_F32 && y_scale > 0) {
-        a.p = split_plan(R, Npix, Ncoeff, true);
-        a.family = bwd_use_dma(Npix) ? RIME_ALM_F16_DMA : RIME_ALM_F16_REG; a.MT = a.p.MT;
-        a.col_tiles = (Ncoeff + 127) / 128; a.row_tiles = a.p.Rpad / (a.p.MT * 32);
-        a.S = a.p.S;
-        a.long_rows = split_long_rows(a.p, R, Npix);
-    } else if (dtype == RIME_F32) {
-        a.family = RIME_ALM_F32_MFMA; a.MT = row_mt(R);
-        a.col_tiles = (Ncoeff + 15) / 16; a.row_tiles = (R + a.MT * 32 - 1) / (a.MT * 32);
+    if (dtype != RIME_F32) return plan_plain(RIME_ALM_F64_VALU, 0, R, 8, Ncoeff, 4);
+    if (!(y_scale > 0)) {
+        AlmPlan a = plan_plain(RIME_ALM_F32_MFMA, row_mt(R), R, row_mt(R) * 32, Ncoeff, 16);
         a.S = bwd_splits(R, Ncoeff, Npix);
-    } else {
-        a.family = RIME_ALM_F64_VALU; a.MT = 0;
-        a.col_tiles = (Ncoeff + 3) / 4; a.row_tiles = (R + 7) / 8;
+        if (a.S > 1) a.ws_bytes = (size_t)a.S * R * Ncoeff * 2 * sizeof(float);
+        return a;
     }
-    return a;
+    if (!packed) return plan_f16(bwd_use_dma(Npix) ? RIME_ALM_F16_DMA : RIME_ALM_F16_REG, R, Ncoeff, Npix, true, -1, 128);
+    const bool wide = wide8 && R > 64;
+    return plan_f16(wide ? RIME_ALM_PACKED8 : RIME_ALM_PACKED4, R, Ncoeff, Npix, true, wide ? 2 : 1, wide ? 256 : 128);
 }
 
-static AlmPlan plan_fwd_packed(int R, int Ncoeff, int Npix)
-{
-    AlmPlan a{};
-    a.p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
-    a.family = RIME_ALM_PACKED4; a.MT = a.p.MT;
-    a.col_tiles = (Npix + 127) / 128; a.row_tiles = a.p.Rpad / (a.p.MT * 32);
-    a.S = fwd_packed_splits(R, Ncoeff, Npix, a.p.MT);
-    a.long_rows = split_long_rows(a.p, R, 2 * Ncoeff);
-    return a;
-}
+// the linear grid of the ring kernels (xcd_block): whole rounds of the 8 XCDs
+static dim3 ring_grid(const AlmPlan& a) { return dim3(8 * ((a.S * a.col_tiles * a.row_tiles + 7) / 8)); }
 
-static AlmPlan plan_bwd_packed(int R, int Ncoeff, int Npix)
+// The row operand of an f16-split transform in the caller's workspace: the hi / lo images, the row scales, the zero granule
+// the ring kernels read beyond the matrix, and where the kernel writes -- `out`, or S partial planes behind the images.
+struct Staged { uint4 *hi, *lo; float* inv; const float* zero16; float* part; };
+
+// part == nullptr: the workspace is smaller than the plan's figure (nothing launched)
+static Staged stage_rows(const float* X, int R, int L, const AlmPlan& a, int neg_odd, void* workspace, size_t bytes, void* out,
+                         hipStream_t st)
 {
-    AlmPlan a{};
-    const bool wide = bwd_packed_wide(R);
-    a.p = split_plan(R, Npix, Ncoeff, true, wide ? 2 : 1);
-    a.family = wide ? RIME_ALM_PACKED8 : RIME_ALM_PACKED4; a.MT = a.p.MT;
-    a.col_tiles = wide ? (Ncoeff + 255) / 256 : (Ncoeff + 127) / 128;
-    a.row_tiles = a.p.Rpad / (a.p.MT * 32);
-    a.S = a.p.S;
-    a.long_rows = split_long_rows(a.p, R, Npix);
-    return a;
+    const SplitPlan& p = a.p;
+    if (!workspace || bytes < a.ws_bytes) return Staged{};
+    Staged s;
+    s.hi = (uint4*)workspace;
+    s.lo = (uint4*)((char*)workspace + p.img_bytes);
+    s.inv = (float*)((char*)workspace + 2 * p.img_bytes);
+    s.zero16 = (const float*)((char*)workspace + split_ws_bytes(p) - 64);
+    s.part = a.S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)out;
+    unsigned int* rowmax = (unsigned int*)(s.inv + p.Rpad);
+    const int nseg = (2 * p.nsteps * 8 + SPLIT_SEG - 1) / SPLIT_SEG;
+    if (a.long_rows) {
+        // `rowmax` doubles as the scale array
+        float* scale = reinterpret_cast<float*>(rowmax);
+        (void)hipMemsetAsync((char*)rowmax + (size_t)p.Rpad * sizeof(unsigned int), 0, 64, st);     // the zero granule
+        hipLaunchKernelGGL(row_scale_alm_kernel, dim3(p.Rpad), dim3(256), 0, st, X, R, L, scale, s.inv);
+        hipLaunchKernelGGL(split_rows_tiled_kernel, dim3((2 * p.nsteps + 31) / 32, p.Rpad / 64), dim3(256), 0, st, X, R, L,
+                           p.Rpad, neg_odd, scale, s.hi, s.lo);
+        return s;
+    }
+    (void)hipMemsetAsync(rowmax, 0, (size_t)p.Rpad * sizeof(unsigned int) + 64, st);     // + the zero granule behind it
+    hipLaunchKernelGGL(row_absmax_kernel, dim3(R, (L + SPLIT_SEG - 1) / SPLIT_SEG), dim3(256), 0, st, X, R, L, rowmax);
+    hipLaunchKernelGGL(split_rows_kernel, dim3(p.Rpad, std::max(1, nseg)), dim3(256), 0, st, X, R, L, p.Rpad,
+                       neg_odd, rowmax, s.hi, s.lo, s.inv);
+    return s;
 }
 
 } // namespace rime
@@ -1519,8 +1445,7 @@ extern "C" int rime_alm2pix_plan(int dtype, double y_scale, int R, int Ncoeff, i
     if (!plan || (dtype != RIME_F32 && dtype != RIME_F64) || !(y_scale >= 0) || R <= 0 || Ncoeff <= 0 || Npix <= 0 ||
         (direction != 0 && direction != 1) || (packed != 0 && packed != 1)) return RIME_EINVAL;
     if (packed && (dtype != RIME_F32 || !(y_scale > 0))) return RIME_EINVAL;
-    const AlmPlan a = packed ? (direction ? plan_bwd_packed(R, Ncoeff, Npix) : plan_fwd_packed(R, Ncoeff, Npix))
-                             : (direction ? plan_bwd(dtype, y_scale, R, Ncoeff, Npix) : plan_fwd(dtype, y_scale, R, Ncoeff, Npix));
+    const AlmPlan a = direction ? plan_bwd(dtype, y_scale, packed, R, Ncoeff, Npix) : plan_fwd(dtype, y_scale, packed, R, Ncoeff, Npix);
     plan[0] = a.family; plan[1] = a.MT; plan[2] = a.row_tiles; plan[3] = a.col_tiles; plan[4] = a.S; plan[5] = a.long_rows;
     return RIME_OK;
 }
@@ -1528,10 +1453,9 @@ extern "C" int rime_alm2pix_plan(int dtype, double y_scale, int R, int Ncoeff, i
 extern "C" size_t rime_alm2pix_fwd_workspace(int dtype, int R, int Ncoeff, int Npix)
 {
     if (dtype != RIME_F32 || R <= 0 || Ncoeff <= 0) return 0;
-    const SplitPlan p = split_plan(R, 2 * Ncoeff, Ncoeff, false);
-    if (Npix <= 0) return split_ws_bytes(p);
-    const int S = fwd_packed_splits(R, Ncoeff, Npix, p.MT);                   // rime_alm2pix_fwd_packed: K-split partial planes
-    return split_ws_bytes(p) + (S > 1 ? (size_t)S * R * Npix * sizeof(float) : 0);
+    // one buffer for rime_alm2pix_fwd and rime_alm2pix_fwd_packed (the K-split partial planes; none without a pixel count)
+    return std::max(plan_fwd(RIME_F32, 1.0, 0, R, Ncoeff, Npix).ws_bytes,
+                    Npix > 0 ? plan_fwd(RIME_F32, 1.0, 1, R, Ncoeff, Npix).ws_bytes : 0);
 }
 
 extern "C" int rime_alm2pix_fwd(int dtype, const void* alm, const void* Ylm, double y_scale, int R, int Ncoeff,
@@ -1540,24 +1464,20 @@ extern "C" int rime_alm2pix_fwd(int dtype, const void* alm, const void* Ylm, dou
     if (!alm || !Ylm || !out || R <= 0 || Ncoeff <= 0 || Npix <= 0 || y_scale < 0) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
-    const AlmPlan pl = plan_fwd(dtype, y_scale, R, Ncoeff, Npix);
+    const AlmPlan pl = plan_fwd(dtype, y_scale, 0, R, Ncoeff, Npix);
     const dim3 grid(pl.col_tiles, pl.row_tiles);
     if (pl.family == RIME_ALM_F16_REG) {
-        const SplitPlan& p = pl.p;
-        if (!workspace || workspace_bytes < split_ws_bytes(p)) return RIME_EWORKSPACE;
-        uint4 *hi, *lo; float* inv;
-        launch_split_rows((const float*)alm, R, 2 * Ncoeff, p, 1, workspace, st, hi, lo, inv);
-        const float ys = (float)y_scale;
-        const float* Y = (const float*)Ylm; float* o = (float*)out;
-        if (p.MT == 4) hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<4>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, o);
-        else if (p.MT == 2) hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<2>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, o);
-        else hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<1>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, o);
+        const Staged s = stage_rows((const float*)alm, R, 2 * Ncoeff, pl, 1, workspace, workspace_bytes, out, st);
+        if (!s.part) return RIME_EWORKSPACE;
+        with_mt(pl.MT, [&](auto mt) {
+            hipLaunchKernelGGL((alm2pix_fwd_f16_kernel<decltype(mt)::value>), grid, dim3(256), 0, st, s.hi, s.lo, s.inv,
+                               (const float*)Ylm, (float)y_scale, R, pl.p.Rpad, Ncoeff, Npix, s.part);
+        });
     } else if (pl.family == RIME_ALM_F32_MFMA) {
-        const float* a = (const float*)alm; const float* Y = (const float*)Ylm; float* o = (float*)out;
-        const int MT = pl.MT;
-        if (MT == 4) hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<4>), grid, dim3(256), 0, st, a, Y, R, Ncoeff, Npix, o);
-        else if (MT == 2) hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<2>), grid, dim3(256), 0, st, a, Y, R, Ncoeff, Npix, o);
-        else hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<1>), grid, dim3(256), 0, st, a, Y, R, Ncoeff, Npix, o);
+        with_mt(pl.MT, [&](auto mt) {
+            hipLaunchKernelGGL((alm2pix_fwd_mfma_kernel<decltype(mt)::value>), grid, dim3(256), 0, st, (const float*)alm,
+                               (const float*)Ylm, R, Ncoeff, Npix, (float*)out);
+        });
     } else {
         constexpr int RTA = 16;                        // plan_fwd: row_tiles
         hipLaunchKernelGGL((alm2pix_fwd_kernel<double, RTA>), grid, dim3(256), 0, st,
@@ -1569,15 +1489,12 @@ extern "C" int rime_alm2pix_fwd(int dtype, const void* alm, const void* Ylm, dou
 extern "C" size_t rime_alm2pix_bwd_workspace(int dtype, int R, int Ncoeff, int Npix)
 {
     if (dtype != RIME_F32 || R <= 0 || Ncoeff <= 0 || Npix <= 0) return 0;
-    // exact-f32 path: split partials; f16-split path: images + row scales + split partials
-    const int S0 = bwd_splits(R, Ncoeff, Npix);
-    const size_t exact = S0 <= 1 ? 0 : (size_t)S0 * R * Ncoeff * 2 * sizeof(float);
-    const SplitPlan p = split_plan(R, Npix, Ncoeff, true);
-    const size_t fast = split_ws_bytes(p) + (size_t)p.S * R * Ncoeff * 2 * sizeof(float);
-    const SplitPlan pp = split_plan(R, Npix, Ncoeff, true, 1);                 // rime_alm2pix_bwd_packed: always a ring
-    const SplitPlan pw = split_plan(R, Npix, Ncoeff, true, 2);
-    const size_t packed = split_ws_bytes(pp) + (size_t)std::max(pp.S, pw.S) * R * Ncoeff * 2 * sizeof(float);
-    return std::max(exact, std::max(fast, packed));
+    // one buffer for the exact-f32 path (split partials), the f16-split path (images + row scales + split partials) and
+    // rime_alm2pix_bwd_packed on either ring
+    size_t need = 0;
+    for (const double ys : {0.0, 1.0}) need = std::max(need, plan_bwd(RIME_F32, ys, 0, R, Ncoeff, Npix).ws_bytes);
+    for (const bool wide8 : {false, true}) need = std::max(need, plan_bwd(RIME_F32, 1.0, 1, R, Ncoeff, Npix, wide8).ws_bytes);
+    return need;
 }
 
 extern "C" int rime_alm2pix_bwd(int dtype, const void* gout, const void* Ylm, double y_scale, int R, int Ncoeff,
@@ -1587,53 +1504,40 @@ extern "C" int rime_alm2pix_bwd(int dtype, const void* gout, const void* Ylm, do
     if (!gout || !Ylm || !galm || R <= 0 || Ncoeff <= 0 || Npix <= 0 || y_scale < 0) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (dtype != RIME_F32 && dtype != RIME_F64) return RIME_EINVAL;
-    const AlmPlan pl = plan_bwd(dtype, y_scale, R, Ncoeff, Npix);
+    const AlmPlan pl = plan_bwd(dtype, y_scale, 0, R, Ncoeff, Npix);
+    const size_t len = (size_t)R * Ncoeff * 2;
     if (pl.family == RIME_ALM_F16_DMA || pl.family == RIME_ALM_F16_REG) {
-        const SplitPlan& p = pl.p;
-        const size_t len = (size_t)R * Ncoeff * 2;
-        const size_t need = split_ws_bytes(p) + (size_t)p.S * len * sizeof(float);
-        if (!workspace || workspace_bytes < need) return RIME_EWORKSPACE;
-        uint4 *hi, *lo; float* inv;
-        launch_split_rows((const float*)gout, R, Npix, p, 0, workspace, st, hi, lo, inv);
-        float* part = p.S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)galm;
-        dim3 grid(pl.S, pl.col_tiles, pl.row_tiles);
+        const Staged s = stage_rows((const float*)gout, R, Npix, pl, 0, workspace, workspace_bytes, galm, st);
+        if (!s.part) return RIME_EWORKSPACE;
         const float ys = (float)y_scale;
         const float* Y = (const float*)Ylm;
-        if (pl.family == RIME_ALM_F16_DMA) {
-            const float* zero16 = (const float*)((char*)workspace + split_ws_bytes(p) - 64);
-            hipError_t e = hipSuccess;
-            // chunks of 2 K steps in a ring of 3 slots; 1 K step in 6 slots (more, smaller loads in flight) measured the same
-            if (p.MT == 4) e = launch_bwd_dma<4, 2, 3>(grid, st, hi, lo, inv, Y, zero16, ys, R, p.Rpad, Ncoeff, Npix, p.S, part);
-            else if (p.MT == 2) e = launch_bwd_dma<2, 2, 3>(grid, st, hi, lo, inv, Y, zero16, ys, R, p.Rpad, Ncoeff, Npix, p.S, part);
-            else e = launch_bwd_dma<1, 2, 3>(grid, st, hi, lo, inv, Y, zero16, ys, R, p.Rpad, Ncoeff, Npix, p.S, part);
-            if (e != hipSuccess) return RIME_ELAUNCH;
-        }
-        else if (p.MT == 4) hipLaunchKernelGGL((alm2pix_bwd_f16_kernel<4>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, p.S, part);
-        else if (p.MT == 2) hipLaunchKernelGGL((alm2pix_bwd_f16_kernel<2>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, p.S, part);
-        else hipLaunchKernelGGL((alm2pix_bwd_f16_kernel<1>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, p.S, part);
-        if (p.S > 1) {
-            int nb = (int)std::min<size_t>((len + 255) / 256, 2048);
-            hipLaunchKernelGGL(alm_reduce_kernel, dim3(nb), dim3(256), 0, st, part, (float*)galm, len, p.S);
-        }
+        const hipError_t e = with_mt(pl.MT, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            if (pl.family == RIME_ALM_F16_DMA)
+                // chunks of 2 K steps in a ring of 3 slots; 1 K step in 6 slots (more, smaller loads in flight) measured the same
+                return launch_dynamic_lds<alm2pix_bwd_f16_dma_kernel<MT, 2, 3>>(
+                    ring_grid(pl), dim3(256), BwdDma<MT, 2, 3>::LDS, st, s.hi, s.lo, s.inv, Y, s.zero16, ys, R, pl.p.Rpad, Ncoeff,
+                    Npix, pl.S, pl.col_tiles, pl.row_tiles, s.part);
+            hipLaunchKernelGGL((alm2pix_bwd_f16_kernel<MT>), dim3(pl.S, pl.col_tiles, pl.row_tiles), dim3(256), 0, st, s.hi, s.lo,
+                               s.inv, Y, ys, R, pl.p.Rpad, Ncoeff, Npix, pl.S, s.part);
+            return hipSuccess;
+        });
+        if (e != hipSuccess) return RIME_ELAUNCH;
+        reduce_planes(s.part, (float*)galm, len, pl.S, st);
         return check_launch();
     }
     if (pl.family == RIME_ALM_F32_MFMA) {
         const int S = pl.S;
-        const size_t len = (size_t)R * Ncoeff * 2;
-        if (S > 1 && (!workspace || workspace_bytes < (size_t)S * len * sizeof(float))) return RIME_EWORKSPACE;
+        if (pl.ws_bytes && (!workspace || workspace_bytes < pl.ws_bytes)) return RIME_EWORKSPACE;
         float* part = S > 1 ? (float*)workspace : (float*)galm;
         int pps = (Npix + S - 1) / S;
         pps = ((pps + 63) / 64) * 64;
-        const int MT = pl.MT;
-        dim3 grid(pl.col_tiles, S, pl.row_tiles);
-        const float* g = (const float*)gout; const float* Y = (const float*)Ylm;
-        if (MT == 4) hipLaunchKernelGGL((alm2pix_bwd_mfma_kernel<4>), grid, dim3(256), 0, st, g, Y, R, Ncoeff, Npix, pps, part);
-        else if (MT == 2) hipLaunchKernelGGL((alm2pix_bwd_mfma_kernel<2>), grid, dim3(128), 0, st, g, Y, R, Ncoeff, Npix, pps, part);
-        else hipLaunchKernelGGL((alm2pix_bwd_mfma_kernel<1>), grid, dim3(64), 0, st, g, Y, R, Ncoeff, Npix, pps, part);
-        if (S > 1) {
-            int nb = (int)std::min<size_t>((len + 255) / 256, 2048);
-            hipLaunchKernelGGL(alm_reduce_kernel, dim3(nb), dim3(256), 0, st, part, (float*)galm, len, S);
-        }
+        with_mt(pl.MT, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            hipLaunchKernelGGL((alm2pix_bwd_mfma_kernel<MT>), dim3(pl.col_tiles, S, pl.row_tiles), dim3(64 * MT), 0, st,
+                               (const float*)gout, (const float*)Ylm, R, Ncoeff, Npix, pps, part);
+        });
+        reduce_planes(part, (float*)galm, len, S, st);
         return check_launch();
     }
     constexpr int CT = 4, RTB = 8;                     // plan_bwd: col_tiles, row_tiles
@@ -1679,26 +1583,17 @@ extern "C" int rime_alm2pix_fwd_packed(const void* alm, const void* packed, doub
 {
     if (!alm || !packed || !out || R <= 0 || Ncoeff <= 0 || Npix <= 0 || !(y_scale > 0)) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const AlmPlan pl = plan_fwd_packed(R, Ncoeff, Npix);
-    const SplitPlan& p = pl.p;
+    const AlmPlan pl = plan_fwd(RIME_F32, y_scale, 1, R, Ncoeff, Npix);
     const int S = pl.S;
-    const size_t len = (size_t)R * Npix;
-    if (!workspace || workspace_bytes < split_ws_bytes(p) + (S > 1 ? (size_t)S * len * sizeof(float) : 0)) return RIME_EWORKSPACE;
-    uint4 *hi, *lo; float* inv;
-    launch_split_rows((const float*)alm, R, 2 * Ncoeff, p, 1, workspace, st, hi, lo, inv);
-    dim3 grid(pl.col_tiles, pl.row_tiles, S);
-    const float ys = (float)y_scale;
-    const uint4* Y = (const uint4*)packed;
-    float* o = S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)out;
+    const Staged s = stage_rows((const float*)alm, R, 2 * Ncoeff, pl, 1, workspace, workspace_bytes, out, st);
+    if (!s.part) return RIME_EWORKSPACE;
     const int nsteps = pk_fwd_steps(Ncoeff);
     const int cps = (nsteps / PK_FWD_CHUNK + S - 1) / S;
-    if (p.MT == 4) hipLaunchKernelGGL((alm2pix_fwd_packed_kernel<4>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, nsteps, cps, o);
-    else if (p.MT == 2) hipLaunchKernelGGL((alm2pix_fwd_packed_kernel<2>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, nsteps, cps, o);
-    else hipLaunchKernelGGL((alm2pix_fwd_packed_kernel<1>), grid, dim3(256), 0, st, hi, lo, inv, Y, ys, R, p.Rpad, Ncoeff, Npix, nsteps, cps, o);
-    if (S > 1) {
-        int nb = (int)std::min<size_t>((len + 255) / 256, 2048);
-        hipLaunchKernelGGL(alm_reduce_kernel, dim3(nb), dim3(256), 0, st, o, (float*)out, len, S);
-    }
+    with_mt(pl.MT, [&](auto mt) {
+        hipLaunchKernelGGL((alm2pix_fwd_packed_kernel<decltype(mt)::value>), dim3(pl.col_tiles, pl.row_tiles, S), dim3(256), 0, st,
+                           s.hi, s.lo, s.inv, (const uint4*)packed, (float)y_scale, R, pl.p.Rpad, Ncoeff, Npix, nsteps, cps, s.part);
+    });
+    reduce_planes(s.part, (float*)out, (size_t)R * Npix, S, st);
     return check_launch();
 }
 
@@ -1707,43 +1602,22 @@ extern "C" int rime_alm2pix_bwd_packed(const void* gout, const void* packed, dou
 {
     if (!gout || !packed || !galm || R <= 0 || Ncoeff <= 0 || Npix <= 0 || !(y_scale > 0)) return RIME_EINVAL;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const AlmPlan pl = plan_bwd_packed(R, Ncoeff, Npix);
-    const bool wide = pl.family == RIME_ALM_PACKED8;
-    const SplitPlan& p = pl.p;
-    const size_t len = (size_t)R * Ncoeff * 2;
-    const size_t need = split_ws_bytes(p) + (size_t)p.S * len * sizeof(float);
-    if (!workspace || workspace_bytes < need) return RIME_EWORKSPACE;
-    uint4 *hi, *lo; float* inv;
-    launch_split_rows((const float*)gout, R, Npix, p, 0, workspace, st, hi, lo, inv);
-    float* part = p.S > 1 ? (float*)((char*)workspace + split_ws_bytes(p)) : (float*)galm;
-    dim3 grid(pl.S, pl.col_tiles, pl.row_tiles);
-    const float* zero16 = (const float*)((char*)workspace + split_ws_bytes(p) - 64);
+    const AlmPlan pl = plan_bwd(RIME_F32, y_scale, 1, R, Ncoeff, Npix);
+    const Staged s = stage_rows((const float*)gout, R, Npix, pl, 0, workspace, workspace_bytes, galm, st);
+    if (!s.part) return RIME_EWORKSPACE;
     const uint4* Y = (const uint4*)packed;
+    const float ys = (float)y_scale;
     const int nsteps = pk_bwd_steps(Npix);
-    hipError_t e;
-    if (wide) {
-        const int CT2 = pl.col_tiles, RT = pl.row_tiles, NB = p.S * CT2 * RT;
-        static unsigned long long configured = 0ull;
-        int devid = 0;
-        if (hipGetDevice(&devid) != hipSuccess) devid = 0;
-        const unsigned long long bit = 1ull << (devid & 63);
-        e = hipSuccess;
-        if (!(configured & bit)) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&alm2pix_bwd_packed8_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, BwdDma8::LDS);
-            if (e == hipSuccess) configured |= bit;
-        }
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(alm2pix_bwd_packed8_kernel, dim3(8 * ((NB + 7) / 8)), dim3(512), BwdDma8::LDS, st, hi, lo, inv, Y,
-                               zero16, (float)y_scale, R, p.Rpad, Ncoeff, Npix, nsteps, p.S, CT2, RT, part);
-    }
-    else if (p.MT == 4) e = launch_bwd_packed<4, 3>(grid, st, hi, lo, inv, Y, zero16, (float)y_scale, R, p.Rpad, Ncoeff, Npix, nsteps, p.S, part);
-    else if (p.MT == 2) e = launch_bwd_packed<2, 3>(grid, st, hi, lo, inv, Y, zero16, (float)y_scale, R, p.Rpad, Ncoeff, Npix, nsteps, p.S, part);
-    else e = launch_bwd_packed<1, 3>(grid, st, hi, lo, inv, Y, zero16, (float)y_scale, R, p.Rpad, Ncoeff, Npix, nsteps, p.S, part);
+    const hipError_t e = pl.family == RIME_ALM_PACKED8
+        ? launch_dynamic_lds<alm2pix_bwd_packed8_kernel>(ring_grid(pl), dim3(512), BwdDma8::LDS, st, s.hi, s.lo, s.inv, Y, s.zero16,
+                                                         ys, R, pl.p.Rpad, Ncoeff, Npix, nsteps, pl.S, pl.col_tiles, pl.row_tiles, s.part)
+        : with_mt(pl.MT, [&](auto mt) {
+              constexpr int MT = decltype(mt)::value;
+              return launch_dynamic_lds<alm2pix_bwd_packed_kernel<MT, 3>>(
+                  ring_grid(pl), dim3(256), BwdDma<MT, PK_BWD_KS, 3>::LDS, st, s.hi, s.lo, s.inv, Y, s.zero16, ys, R, pl.p.Rpad,
+                  Ncoeff, Npix, nsteps, pl.S, pl.col_tiles, pl.row_tiles, s.part);
+          });
     if (e != hipSuccess) return RIME_ELAUNCH;
-    if (p.S > 1) {
-        int nb = (int)std::min<size_t>((len + 255) / 256, 2048);
-        hipLaunchKernelGGL(alm_reduce_kernel, dim3(nb), dim3(256), 0, st, part, (float*)galm, len, p.S);
-    }
+    reduce_planes(s.part, (float*)galm, (size_t)R * Ncoeff * 2, pl.S, st);
     return check_launch();
 }
