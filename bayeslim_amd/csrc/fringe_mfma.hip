@@ -23,8 +23,6 @@
 
 namespace rime {
 
-constexpr int MF_NA = 128;                   // antennas per block (4 x 4 tiles)
-
 struct AntArgs {
     const double* antpos;      // [Nant, 3]
     const double* sdir;        // [Nt, 3, Pstride]
@@ -128,8 +126,6 @@ __device__ __forceinline__ void split2_prod(float a0, float b0, float a1, float 
 // C4 (127-antenna hexagon + outrigger: 7 of 8 groups) 85.4 -> 79.4 ms/step, C3 20.3 -> 18.1, C2 0.861 -> 0.825
 // (profiles/r05/mirror_pairs.txt; a timing-only build had promised twice as much for the forward -- an artefact: its
 // duplicated image rows lowered the matrix pipe's switching power, and the chip is power-limited under these kernels).
-constexpr int MF_NH = MF_KP / 16;               // 16-pixel K steps per panel
-constexpr int MF_ROWB = 4 * MF_KP + 16;         // [re KP x f16][im KP x f16][pad]: odd number of 16-B granules
 
 // Block shapes.  Diagonal block: one group of <= 128 antennas against itself, upper-triangular
 // tiles, 4 waves.  Cross block (arrays with more than 128 antennas): group I (image rows 0..127,
@@ -259,17 +255,15 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
     constexpr bool SROWS_X = SIGNED && !CPLX && SH::CROSS && !SH::SELF;
     constexpr int SROWS = SROWS_X ? SH::TI : 0;
     constexpr bool XORL = SIGNED && !SROWS_X;
+    // block coordinates, panel source and wave switch of this body are in place, not the fragments of fringe_mfma_common.h:
+    // with them the two-tile unsigned instantiations take 128 registers instead of 134, i.e. four blocks per CU instead of
+    // three
     const int tid = threadIdx.x, lane = tid & 63;
-    // 1-D grid, channel fastest: blocks that run together share (t, split), i.e. the same pointing
-    // vectors (L2 hits), and no grid dimension hits the 65535 cap
     const int f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf), ts = blockIdx.x / A.Nf;
     const int t = __builtin_amdgcn_readfirstlane(ts / A.S), split = __builtin_amdgcn_readfirstlane(ts % A.S);
 
     const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
     const float scl = A.scale[t * A.Nf + f];
-    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
-    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
-    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
 
     // generation mapping: lane = (pixel pair pp, antenna slot ag); rows of one ds_write are 2 apart
     // (80-B rows: 8 rows x 32 B land in 16 distinct 16-B granules of the 64 banks)
@@ -293,60 +287,39 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
     // (round 4) the rows of a sweep are one OCTET per wave pair -- rows 16 u + 8 (W >> 1) + 2 (ag & 3) + (ag >> 2), conflict-free
     // ds_write_b32 as before -- instead of the rows of one parity: the sweeps a wave skips are then whole octets of padding,
     // 19 antennas cost 2 + 1 sweeps per wave pair instead of 2 + 2, 37 antennas 3 + 2 instead of 3 + 3 (same bits)
-    // (round 5) ... and the sweeps of a wave pair p = W >> 1 walk the octets of ONE 16-row group after the other: sweep u = rows
-    // 32 (u >> 1) + 16 p + 8 (u & 1) + i (before: 16 u + 8 p + i -- the same octets, dealt differently: same bits), so that
-    // the mirror antennas of a sweep's rows (AntArgs.mirror) are the next sweep's rows of the same lanes
-    const int orow = 16 * (W >> 1) + 2 * (ag & 3) + (ag >> 2);
-    auto octet_row = [&](int u) { return 32 * (u >> 1) + 8 * (u & 1) + orow; };
-    // sweeps whose octet starts below Nant (monotone in u): uniform
-    const int mrow = A.Nant - 16 * (W >> 1);
-    const int nk = (OCT && !OCT8) ? min(NGEN, (max(mrow, 0) + 31) / 32 + (max(mrow - 8, 0) + 31) / 32) : NGEN;
+    // (round 5) ... and the sweeps of a wave pair walk the octets of ONE 16-row group after the other (octet_row; before: rows
+    // 16 u + 8 p + i -- the same octets, dealt differently: same bits)
+    const int orow = octet_lane_row(W, ag);
+    const int nk = (OCT && !OCT8) ? octet_sweeps(A.Nant, W, NGEN) : NGEN;
     const int growx = SH::NW == 8 ? 2 * ag + 16 * ((W >> 1) & 1) + (W >> 2) : 2 * ag + (W >> 1);
     static_assert(!MIR || (OCT && !OCT8), "mirror groups: diagonal blocks with the half-panel generation mapping");
     double ax[NGEN], ay[NGEN], az[NGEN];
 #pragma unroll
     for (int u = 0; u < NGEN; ++u) {
-        const int an = OCT8 ? 32 * u + growx : OCT ? octet_row(u) : (OCTX ? SWX * u + growx : SH::GROWS * u + grow);
-        const bool ok = an < A.Nant;
-        ax[u] = ok ? nu_c * A.antpos[3 * an] : 0.0;
-        ay[u] = ok ? nu_c * A.antpos[3 * an + 1] : 0.0;
-        az[u] = ok ? nu_c * A.antpos[3 * an + 2] : 0.0;
+        const int an = OCT8 ? 32 * u + growx : OCT ? octet_row(u, orow) : (OCTX ? SWX * u + growx : SH::GROWS * u + grow);
+        load_ant(A.antpos, an, an < A.Nant, nu_c, ax[u], ay[u], az[u]);
     }
     const int goff = grow * MF_ROWB + pp * 4;
 
     f32x16 acc[UPW][2];
 #pragma unroll
-    for (int s = 0; s < UPW; ++s)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { acc[s][0][e] = 0.f; acc[s][1][e] = 0.f; }
+    for (int s = 0; s < UPW; ++s) { zero(acc[s][0]); zero(acc[s][1]); }
 
     const int npanel = A.Pstride / MF_KP;
     const int pbeg = __builtin_amdgcn_readfirstlane(split * A.panels_per_split);
     const int pend = __builtin_amdgcn_readfirstlane(min(npanel, pbeg + A.panels_per_split));
     if (pbeg >= pend) return;                        // uniform over the block
+    const FwdBlock blk = {f, t, split, pbeg, pend};
 
-    // panel fetch: wave-uniform bases (scalar address arithmetic) + constant 32-bit lane offsets;
-    // psky is read as two dwords with the runtime pixel stride (a branch on the stride makes the
-    // compiler issue both variants with 64-bit vector multiplies: 17 % of the loop's VALU work)
     double2 sx[MF_NH], sy[MF_NH], sz[MF_NH]; float2 av[MF_NH]; float2 aw[CPLX ? MF_NH : 1];   // aw: imaginary plane
+    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
+    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
+    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
     const uint32_t lo_s = 16u * pp, lo_a0 = 8u * pp * (uint32_t)st_p, lo_a1 = lo_a0 + 4u * (uint32_t)st_p;
-    const double* sdy = sd + A.Pstride;
-    const double* sdz = sd + 2 * (size_t)A.Pstride;
-    // buffer loads: descriptor (SGPRs, wave-uniform: built from kernel arguments and the block index) + constant per-lane
-    // offset + scalar panel offset -- no vector address arithmetic in the generation phase, whose cost is its
-    // instruction count (profiles/r03/lab_forward_experiments.txt); out-of-range reads return 0 instead of faulting
-    // (the descriptor inputs go through readfirstlane: a base pointer the compiler cannot PROVE wave-uniform makes it wrap
-    // every buffer load in a waterfall loop of ~14 instructions -- seen here on the psky descriptor, guide T20)
-    auto uniform_ptr = [](const void* q) {
-        const unsigned long long a = reinterpret_cast<unsigned long long>(q);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        return reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    };
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(sd), 0, __builtin_amdgcn_readfirstlane((int)min((long long)3 * A.Pstride * 8, 0x7fffffffLL)), 0x00020000);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(arow), 0, __builtin_amdgcn_readfirstlane((int)min((long long)A.Pstride * st_p * 4, 0x7fffffffLL)), 0x00020000);
-    (void)sdy; (void)sdz;
     auto fetch = [&](int panel, int hf) {
         const int p0 = panel * MF_KP + 16 * hf;      // uniform
         sx[hf] = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, p0 * 8, 0));
@@ -362,34 +335,24 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
     auto generate = [&](unsigned char* buf, int next_panel) {
         if constexpr (OCT) {
             constexpr int hf = W & 1;
-            const float w0 = __builtin_amdgcn_sqrtf(fabsf(av[hf].x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av[hf].y) * scl);
+            float w0, w1;
+            pixel_weights(av[hf], scl, w0, w1);
             if (SIGNED && !SROWS_X && W < 2 && lane < 8)
-                *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
-                    ((__float_as_uint(av[hf].x) >> 16) & 0x8000u) | (__float_as_uint(av[hf].y) & 0x80000000u);
+                *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) = sign_dword(av[hf]);
             // the weight with the sign of psky: sweeps below SROWS store it.  Of the shapes that come this way only the eight-wave
             // cross blocks (OCT8) have SROWS > 0; in every diagonal instantiation -- MIR included, which implies !CROSS -- SROWS is 0,
             // `u < SROWS ? g : w` folds to w at compile time and their code is the parent's instruction for instruction
             float g0 = w0, g1 = w1;
-            if constexpr (SROWS > 0) {
-                g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av[hf].x) & 0x80000000u));
-                g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av[hf].y) & 0x80000000u));
-            }
+            if constexpr (SROWS > 0) signed_weights(av[hf], w0, w1, g0, g1);
             // one evaluated sweep: the weighted f16 halves of this lane's pixel pair for the antenna at (bx, by, bz)
             auto sweep = [&](float w0, float w1, double bx, double by, double bz, uint32_t& rh, uint32_t& rl, uint32_t& ih, uint32_t& il) {
-                const double ph0 = phase3(bx, sx[hf].x, by, sy[hf].x, bz, sz[hf].x);
-                const double ph1 = phase3(bx, sx[hf].y, by, sy[hf].y, bz, sz[hf].y);
-                const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                float c0, s0, c1, s1;
+                phasor_pair<false>(bx, by, bz, sx[hf], sy[hf], sz[hf], c0, s0, c1, s1);
                 split2(w0 * c0, w1 * c1, rh, rl);
                 split2(w0 * s0, w1 * s1, ih, il);
             };
             auto store = [&](int row, uint32_t rh, uint32_t rl, uint32_t ih, uint32_t il) {
-                unsigned char* o = buf + row * MF_ROWB + pp * 4 + 32 * hf;
-                *reinterpret_cast<uint32_t*>(o) = rh;
-                *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG) = rl;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG + 2 * MF_KP) = il;
+                store_image<MF_IMG>(buf + row * MF_ROWB + pp * 4 + 32 * hf, rh, rl, ih, il);
             };
             if constexpr (MIR) {
                 uint32_t m_rh = 0, m_rl = 0, m_ih = 0, m_il = 0;
@@ -401,7 +364,7 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                             rh = m_rh; rl = m_rl; ih = m_ih ^ 0x80008000u; il = m_il ^ 0x80008000u;
                         } else sweep(u < SROWS ? g0 : w0, u < SROWS ? g1 : w1, ax[u], ay[u], az[u], rh, rl, ih, il);
                         if (!(u & 1)) { m_rh = rh; m_rl = rl; m_ih = ih; m_il = il; }
-                        store(octet_row(u), rh, rl, ih, il);
+                        store(octet_row(u, orow), rh, rl, ih, il);
                     }
                 }
             } else {
@@ -410,7 +373,7 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                     if (u < nk) {
                         uint32_t rh, rl, ih, il;
                         sweep(u < SROWS ? g0 : w0, u < SROWS ? g1 : w1, ax[u], ay[u], az[u], rh, rl, ih, il);
-                        store(OCT8 ? 32 * u + growx : octet_row(u), rh, rl, ih, il);
+                        store(OCT8 ? 32 * u + growx : octet_row(u, orow), rh, rl, ih, il);
                     }
                 }
             }
@@ -426,30 +389,21 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                 const float ar0 = av[hf].x * sb, ar1 = av[hf].y * sb, ai0 = aw[hf].x * si, ai1 = aw[hf].y * si;
 #pragma unroll
                 for (int u = 0; u < NGEN; ++u) {
-                    const double ph0 = phase3(ax[u], sx[hf].x, ay[u], sy[hf].x, az[u], sz[hf].x);
-                    const double ph1 = phase3(ax[u], sx[hf].y, ay[u], sy[hf].y, az[u], sz[hf].y);
-                    const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                    const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                    const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                    float c0, s0, c1, s1;
+                    phasor_pair<false>(ax[u], ay[u], az[u], sx[hf], sy[hf], sz[hf], c0, s0, c1, s1);
                     uint32_t rh, rl, ih, il;
                     unsigned char* o = OCTX ? buf + (SWX * u + growx) * MF_ROWB + pp * 4 + 32 * hf
                                             : buf + goff + u * SH::GROWS * MF_ROWB + 32 * hf;
                     if (SH::SELF || u < NI) { // group I: L = 2^7 E
                         split2(128.0f * c0, 128.0f * c1, rh, rl);
                         split2(128.0f * s0, 128.0f * s1, ih, il);
-                        *reinterpret_cast<uint32_t*>(o) = rh;
-                        *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                        *reinterpret_cast<uint32_t*>(o + MF_IMG) = rl;
-                        *reinterpret_cast<uint32_t*>(o + MF_IMG + 2 * MF_KP) = il;
+                        store_image<MF_IMG>(o, rh, rl, ih, il);
                         if constexpr (SH::SELF) o += SH::GEN_I * SH::GROWS * MF_ROWB;     // the same antenna's B row
                     }
                     if (SH::SELF || u >= NI) { // group J: B = psky E (complex product)
                         split2(fmaf(ar0, c0, -ai0 * s0), fmaf(ar1, c1, -ai1 * s1), rh, rl);
                         split2(fmaf(ar0, s0, ai0 * c0), fmaf(ar1, s1, ai1 * c1), ih, il);
-                        *reinterpret_cast<uint32_t*>(o) = rh;
-                        *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                        *reinterpret_cast<uint32_t*>(o + MF_IMG) = rl;
-                        *reinterpret_cast<uint32_t*>(o + MF_IMG + 2 * MF_KP) = il;
+                        store_image<MF_IMG>(o, rh, rl, ih, il);
                     }
                 }
                 fetch(next_panel, hf);
@@ -458,31 +412,21 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
         }
 #pragma unroll
         for (int hf = 0; hf < MF_NH; ++hf) {
-            const float w0 = __builtin_amdgcn_sqrtf(fabsf(av[hf].x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av[hf].y) * scl);
+            float w0, w1;
+            pixel_weights(av[hf], scl, w0, w1);
             if (SIGNED && !SROWS_X && tid < 8)
-                *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
-                    ((__float_as_uint(av[hf].x) >> 16) & 0x8000u) | (__float_as_uint(av[hf].y) & 0x80000000u);
+                *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) = sign_dword(av[hf]);
             float g0 = w0, g1 = w1;                  // the weight with the sign of psky: sweeps below SROWS store it
-            if constexpr (SROWS > 0) {
-                g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av[hf].x) & 0x80000000u));
-                g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av[hf].y) & 0x80000000u));
-            }
+            if constexpr (SROWS > 0) signed_weights(av[hf], w0, w1, g0, g1);
 #pragma unroll
             for (int u = 0; u < SH::GEN; ++u) {
                 const float m0 = u < SROWS ? g0 : w0, m1 = u < SROWS ? g1 : w1;
-                const double ph0 = phase3(ax[u], sx[hf].x, ay[u], sy[hf].x, az[u], sz[hf].x);
-                const double ph1 = phase3(ax[u], sx[hf].y, ay[u], sy[hf].y, az[u], sz[hf].y);
-                const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                float c0, s0, c1, s1;
+                phasor_pair<false>(ax[u], ay[u], az[u], sx[hf], sy[hf], sz[hf], c0, s0, c1, s1);
                 uint32_t rh, rl, ih, il;
                 split2(m0 * c0, m1 * c1, rh, rl);
                 split2(m0 * s0, m1 * s1, ih, il);
-                unsigned char* o = buf + goff + u * SH::GROWS * MF_ROWB + 32 * hf;
-                *reinterpret_cast<uint32_t*>(o) = rh;
-                *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG) = rl;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG + 2 * MF_KP) = il;
+                store_image<MF_IMG>(buf + goff + u * SH::GROWS * MF_ROWB + 32 * hf, rh, rl, ih, il);
             }
             fetch(next_panel, hf);                   // latency hidden by the MFMA phase
         }
@@ -554,14 +498,14 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
             });
         }
     };
-    // two panels per trip: buffer addresses are compile-time offsets
-    unsigned char* const buf0 = smem;
-    unsigned char* const buf1 = smem + MF_BUF;
     if constexpr (OCT || OCTX) fetch(pbeg, W & 1);
     else {
 #pragma unroll
         for (int hf = 0; hf < MF_NH; ++hf) fetch(pbeg, hf);
     }
+    // two panels per trip: buffer addresses are compile-time offsets (the loop is written out in every body: DESIGN.md 5.1f)
+    unsigned char* const buf0 = smem;
+    unsigned char* const buf1 = smem + MF_BUF;
     generate(buf0, min(pbeg + 1, pend - 1));
     __syncthreads();
     for (int panel = pbeg; panel < pend; panel += 2) {
@@ -575,19 +519,15 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
         __syncthreads();
     }
 
-    // epilogue: V[i,j] / scale -> the baseline slot(s) of pair (i,j) of this block's slab
-    // ws[split][t][f][re|im][Nbl]: consecutive lanes (columns j) hit consecutive baseline slots, so
-    // the stores coalesce (a scattered store into the [Nbl][Nt][Nf][2] result costs a 32-B sector per
-    // 4-B value: 8 GB instead of 1.6 GB per launch at C4); reduce_vis_kernel sums the splits in a
-    // fixed order and transposes into the result layout.
-    float* dst = A.ws + (((size_t)split * A.Nt + t) * A.Nf + f) * 2 * A.Nbl;
+    // epilogue: V[i,j] / scale -> the baseline slot(s) of pair (i,j) of this block's slab (fwd_slab)
+    float* dst = fwd_slab(A, blk);
     const float inv = 1.0f / scl;
     // (the three-row-tile self block is one register over its budget here: its epilogue re-derives the lane index from the
     //  execution mask instead of keeping `lane & 31` / `lane >> 5` alive across the panel loop -- until round 5 that was 8 bytes
     //  of scratch, a store before the loop and a load after it)
     int elane = lane;
     if constexpr (SH::SELF && SH::TI == 3) elane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    const int col = elane & 31;
+    const int col = elane & 31, eh = elane >> 5;
     RIME_MFMA_SETTLE();
     // the image buffers are free after the loop's last barrier: a private 32 x 33 float tile per wave
     // transposes the accumulators of diagonal-tile units (written and read by this wave only)
@@ -614,45 +554,21 @@ __device__ __forceinline__ void ant_fwd_body(const AntArgs& A, unsigned char* sm
                 for (int e = 0; e < 16; ++e) val[e] += ex[e * 64 + lane];
             }
             if (is_diag<SH>(u >> 1)) {
+                const f32x16 tv = transposed(tr, val, col, eh);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) tr[((e & 3) + 8 * (e >> 2) + 4 * (elane >> 5)) * 33 + col] = val[e];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float tv = tr[col * 33 + (e & 3) + 8 * (e >> 2) + 4 * (elane >> 5)];
-                    val[e] = im ? val[e] - tv : val[e] + tv;
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                for (int e = 0; e < 16; ++e) val[e] = im ? val[e] - tv[e] : val[e] + tv[e];
             }
 #pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2) + 4 * (elane >> 5);
-                const int i = ti * 32 + row, j = tj * 32 + col;      // indices inside group I / group J
-                const float v = val[e] * inv;
-                const int bd = A.pair_direct[i * MF_NA + j];
-                if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
-                const int bc = A.pair_conj[i * MF_NA + j];
-                if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
-            }
+            for (int e = 0; e < 16; ++e)              // indices inside group I / group J
+                put1(A, dst, ti * 32 + acc_row(e, eh), tj * 32 + col, im, val[e] * inv);
         }
     }
-}
-
-// A block works on one psky row (t, f): rows without a negative value (beam-weighted emission is
-// non-negative) take the kernel instantiation without sign masks.  Both instantiations are launched
-// over the full grid and a block returns at once when its row belongs to the other one: a branch
-// inside one kernel costs registers (the allocator serves the union of both paths and spills).
-__device__ __forceinline__ bool row_is_signed(const AntArgs& A)
-{
-    if (!A.rowmin) return true;
-    const int f = blockIdx.x % A.Nf, t = (blockIdx.x / A.Nf) / A.S;
-    return A.rowmin[t * A.Nf + f] < 0.f;
 }
 
 template <class SH, bool SIGNED, bool CPLX, bool MIR = false>
 __device__ __forceinline__ void ant_fwd_dispatch(const AntArgs& A, unsigned char* smem)
 {
-    if constexpr (!CPLX) { if (row_is_signed(A) != SIGNED) return; }        // uniform over the block
+    if constexpr (!CPLX) { if (row_is_signed(A, fwd_block(A)) != SIGNED) return; }      // uniform over the block
     switch (threadIdx.x >> 6) {                      // wave-uniform: every wave runs the same barriers
         case 0: ant_fwd_body<SH, 0, SIGNED, CPLX, MIR>(A, smem); break;
         case 1: ant_fwd_body<SH, 1, SIGNED, CPLX, MIR>(A, smem); break;
@@ -742,15 +658,12 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
 {
     constexpr int KS = W & 1;                           // this wave's K step of every panel
     constexpr bool PAIR_B = W >= 2;                     // waves 2, 3: tiles (0,1) + (1,1); waves 0, 1: tile (0,0)
+    const FwdBlock blk = fwd_block(A);
     const int tid = threadIdx.x, lane = tid & 63;
-    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf), ts = blockIdx.x / A.Nf;
-    const int t = __builtin_amdgcn_readfirstlane(ts / A.S), split = __builtin_amdgcn_readfirstlane(ts % A.S);
+    const int f = blk.f, t = blk.t;
 
     const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
     const float scl = A.scale[t * A.Nf + f];
-    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
-    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
-    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
 
     // generation: lane = (pixel pair pp, antenna slot ag); this wave writes the 16-pixel half `hf` of the panel for the
     // antennas 16 u + 8 (W >> 1) + 2 (ag & 3) + (ag >> 2), u = 0, 1 (first row tile), 2 (second); sweeps whose octet is all
@@ -769,48 +682,24 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
     double ax[NGEN], ay[NGEN], az[NGEN];
 #pragma unroll
     for (int u = 0; u < NGEN; ++u) {
-        const int an = sweep_row(u);
-        const bool ok = an < A.Nant;
-        ax[u] = ok ? nu_c * A.antpos[3 * an] : 0.0;
-        ay[u] = ok ? nu_c * A.antpos[3 * an + 1] : 0.0;
-        az[u] = ok ? nu_c * A.antpos[3 * an + 2] : 0.0;
+        load_ant(A.antpos, sweep_row(u), sweep_row(u) < A.Nant, nu_c, ax[u], ay[u], az[u]);
     }
 
     f32x16 acc0, acc1, acc2, acc3; // waves 0, 1: R (hi x lo), I (two products), R (hi x hi); waves 2, 3: tile (0,1), tile (1,1)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; acc2[e] = 0.f; acc3[e] = 0.f; }
+    zero(acc0); zero(acc1); zero(acc2); zero(acc3);
 
-    const int npanel = A.Pstride / MF_KP;
-    const int pbeg = __builtin_amdgcn_readfirstlane(split * A.panels_per_split);
-    const int pend = __builtin_amdgcn_readfirstlane(min(npanel, pbeg + A.panels_per_split));
-    if (pbeg >= pend) return;                        // uniform over the block
+    if (blk.pbeg >= blk.pend) return;                // uniform over the block
 
-    // panel fetch through buffer loads (see the generic kernel): descriptor in SGPRs + constant lane offset + scalar offset
     double2 sx, sy, sz; float2 av;
-    const uint32_t lo_s = 16u * pp, lo_a0 = 8u * pp * (uint32_t)st_p, lo_a1 = lo_a0 + 4u * (uint32_t)st_p;
-    auto uniform_ptr = [](const void* q) {
-        const unsigned long long a = reinterpret_cast<unsigned long long>(q);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        return reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    };
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        uniform_ptr(sd), 0, __builtin_amdgcn_readfirstlane((int)min((long long)3 * A.Pstride * 8, 0x7fffffffLL)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        uniform_ptr(arow), 0, __builtin_amdgcn_readfirstlane((int)min((long long)A.Pstride * st_p * 4, 0x7fffffffLL)), 0x00020000);
+    const PanelSource src = panel_source(A, blk, pp);
     auto fetch = [&](int panel) {
-        const int p0 = panel * MF_KP + 16 * hf;      // uniform
-        sx = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, p0 * 8, 0));
-        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (A.Pstride + p0) * 8, 0));
-        sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (2 * A.Pstride + p0) * 8, 0));
-        const int so = p0 * st_p * 4;
-        av = make_float2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a0, so, 0)),
-                         __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a1, so, 0)));
+        fetch_dirs(src, panel, hf, sx, sy, sz);
+        fetch_psky(src, panel, hf, av);
     };
     auto generate = [&](unsigned char* buf, int next_panel) {
-        const float w0 = __builtin_amdgcn_sqrtf(fabsf(av.x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av.y) * scl);
-        if (SIGNED && W < 2 && lane < 8)
-            *reinterpret_cast<uint32_t*>(buf + 2 * PK::IMG + 4 * (8 * hf + pp)) =
-                ((__float_as_uint(av.x) >> 16) & 0x8000u) | (__float_as_uint(av.y) & 0x80000000u);
+        float w0, w1;
+        pixel_weights(av, scl, w0, w1);
+        if (SIGNED && W < 2 && lane < 8) *reinterpret_cast<uint32_t*>(buf + 2 * PK::IMG + 4 * (8 * hf + pp)) = sign_dword(av);
         uint32_t m_rh = 0, m_rl = 0, m_ih = 0, m_il = 0;          // sweep 0: sweep 1 of a mirror group is its conjugate
 #pragma unroll
         for (int u = 0; u < NGEN; ++u) {
@@ -819,21 +708,14 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
                 if (MIR && u == 1 && ((A.mirror >> (W >> 1)) & 1)) {   // uniform
                     rh = m_rh; rl = m_rl; ih = m_ih ^ 0x80008000u; il = m_il ^ 0x80008000u;
                 } else {
-                    const double ph0 = phase3(ax[u], sx.x, ay[u], sy.x, az[u], sz.x);
-                    const double ph1 = phase3(ax[u], sx.y, ay[u], sy.y, az[u], sz.y);
-                    const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                    const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                    const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                    float c0, s0, c1, s1;
+                    phasor_pair<false>(ax[u], ay[u], az[u], sx, sy, sz, c0, s0, c1, s1);
                     split2(w0 * c0, w1 * c1, rh, rl);
                     split2(w0 * s0, w1 * s1, ih, il);
                 }
                 if (MIR && u == 0) { m_rh = rh; m_rl = rl; m_ih = ih; m_il = il; }
                 if (u < 2) {
-                    unsigned char* o = buf + sweep_row(u) * PK::ROWB0 + pp * 4 + 32 * hf;
-                    *reinterpret_cast<uint32_t*>(o) = rh;
-                    *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                    *reinterpret_cast<uint32_t*>(o + PK::IMG) = rl;
-                    *reinterpret_cast<uint32_t*>(o + PK::IMG + 2 * MF_KP) = il;
+                    store_image<PK::IMG>(buf + sweep_row(u) * PK::ROWB0 + pp * 4 + 32 * hf, rh, rl, ih, il);
                 } else {
                     unsigned char* o = buf + PK::IMG0 + grow * PK::ROWB1 + pp * 4 + 32 * hf;
                     *reinterpret_cast<uint32_t*>(o) = rh;
@@ -892,9 +774,11 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
         }
     };
 
+    fetch(blk.pbeg);
+    // two panels per trip: buffer addresses are compile-time offsets
     unsigned char* const buf0 = smem;
     unsigned char* const buf1 = smem + PK::BUF;
-    fetch(pbeg);
+    const int pbeg = blk.pbeg, pend = blk.pend;
     generate(buf0, min(pbeg + 1, pend - 1));
     __syncthreads();
     for (int panel = pbeg; panel < pend; panel += 2) {
@@ -911,15 +795,14 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
     // epilogue.  The waves of a pair hold the two K steps' partial sums of the same tiles: wave 0 finishes the real part
     // of tile (0,0), wave 1 its imaginary part, wave 2 tile (0,1), wave 3 tile (1,1); each hands the other unit's partial
     // tile to its partner through LDS ([e][lane] floats behind the four transposition tiles).
-    float* dst = A.ws + (((size_t)split * A.Nt + t) * A.Nf + f) * 2 * A.Nbl;
+    float* dst = fwd_slab(A, blk);
     const float inv = 1.0f / scl;
     const int col = lane & 31;
     RIME_MFMA_SETTLE();
     float* tr = reinterpret_cast<float*>(smem) + W * (32 * 33);
     float* ex = reinterpret_cast<float*>(smem) + 4 * (32 * 33);
     f32x16 val, sym;                                 // sym: the part of the real unit that is symmetric as it stands
-#pragma unroll
-    for (int e = 0; e < 16; ++e) sym[e] = 0.f;
+    zero(sym);
     if constexpr (!PAIR_B) {
         // give: the unit the partner finishes; keep: mine.  W = 0 keeps R (acc0, acc3), gives I = acc1 - acc2; W = 1 the
         // reverse (its two R parts go through its own exchange tile and a fifth one)
@@ -947,35 +830,16 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
 
     if constexpr (!PAIR_B) {
         constexpr int im = W;                        // wave 0: real part, wave 1: imaginary part
+        const f32x16 tv = transposed(tr, val, col, lane >> 5);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) tr[((e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)) * 33 + col] = val[e];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int e = 0; e < 16; ++e) val[e] = im ? val[e] - tv[e] : (val[e] + tv[e]) + sym[e];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float tv = tr[col * 33 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)];
-            val[e] = im ? val[e] - tv : (val[e] + tv) + sym[e];
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int i = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5), j = col;
-            const float v = val[e] * inv;
-            const int bd = A.pair_direct[i * MF_NA + j];
-            if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
-            const int bc = A.pair_conj[i * MF_NA + j];
-            if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
-        }
+        for (int e = 0; e < 16; ++e) put1(A, dst, acc_row(e, lane >> 5), col, im, val[e] * inv);
     } else if constexpr (W == 2) {
         // tile (0,1): rows = antennas 0..31, columns 0..15: Vr of antenna 32 + col, columns 16..31: Vi of antenna 16 + col
         const int im = col >> 4, j = 32 + (col & 15);
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int i = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-            const float v = val[e] * inv;
-            const int bd = A.pair_direct[i * MF_NA + j];
-            if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
-            const int bc = A.pair_conj[i * MF_NA + j];
-            if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
-        }
+        for (int e = 0; e < 16; ++e) put1(A, dst, acc_row(e, lane >> 5), j, im, val[e] * inv);
     } else {
         // tile (1,1): D rows a (elements e < 8) and 16 + a (e + 8) of this lane's column, partner column in lane ^ 16:
         //   col < 16:  Vr[a][col]      = D[a][col] + D[16 + a][16 + col]
@@ -984,12 +848,7 @@ __device__ __forceinline__ void ant_fwd_packed_body(const AntArgs& A, unsigned c
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float other = __shfl_xor(val[e + 8], 16, 64);
-            const float v = (im ? val[e] - other : val[e] + other) * inv;
-            const int i = 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-            const int bd = A.pair_direct[i * MF_NA + j];
-            if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
-            const int bc = A.pair_conj[i * MF_NA + j];
-            if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
+            put1(A, dst, 32 + acc_row(e, lane >> 5), j, im, (im ? val[e] - other : val[e] + other) * inv);
         }
     }
 }
@@ -999,13 +858,8 @@ __global__ void __launch_bounds__(PK::NW * 64, 2)
 fringe_ant_fwd_packed_kernel(AntArgs A)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (row_is_signed(A) != SIGNED) return;              // uniform over the block
-    switch (threadIdx.x >> 6) {                          // wave-uniform: every wave runs the same barriers
-        case 0: ant_fwd_packed_body<0, SIGNED, MIR>(A, smem); break;
-        case 1: ant_fwd_packed_body<1, SIGNED, MIR>(A, smem); break;
-        case 2: ant_fwd_packed_body<2, SIGNED, MIR>(A, smem); break;
-        default: ant_fwd_packed_body<3, SIGNED, MIR>(A, smem); break;
-    }
+    if (row_is_signed(A, fwd_block(A)) != SIGNED) return;        // uniform over the block
+    for_wave<PK::NW>([&](auto w) { ant_fwd_packed_body<w(), SIGNED, MIR>(A, smem); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1046,92 +900,70 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
 {
     using SH = FwdShape<2, 2, false>;
     constexpr int MF_IMG = SH::IMG, MF_BUF = SH::BUF;
+    const FwdBlock blk = fwd_block(A);
     const int tid = threadIdx.x, lane = tid & 63;
-    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf), ts = blockIdx.x / A.Nf;
-    const int t = __builtin_amdgcn_readfirstlane(ts / A.S), split = __builtin_amdgcn_readfirstlane(ts % A.S);
+    const int f = blk.f, t = blk.t;
 
     const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
     const float scl = A.scale[t * A.Nf + f];
-    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
-    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
-    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
 
     // generation: the half-panel mapping of the two-tile blocks -- lane = (pixel pair pp, row ag of an octet), this wave writes
     // the 16-pixel half W & 1 for the octets of the wave pair W >> 1 (rows 32 (u >> 1) + 16 (W >> 1) + 8 (u & 1) + i)
     const int pp = lane & 7, ag = lane >> 3;
     constexpr int hf = W & 1;
     constexpr int NGEN = 4;
-    const int orow = 16 * (W >> 1) + 2 * (ag & 3) + (ag >> 2);
-    auto octet_row = [&](int u) { return 32 * (u >> 1) + 8 * (u & 1) + orow; };
-    const int mrow = A.Nant - 16 * (W >> 1);
-    const int nk = min(NGEN, (max(mrow, 0) + 31) / 32 + (max(mrow - 8, 0) + 31) / 32);     // sweeps whose octet starts below Nant
+    const int orow = octet_lane_row(W, ag);
+    const int nk = octet_sweeps(A.Nant, W, NGEN);
     double ax[NGEN], ay[NGEN], az[NGEN];
 #pragma unroll
     for (int u = 0; u < NGEN; ++u) {
-        const int an = octet_row(u);
-        const bool ok = an < A.Nant;
-        ax[u] = ok ? nu_c * A.antpos[3 * an] : 0.0;
-        ay[u] = ok ? nu_c * A.antpos[3 * an + 1] : 0.0;
-        az[u] = ok ? nu_c * A.antpos[3 * an + 2] : 0.0;
+        load_ant(A.antpos, octet_row(u, orow), octet_row(u, orow) < A.Nant, nu_c, ax[u], ay[u], az[u]);
     }
 
     // waves 0, 1: acc[0], acc[1]; waves 2, 3: 0 half of Pcc, 1 half of Pss, 2 cs (hi x hi + hi x lo), 3 sc (hi x lo)
     constexpr int NACC = W < 2 ? 2 : 4;
     f32x16 acc[NACC];
 #pragma unroll
-    for (int s = 0; s < NACC; ++s)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
+    for (int s = 0; s < NACC; ++s) zero(acc[s]);
     float cr[NGEN], ci[NGEN];                        // CEN: column sums of this lane's rows
 #pragma unroll
     for (int u = 0; u < NGEN; ++u) { cr[u] = 0.f; ci[u] = 0.f; }
 
-    const int npanel = A.Pstride / MF_KP;
-    const int pbeg = __builtin_amdgcn_readfirstlane(split * A.panels_per_split);
-    const int pend = __builtin_amdgcn_readfirstlane(min(npanel, pbeg + A.panels_per_split));
-    if (pbeg >= pend) return;                        // uniform over the block
+    if (blk.pbeg >= blk.pend) return;                // uniform over the block
 
-    // panel fetch through buffer loads (see the generic kernel): descriptor in SGPRs + constant lane offset + scalar offset
     double2 sx, sy, sz = make_double2(0.0, 0.0); float2 av;
+    // panel source in place, offsets through readfirstlane (bit-stable results, no waterfall loop)
+    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
+    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
+    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
     const uint32_t lo_s = 16u * pp, lo_a0 = 8u * pp * (uint32_t)st_p, lo_a1 = lo_a0 + 4u * (uint32_t)st_p;
-    auto uniform_ptr = [](const void* q) {
-        const unsigned long long a = reinterpret_cast<unsigned long long>(q);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        return reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    };
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(sd), 0, __builtin_amdgcn_readfirstlane((int)min((long long)3 * A.Pstride * 8, 0x7fffffffLL)), 0x00020000);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(arow), 0, __builtin_amdgcn_readfirstlane((int)min((long long)A.Pstride * st_p * 4, 0x7fffffffLL)), 0x00020000);
     auto fetch = [&](int panel) {
         const int p0 = panel * MF_KP + 16 * hf;      // uniform
+        const int oy = __builtin_amdgcn_readfirstlane((A.Pstride + p0) * 8), oz = __builtin_amdgcn_readfirstlane((2 * A.Pstride + p0) * 8);
         sx = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, p0 * 8, 0));
-        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (A.Pstride + p0) * 8, 0));
-        if constexpr (!FLAT) sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (2 * A.Pstride + p0) * 8, 0));
-        const int so = p0 * st_p * 4;
+        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, oy, 0));
+        if constexpr (!FLAT) sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, oz, 0));
+        const int so = __builtin_amdgcn_readfirstlane(p0 * st_p * 4);
         av = make_float2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a0, so, 0)),
                          __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a1, so, 0)));
     };
     auto generate = [&](unsigned char* buf, int next_panel) {
-        const float w0 = __builtin_amdgcn_sqrtf(fabsf(av.x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av.y) * scl);
-        if (SIGNED && W < 2 && lane < 8)
-            *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
-                ((__float_as_uint(av.x) >> 16) & 0x8000u) | (__float_as_uint(av.y) & 0x80000000u);
+        float w0, w1;
+        pixel_weights(av, scl, w0, w1);
+        if (SIGNED && W < 2 && lane < 8) *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) = sign_dword(av);
         // the weight once more, with the sign of psky: the rows of tile 0 are stored with it (SIGNED ROWS above), and with CEN
         // sum_p psky scale E = sum_p (+-w)(w E) is the product of the two weights whichever of them the row carries
         float g0 = w0, g1 = w1;
-        if constexpr (SIGNED) {
-            g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av.x) & 0x80000000u));
-            g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av.y) & 0x80000000u));
-        }
+        if constexpr (SIGNED) signed_weights(av, w0, w1, g0, g1);
 #pragma unroll
         for (int u = 0; u < NGEN; ++u) {
             if (u < nk) {
-                const double ph0 = phase_of<FLAT>(ax[u], sx.x, ay[u], sy.x, az[u], sz.x);
-                const double ph1 = phase_of<FLAT>(ax[u], sx.y, ay[u], sy.y, az[u], sz.y);
-                const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                float c0, s0, c1, s1;
+                phasor_pair<FLAT>(ax[u], ay[u], az[u], sx, sy, sz, c0, s0, c1, s1);
                 // sweeps 0, 1 write tile 0 (signed rows), sweeps 2, 3 tile 1 (unsigned): m the weight stored, n the other one
                 const float m0 = u < 2 ? g0 : w0, m1 = u < 2 ? g1 : w1;
                 const float n0 = u < 2 ? w0 : g0, n1 = u < 2 ? w1 : g1;
@@ -1146,11 +978,7 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
                     cr[u] = fmaf(n0, xr0, cr[u]); keep_scalar(cr[u]); ci[u] = fmaf(n0, xi0, ci[u]);
                     cr[u] = fmaf(n1, xr1, cr[u]); keep_scalar(cr[u]); ci[u] = fmaf(n1, xi1, ci[u]);
                 }
-                unsigned char* o = buf + octet_row(u) * MF_ROWB + pp * 4 + 32 * hf;
-                *reinterpret_cast<uint32_t*>(o) = rh;
-                *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG) = rl;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG + 2 * MF_KP) = il;
+                store_image<MF_IMG>(buf + octet_row(u, orow) * MF_ROWB + pp * 4 + 32 * hf, rh, rl, ih, il);
             }
         }
         fetch(next_panel);
@@ -1208,9 +1036,11 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
         }
     };
 
+    fetch(blk.pbeg);
+    // two panels per trip: buffer addresses are compile-time offsets
     unsigned char* const buf0 = smem;
     unsigned char* const buf1 = smem + MF_BUF;
-    fetch(pbeg);
+    const int pbeg = blk.pbeg, pend = blk.pend;
     generate(buf0, min(pbeg + 1, pend - 1));
     __syncthreads();
     for (int panel = pbeg; panel < pend; panel += 2) {
@@ -1224,23 +1054,13 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
         __syncthreads();
     }
 
-    // epilogue: slab ws[split][t][f][re|im][Nbl] as in the generic kernel, through the tables of the virtual 128-row block
-    float* dst = A.ws + (((size_t)split * A.Nt + t) * A.Nf + f) * 2 * A.Nbl;
+    // epilogue: the block's slab as in the generic kernel, through the tables of the virtual 128-row block
+    float* dst = fwd_slab(A, blk);
     const float inv = 1.0f / scl;
-    const int col = lane & 31, rb = 4 * (lane >> 5);
+    const int col = lane & 31;
     RIME_MFMA_SETTLE();
-    auto put = [&](int r, int c, float vr, float vi) {            // V[r, c] = vr + i vi
-        const int bd = A.pair_direct[r * MF_NA + c];
-        if (bd >= 0) { dst[bd] = vr; dst[(size_t)A.Nbl + bd] = vi; }
-        const int bc = A.pair_conj[r * MF_NA + c];
-        if (bc >= 0) { dst[bc] = vr; dst[(size_t)A.Nbl + bc] = -vi; }
-    };
-    auto put1 = [&](int r, int c, int im, float v) {              // one plane of V[r, c]
-        const int bd = A.pair_direct[r * MF_NA + c];
-        if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
-        const int bc = A.pair_conj[r * MF_NA + c];
-        if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
-    };
+    auto put = [&](int r, int c, float vr, float vi) { rime::put(A, dst, r, c, vr, vi); };            // V[r, c] = vr + i vi
+    auto put1 = [&](int r, int c, int im, float v) { rime::put1(A, dst, r, c, im, v); };              // one plane of V[r, c]
     if constexpr (CEN) {
         // the hub's visibilities: sum the column sums over the 8 pixel-pair lanes and the two half-panel waves of a row
 #pragma unroll
@@ -1251,7 +1071,7 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
         if (pp == 0) {
 #pragma unroll
             for (int u = 0; u < NGEN; ++u)
-                if (u < nk) { cs[(hf * 64 + octet_row(u)) * 2] = cr[u]; cs[(hf * 64 + octet_row(u)) * 2 + 1] = ci[u]; }
+                if (u < nk) { cs[(hf * 64 + octet_row(u, orow)) * 2] = cr[u]; cs[(hf * 64 + octet_row(u, orow)) * 2 + 1] = ci[u]; }
         }
         __syncthreads();
         if (tid < A.Nant) {                          // (Nant <= 64: wave 0)
@@ -1271,16 +1091,7 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
     }
     // a private 32 x 33 float tile per wave takes the transposes (the image buffers are free after the loop's last barrier)
     float* tr = reinterpret_cast<float*>(smem) + W * (32 * 33);
-    auto transposed = [&](const f32x16& v) {
-        f32x16 tv;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) tr[((e & 3) + 8 * (e >> 2) + rb) * 33 + col] = v[e];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int e = 0; e < 16; ++e) tv[e] = tr[col * 33 + (e & 3) + 8 * (e >> 2) + rb];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        return tv;
-    };
+    auto transposed = [&](const f32x16& v) { return rime::transposed(tr, v, col, lane >> 5); };
     // Store order.  A wave's store instruction covers one accumulator element of all lanes: 32 consecutive COLUMNS of one row.
     // With the baselines in antenna order (the usual sim_bls) the slots of V[r, c .. c + 31] are consecutive when the lanes run
     // along the LATER antenna of the pair: true as they stand for V[i, j] and V[i, j'] (rows i, lanes j), but V[i', j'] and
@@ -1294,7 +1105,7 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
         const f32x16 st = transposed(s), dt = transposed(d);          // st[e] of lane c = s at (row c, column row(e))
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int re = (e & 3) + 8 * (e >> 2) + rb;
+            const int re = acc_row(e, lane >> 5);
             const int i = re, j = 32 + col;                               // as accumulated: rows i, lanes j
             const int it = col, jt = 32 + re;                             // transposed: rows j, lanes i
             if constexpr (W == 0) {                  // real parts: Ar = Pcc + Pss, Br = Pcc - Pss
@@ -1323,7 +1134,7 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
         for (int e = 0; e < 16; ++e) { ai[e] = x[e] - xt2[e]; bi[e] = y[e] + yt2[e]; }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int i = 32 * tt + (e & 3) + 8 * (e >> 2) + rb, j = 32 * tt + col;
+            const int i = 32 * tt + acc_row(e, lane >> 5), j = 32 * tt + col;
             put(i, j, ar[e] * inv, ai[e] * inv);
             put(64 + i, 64 + j, ar[e] * inv, -ai[e] * inv);
             put(i, 64 + j, br[e] * inv, -bi[e] * inv);            // conj(B[j,i]) = conj(B[i,j]) -> V[i, j']
@@ -1336,13 +1147,8 @@ __global__ void __launch_bounds__(256, 3)
 fringe_pair_fwd_kernel(PairArgs A)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (row_is_signed(A) != SIGNED) return;              // uniform over the block
-    switch (threadIdx.x >> 6) {                          // wave-uniform: every wave runs the same barriers
-        case 0: pair_fwd_body<0, SIGNED, CEN, FLAT>(A, smem); break;
-        case 1: pair_fwd_body<1, SIGNED, CEN, FLAT>(A, smem); break;
-        case 2: pair_fwd_body<2, SIGNED, CEN, FLAT>(A, smem); break;
-        default: pair_fwd_body<3, SIGNED, CEN, FLAT>(A, smem); break;
-    }
+    if (row_is_signed(A, fwd_block(A)) != SIGNED) return;        // uniform over the block
+    for_wave<4>([&](auto w) { pair_fwd_body<w(), SIGNED, CEN, FLAT>(A, smem); });
 }
 
 // Conjugate-pair form, ONE row tile (<= 32 rows; arrays of 33..64 antennas -- HERA-37: 18 pairs + the hub in 19 rows): the single
@@ -1356,81 +1162,62 @@ __device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char*
     using SH = FwdShape<1, 1, false>;
     constexpr int MF_IMG = SH::IMG, MF_BUF = SH::BUF;
     constexpr int KS = W & 1;
+    const FwdBlock blk = fwd_block(A);
     const int tid = threadIdx.x, lane = tid & 63;
-    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf), ts = blockIdx.x / A.Nf;
-    const int t = __builtin_amdgcn_readfirstlane(ts / A.S), split = __builtin_amdgcn_readfirstlane(ts % A.S);
+    const int f = blk.f, t = blk.t;
 
     const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
     const float scl = A.scale[t * A.Nf + f];
-    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
-    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
-    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
 
     // generation: this wave writes the 16-pixel half W & 1 for the two octets of the wave pair W >> 1 (rows 16 (W >> 1) + 8 u + i)
     const int pp = lane & 7, ag = lane >> 3;
     constexpr int hf = W & 1;
     constexpr int NGEN = 2;
-    const int orow = 16 * (W >> 1) + 2 * (ag & 3) + (ag >> 2);
+    const int orow = octet_lane_row(W, ag);
     const int nk = (16 * (W >> 1) < A.Nant) + (16 * (W >> 1) + 8 < A.Nant);          // sweeps whose octet starts below Nant
     double ax[NGEN], ay[NGEN], az[NGEN];
 #pragma unroll
     for (int u = 0; u < NGEN; ++u) {
-        const int an = 8 * u + orow;
-        const bool ok = an < A.Nant;
-        ax[u] = ok ? nu_c * A.antpos[3 * an] : 0.0;
-        ay[u] = ok ? nu_c * A.antpos[3 * an + 1] : 0.0;
-        az[u] = ok ? nu_c * A.antpos[3 * an + 2] : 0.0;
+        load_ant(A.antpos, 8 * u + orow, 8 * u + orow < A.Nant, nu_c, ax[u], ay[u], az[u]);
     }
     f32x16 acc0, acc1;                               // waves 0, 1: halves of Pcc, Pss; waves 2, 3: cs (hi x hi + hi x lo), sc (hi x lo)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
+    zero(acc0); zero(acc1);
 
-    const int npanel = A.Pstride / MF_KP;
-    const int pbeg = __builtin_amdgcn_readfirstlane(split * A.panels_per_split);
-    const int pend = __builtin_amdgcn_readfirstlane(min(npanel, pbeg + A.panels_per_split));
-    if (pbeg >= pend) return;                        // uniform over the block
+    if (blk.pbeg >= blk.pend) return;                // uniform over the block
 
     double2 sx, sy, sz = make_double2(0.0, 0.0); float2 av;
+    // panel source in place, offsets through readfirstlane (bit-stable results, no waterfall loop)
+    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
+    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
+    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
     const uint32_t lo_s = 16u * pp, lo_a0 = 8u * pp * (uint32_t)st_p, lo_a1 = lo_a0 + 4u * (uint32_t)st_p;
-    auto uniform_ptr = [](const void* q) {
-        const unsigned long long a = reinterpret_cast<unsigned long long>(q);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        return reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    };
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(sd), 0, __builtin_amdgcn_readfirstlane((int)min((long long)3 * A.Pstride * 8, 0x7fffffffLL)), 0x00020000);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(arow), 0, __builtin_amdgcn_readfirstlane((int)min((long long)A.Pstride * st_p * 4, 0x7fffffffLL)), 0x00020000);
     auto fetch = [&](int panel) {
         const int p0 = panel * MF_KP + 16 * hf;      // uniform
+        const int oy = __builtin_amdgcn_readfirstlane((A.Pstride + p0) * 8), oz = __builtin_amdgcn_readfirstlane((2 * A.Pstride + p0) * 8);
         sx = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, p0 * 8, 0));
-        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (A.Pstride + p0) * 8, 0));
-        if constexpr (!FLAT) sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (2 * A.Pstride + p0) * 8, 0));
-        const int so = p0 * st_p * 4;
+        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, oy, 0));
+        if constexpr (!FLAT) sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, oz, 0));
+        const int so = __builtin_amdgcn_readfirstlane(p0 * st_p * 4);
         av = make_float2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a0, so, 0)),
                          __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a1, so, 0)));
     };
     auto generate = [&](unsigned char* buf, int next_panel) {
-        const float w0 = __builtin_amdgcn_sqrtf(fabsf(av.x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av.y) * scl);
-        if (SIGNED && W < 2 && lane < 8)
-            *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) =
-                ((__float_as_uint(av.x) >> 16) & 0x8000u) | (__float_as_uint(av.y) & 0x80000000u);
+        float w0, w1;
+        pixel_weights(av, scl, w0, w1);
+        if (SIGNED && W < 2 && lane < 8) *reinterpret_cast<uint32_t*>(buf + 2 * MF_IMG + 4 * (8 * hf + pp)) = sign_dword(av);
 #pragma unroll
         for (int u = 0; u < NGEN; ++u) {
             if (u < nk) {
-                const double ph0 = phase_of<FLAT>(ax[u], sx.x, ay[u], sy.x, az[u], sz.x);
-                const double ph1 = phase_of<FLAT>(ax[u], sx.y, ay[u], sy.y, az[u], sz.y);
-                const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                float c0, s0, c1, s1;
+                phasor_pair<FLAT>(ax[u], ay[u], az[u], sx, sy, sz, c0, s0, c1, s1);
                 uint32_t rh, rl, ih, il;
                 split2(w0 * c0, w1 * c1, rh, rl);
                 split2(w0 * s0, w1 * s1, ih, il);
-                unsigned char* o = buf + (8 * u + orow) * MF_ROWB + pp * 4 + 32 * hf;
-                *reinterpret_cast<uint32_t*>(o) = rh;
-                *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG) = rl;
-                *reinterpret_cast<uint32_t*>(o + MF_IMG + 2 * MF_KP) = il;
+                store_image<MF_IMG>(buf + (8 * u + orow) * MF_ROWB + pp * 4 + 32 * hf, rh, rl, ih, il);
             }
         }
         fetch(next_panel);
@@ -1462,9 +1249,11 @@ __device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char*
         }
     };
 
+    fetch(blk.pbeg);
+    // two panels per trip: buffer addresses are compile-time offsets
     unsigned char* const buf0 = smem;
     unsigned char* const buf1 = smem + MF_BUF;
-    fetch(pbeg);
+    const int pbeg = blk.pbeg, pend = blk.pend;
     generate(buf0, min(pbeg + 1, pend - 1));
     __syncthreads();
     for (int panel = pbeg; panel < pend; panel += 2) {
@@ -1480,9 +1269,9 @@ __device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char*
 
     // epilogue: the odd wave of a pair hands its K step's partial tiles to the even one ([e][lane] floats behind the transposition
     // tiles); wave 0 finishes the real parts, wave 2 the imaginary parts
-    float* dst = A.ws + (((size_t)split * A.Nt + t) * A.Nf + f) * 2 * A.Nbl;
+    float* dst = fwd_slab(A, blk);
     const float inv = 1.0f / scl;
-    const int col = lane & 31, rb = 4 * (lane >> 5);
+    const int col = lane & 31;
     RIME_MFMA_SETTLE();
     float* ex = reinterpret_cast<float*>(smem) + 4 * (32 * 33) + (W >> 1) * (2 * 16 * 64);
     if constexpr ((W & 1) == 1) {
@@ -1494,22 +1283,8 @@ __device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char*
 #pragma unroll
     for (int e = 0; e < 16; ++e) { acc0[e] += ex[e * 64 + lane]; acc1[e] += ex[(16 + e) * 64 + lane]; }
     float* tr = reinterpret_cast<float*>(smem) + W * (32 * 33);
-    auto transposed = [&](const f32x16& v) {
-        f32x16 tv;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) tr[((e & 3) + 8 * (e >> 2) + rb) * 33 + col] = v[e];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int e = 0; e < 16; ++e) tv[e] = tr[col * 33 + (e & 3) + 8 * (e >> 2) + rb];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        return tv;
-    };
-    auto put1 = [&](int r, int c, int im, float v) {              // one plane of V[r, c] of the virtual 128-row block
-        const int bd = A.pair_direct[r * MF_NA + c];
-        if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
-        const int bc = A.pair_conj[r * MF_NA + c];
-        if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
-    };
+    auto transposed = [&](const f32x16& v) { return rime::transposed(tr, v, col, lane >> 5); };
+    auto put1 = [&](int r, int c, int im, float v) { rime::put1(A, dst, r, c, im, v); };      // one plane of V[r, c] of the virtual 128-row block
     f32x16 x, y;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -1519,7 +1294,7 @@ __device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char*
     const f32x16 xt = transposed(x), yt = transposed(y);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int i = (e & 3) + 8 * (e >> 2) + rb, j = col;
+        const int i = acc_row(e, lane >> 5), j = col;
         if constexpr (W == 0) {
             const float ar = (x[e] + xt[e]) * inv, br = (y[e] + yt[e]) * inv;
             put1(i, j, 0, ar); put1(64 + i, 64 + j, 0, ar); put1(i, 64 + j, 0, br);     // (B = B^T: lanes along the later antenna)
@@ -1535,13 +1310,8 @@ __global__ void __launch_bounds__(256, 2)
 fringe_pair_fwd1_kernel(PairArgs A)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (row_is_signed(A) != SIGNED) return;              // uniform over the block
-    switch (threadIdx.x >> 6) {                          // wave-uniform: every wave runs the same barriers
-        case 0: pair_fwd1_body<0, SIGNED, FLAT>(A, smem); break;
-        case 1: pair_fwd1_body<1, SIGNED, FLAT>(A, smem); break;
-        case 2: pair_fwd1_body<2, SIGNED, FLAT>(A, smem); break;
-        default: pair_fwd1_body<3, SIGNED, FLAT>(A, smem); break;
-    }
+    if (row_is_signed(A, fwd_block(A)) != SIGNED) return;        // uniform over the block
+    for_wave<4>([&](auto w) { pair_fwd1_body<w(), SIGNED, FLAT>(A, smem); });
 }
 
 // ---------------------------------------------------------------------------------------

@@ -81,6 +81,230 @@ __device__ __forceinline__ f16x8 as_frag(const uint4& v) { return __builtin_bit_
 
 #define RIME_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(as_frag(a), as_frag(b), c, 0, 0, 0)
 
+// ---- device fragments of the forward kernels ------------------------------------------------------------
+// What ant_fwd_body, ant_fwd_packed_body, pair_fwd_body, pair_fwd1_body (fringe_mfma.hip) and xpair_fwd_body (fringe_xpair.hip)
+// share, once each, all forced inline.  KNOWN WEAKNESS: the f64 phase ax sx + ay sy + az sz is contracted by the compiler
+// (-ffp-contract=fast), and which product stays a rounded multiply is its choice for every inlined copy of `generate`, so the
+// last bit of a few visibilities per 10^6 depends on code structure.  A body uses a fragment only where tools/fringe_digest.py
+// prints the same lines with and without it; DESIGN.md 5.1f lists what is written out where.  Follow-up: explicit fma() in
+// phase3 / phase_of (an arithmetic change, to be made on its own), after which every body can take every fragment.
+constexpr int MF_NA = 128;                      // antennas per block (4 x 4 tiles): rows / columns of the slot tables
+constexpr int MF_NH = MF_KP / 16;               // 16-pixel K steps per panel
+constexpr int MF_ROWB = 4 * MF_KP + 16;         // image row: [re KP x f16][im KP x f16][pad], an odd number of 16-B granules
+
+// 1. Block coordinates.  1-D grid, channel fastest: blocks that run together share (t, split), i.e. the same pointing vectors
+// (L2 hits), and no grid dimension hits the 65535 cap.  Panels [pbeg, pend) are this block's pixel split.
+struct FwdBlock { int f, t, split, pbeg, pend; };
+template <class Args>
+__device__ __forceinline__ FwdBlock fwd_block(const Args& A)
+{
+    FwdBlock b;
+    b.f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf);
+    const int ts = blockIdx.x / A.Nf;
+    b.t = __builtin_amdgcn_readfirstlane(ts / A.S);
+    b.split = __builtin_amdgcn_readfirstlane(ts % A.S);
+    b.pbeg = __builtin_amdgcn_readfirstlane(b.split * A.panels_per_split);
+    b.pend = __builtin_amdgcn_readfirstlane(min(A.Pstride / MF_KP, b.pbeg + A.panels_per_split));
+    return b;
+}
+// A block works on one psky row (t, f): rows without a negative value (beam-weighted emission is non-negative) take the kernel
+// instantiation without sign masks.  Both instantiations are launched over the full grid and a block returns at once when its
+// row belongs to the other one: a branch inside one kernel costs registers (the allocator serves the union of both paths and spills).
+template <class Args>
+__device__ __forceinline__ bool row_is_signed(const Args& A, const FwdBlock& b)
+{
+    if (!A.rowmin) return true;
+    return A.rowmin[b.t * A.Nf + b.f] < 0.f;
+}
+
+// 2. Panel source.  Wave-uniform bases (scalar address arithmetic) + constant 32-bit lane offsets; psky is read as two dwords
+// with the runtime pixel stride (a branch on the stride makes the compiler issue both variants with 64-bit vector multiplies:
+// 17 % of the loop's VALU work).  Buffer loads: descriptor (SGPRs, wave-uniform: built from kernel arguments and the block
+// index) + constant per-lane offset + scalar panel offset -- no vector address arithmetic in the generation phase, whose cost
+// is its instruction count (profiles/r03/lab_forward_experiments.txt); the descriptors bound the fetch to the row ([3][Pstride]
+// doubles of sdir, Pstride strided floats of psky) and out-of-range reads return 0 instead of faulting.  The descriptor inputs
+// go through readfirstlane: a base pointer the compiler cannot PROVE wave-uniform makes it wrap every buffer load in a
+// waterfall loop of ~14 instructions -- seen on the psky descriptor, guide T20.
+__device__ __forceinline__ void* uniform_ptr(const void* q)
+{
+    const unsigned long long a = reinterpret_cast<unsigned long long>(q);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
+}
+struct PanelSource {
+    __amdgpu_buffer_rsrc_t rs, ra;               // the three sdir rows of time t; the psky row (t, f)
+    uint32_t lo_s, lo_a0, lo_a1;                 // lane offsets of pixel pair pp: its two directions, its two psky values
+    int Pstride, st_p;
+};
+template <class Args>
+__device__ __forceinline__ PanelSource panel_source(const Args& A, const FwdBlock& b, int pp)
+{
+    const float* arow = A.psky + (size_t)b.t * A.st_t + (size_t)b.f * A.st_f;
+    const double* sd = A.sdir + (size_t)b.t * 3 * A.Pstride;
+    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
+    PanelSource s;
+    s.Pstride = A.Pstride; s.st_p = st_p;
+    s.lo_s = 16u * pp; s.lo_a0 = 8u * pp * (uint32_t)st_p; s.lo_a1 = s.lo_a0 + 4u * (uint32_t)st_p;
+    s.rs = __builtin_amdgcn_make_buffer_rsrc(
+        uniform_ptr(sd), 0, __builtin_amdgcn_readfirstlane((int)min((long long)3 * A.Pstride * 8, 0x7fffffffLL)), 0x00020000);
+    s.ra = __builtin_amdgcn_make_buffer_rsrc(
+        uniform_ptr(arow), 0, __builtin_amdgcn_readfirstlane((int)min((long long)A.Pstride * st_p * 4, 0x7fffffffLL)), 0x00020000);
+    return s;
+}
+// the directions of this lane's pixel pair in the 16-pixel half `hf` of `panel`
+__device__ __forceinline__ void fetch_dirs(const PanelSource& s, int panel, int hf, double2& sx, double2& sy, double2& sz)
+{
+    const int p0 = panel * MF_KP + 16 * hf;          // uniform
+    sx = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.rs, (int)s.lo_s, p0 * 8, 0));
+    sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.rs, (int)s.lo_s, (s.Pstride + p0) * 8, 0));
+    sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(s.rs, (int)s.lo_s, (2 * s.Pstride + p0) * 8, 0));
+}
+// ... and its two psky values: the real plane (av), with CPLX the imaginary plane too (aw)
+template <bool CPLX>
+__device__ __forceinline__ void fetch_psky(const PanelSource& s, int panel, int hf, float2& av, float2& aw)
+{
+    const int so = (panel * MF_KP + 16 * hf) * s.st_p * 4;
+    av = make_float2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.ra, (int)s.lo_a0, so, 0)),
+                     __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.ra, (int)s.lo_a1, so, 0)));
+    if constexpr (CPLX)
+        aw = make_float2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.ra, (int)s.lo_a0 + 4, so, 0)),
+                         __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.ra, (int)s.lo_a1 + 4, so, 0)));
+}
+__device__ __forceinline__ void fetch_psky(const PanelSource& s, int panel, int hf, float2& av)
+{
+    fetch_psky<false>(s, panel, hf, av, av);
+}
+
+// 3. Row mapping of the half-panel generation: lane = (pixel pair pp = lane & 7, row ag = lane >> 3 of an octet); the rows of a
+// sweep are one OCTET per wave pair p = W >> 1 -- 2 apart inside a wave: conflict-free ds_write_b32 -- and the sweeps of a wave
+// pair walk the octets of ONE 16-row group after the other: sweep u = rows 32 (u >> 1) + 16 p + 8 (u & 1) + i, so that the
+// mirror antennas of a sweep's rows (AntArgs.mirror) are the next sweep's rows of the same lanes.
+__device__ __forceinline__ int octet_lane_row(int W, int ag) { return 16 * (W >> 1) + 2 * (ag & 3) + (ag >> 2); }
+__device__ __forceinline__ int octet_row(int u, int orow) { return 32 * (u >> 1) + 8 * (u & 1) + orow; }
+// sweeps whose octet starts below Nant (monotone in u; uniform): the others are whole octets of padding and are skipped
+__device__ __forceinline__ int octet_sweeps(int Nant, int W, int ngen)
+{
+    const int mrow = Nant - 16 * (W >> 1);
+    return min(ngen, (max(mrow, 0) + 31) / 32 + (max(mrow - 8, 0) + 31) / 32);
+}
+// coordinates of antenna `an` scaled by sign nu / c; zero for a padding row
+__device__ __forceinline__ void load_ant(const double* antpos, int an, bool ok, double nu_c, double& ax, double& ay, double& az)
+{
+    ax = ok ? nu_c * antpos[3 * an] : 0.0;
+    ay = ok ? nu_c * antpos[3 * an + 1] : 0.0;
+    az = ok ? nu_c * antpos[3 * an + 2] : 0.0;
+}
+
+// 4. Phasor pair: E = c + i s of the antenna at (bx, by, bz) for the lane's two pixels (.x and .y of the directions)
+template <bool FLAT>
+__device__ __forceinline__ void phasor_pair(double bx, double by, double bz, const double2& sx, const double2& sy,
+                                            const double2& sz, float& c0, float& s0, float& c1, float& s1)
+{
+    const double ph0 = phase_of<FLAT>(bx, sx.x, by, sy.x, bz, sz.x);
+    const double ph1 = phase_of<FLAT>(bx, sx.y, by, sy.y, bz, sz.y);
+    const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
+    s0 = __builtin_amdgcn_sinf(r0); c0 = __builtin_amdgcn_cosf(r0);
+    s1 = __builtin_amdgcn_sinf(r1); c1 = __builtin_amdgcn_cosf(r1);
+}
+
+// 5. Weights of the symmetric form, w = sqrt(|psky| scale) for the lane's two pixels; g: the same with the sign of psky (SIGNED
+// ROWS in fringe_mfma.hip); sign_dword: the signs as the XOR mask of a packed f16 pair, stored behind the images of a panel
+__device__ __forceinline__ void pixel_weights(const float2& av, float scl, float& w0, float& w1)
+{
+    w0 = __builtin_amdgcn_sqrtf(fabsf(av.x) * scl); w1 = __builtin_amdgcn_sqrtf(fabsf(av.y) * scl);
+}
+__device__ __forceinline__ void signed_weights(const float2& av, float w0, float w1, float& g0, float& g1)
+{
+    g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av.x) & 0x80000000u));
+    g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av.y) & 0x80000000u));
+}
+__device__ __forceinline__ uint32_t sign_dword(const float2& av)
+{
+    return ((__float_as_uint(av.x) >> 16) & 0x8000u) | (__float_as_uint(av.y) & 0x80000000u);
+}
+
+// 6. Image store: the packed f16 (p, p + 1) pairs of one row at o = row and half-panel offset; IMG = bytes of the hi image
+template <int IMG>
+__device__ __forceinline__ void store_image(unsigned char* o, uint32_t rh, uint32_t rl, uint32_t ih, uint32_t il)
+{
+    *reinterpret_cast<uint32_t*>(o) = rh;
+    *reinterpret_cast<uint32_t*>(o + 2 * MF_KP) = ih;
+    *reinterpret_cast<uint32_t*>(o + IMG) = rl;
+    *reinterpret_cast<uint32_t*>(o + IMG + 2 * MF_KP) = il;
+}
+
+// 7. Accumulators.  Element e of a 32 x 32 accumulator is row acc_row(e, lane >> 5), column lane & 31.
+__device__ __forceinline__ void zero(f32x16& a)
+{
+#pragma unroll
+    for (int e = 0; e < 16; ++e) a[e] = 0.f;
+}
+__device__ __forceinline__ int acc_row(int e, int half) { return (e & 3) + 8 * (e >> 2) + 4 * half; }
+// the transpose of a tile through a private 32 x 33 float tile of LDS (written and read by this wave only)
+__device__ __forceinline__ f32x16 transposed(float* tr, const f32x16& v, int col, int half)
+{
+    f32x16 tv;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) tr[acc_row(e, half) * 33 + col] = v[e];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int e = 0; e < 16; ++e) tv[e] = tr[col * 33 + acc_row(e, half)];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    return tv;
+}
+// This block's slab ws[split][t][f][re|im][Nbl]: consecutive lanes (columns j) hit consecutive baseline slots, so the stores
+// coalesce (a scattered store into the [Nbl][Nt][Nf][2] result costs a 32-B sector per 4-B value: 8 GB instead of 1.6 GB per
+// launch at C4); reduce_vis_kernel sums the splits in a fixed order and transposes into the result layout.
+template <class Args>
+__device__ __forceinline__ float* fwd_slab(const Args& A, const FwdBlock& b)
+{
+    return A.ws + (((size_t)b.split * A.Nt + b.t) * A.Nf + b.f) * 2 * A.Nbl;
+}
+// V[r, c] = vr + i vi -> the baseline slot(s) of pair (r, c) in the slab; put1: one plane of it
+template <class Args>
+__device__ __forceinline__ void put(const Args& A, float* dst, int r, int c, float vr, float vi)
+{
+    const int bd = A.pair_direct[r * MF_NA + c];
+    if (bd >= 0) { dst[bd] = vr; dst[(size_t)A.Nbl + bd] = vi; }
+    const int bc = A.pair_conj[r * MF_NA + c];
+    if (bc >= 0) { dst[bc] = vr; dst[(size_t)A.Nbl + bc] = -vi; }
+}
+template <class Args>
+__device__ __forceinline__ void put1(const Args& A, float* dst, int r, int c, int im, float v)
+{
+    const int bd = A.pair_direct[r * MF_NA + c];
+    if (bd >= 0) dst[(size_t)im * A.Nbl + bd] = v;
+    const int bc = A.pair_conj[r * MF_NA + c];
+    if (bc >= 0) dst[(size_t)im * A.Nbl + bc] = im ? -v : v;
+}
+
+// 8. Wave dispatch: go(int_c<W>{}) for this thread's wave W of NW.  Wave-uniform: every wave runs the same barriers.
+template <int NW, class F>
+__device__ __forceinline__ void for_wave(F&& go)
+{
+    static_assert(NW == 4 || NW == 8, "blocks of four or eight waves");
+    const int w = threadIdx.x >> 6;
+    if constexpr (NW == 4) {
+        switch (w) {
+            case 0: go(int_c<0>{}); break;
+            case 1: go(int_c<1>{}); break;
+            case 2: go(int_c<2>{}); break;
+            default: go(int_c<3>{}); break;
+        }
+    } else {
+        switch (w) {
+            case 0: go(int_c<0>{}); break;
+            case 1: go(int_c<1>{}); break;
+            case 2: go(int_c<2>{}); break;
+            case 3: go(int_c<3>{}); break;
+            case 4: go(int_c<4>{}); break;
+            case 5: go(int_c<5>{}); break;
+            case 6: go(int_c<6>{}); break;
+            default: go(int_c<7>{}); break;
+        }
+    }
+}
+
 // ---- host: from the arguments of a block entry point to its launches -----------------------------------------------------
 // An A/B switch of the environment: atoi of the variable, `dflt` where it is not set.  A caller keeps the answer in a
 // function-local static, so that the variable is read once, on first use.

@@ -29,16 +29,14 @@
 namespace rime {
 namespace xp {
 
-constexpr int NA = 128;                      // rows / columns of the slot tables (virtual block: 64 firsts + 64 mirrors a side)
+constexpr int NA = MF_NA;                    // rows / columns of the slot tables (virtual block: 64 firsts + 64 mirrors a side)
 constexpr int XR = 64;                       // rows of one group
-constexpr int KP = 32;                       // pixels per panel; 16 per MFMA
-constexpr int NH = KP / 16;
-constexpr int ROWB = 4 * KP + 16;            // [re KP x f16][im KP x f16][pad]: odd number of 16-B granules
+constexpr int KP = MF_KP;                    // pixels per panel; 16 per MFMA
+constexpr int NH = MF_NH;
+constexpr int ROWB = MF_ROWB;                // [re KP x f16][im KP x f16][pad]: odd number of 16-B granules
 constexpr int IMG = 2 * XR * ROWB;           // one image (hi or lo): rows 0..63 group I, 64..127 group J
 constexpr int BUF = 2 * IMG + 64;            // hi + lo (+ 64 bytes that held the panel's sign dwords: unused, the offsets stay)
 constexpr size_t FWD_LDS = 2 * (size_t)BUF;
-
-static_assert(KP == MF_KP, "the forward split plan (fringe_mfma_common.h) counts panels of MF_KP pixels");
 
 struct FwdArgs {
     const double* antpos;      // [rows_i + rows_j, 3] from the centre of symmetry: group I, then group J
@@ -56,114 +54,85 @@ struct FwdArgs {
     double sign;
 };
 
-__device__ __forceinline__ bool row_is_signed(const FwdArgs& A)
-{
-    if (!A.rowmin) return true;
-    const int f = blockIdx.x % A.Nf, t = (blockIdx.x / A.Nf) / A.S;
-    return A.rowmin[t * A.Nf + f] < 0.f;
-}
-
 // Forward.  Block = one (t, f, pixel split), four waves.  Generation as in the pair kernels: lane = (pixel pair, row of an octet),
 // a wave writes one 16-pixel half of the panel for every second 16-row group of the 128 image rows (8 sweeps; octets that hold
 // padding rows only are skipped).  Symmetric weighting: both groups' rows hold sqrt(|psky| scale) E, and the rows of group I are
 // GENERATED with the sign of psky in their weight (SIGNED ROWS in fringe_mfma.hip: L always comes from group I, B from group J, so
 // no fragment is signed after it is read; the stored f16 pairs are bit for bit those an XOR mask on the group-I fragments gave:
 // cvt_pkrtz is odd, the residual of the split an exact negation).  Wave W contracts output tile (W >> 1, W & 1): Pcc, Pss, Pcs, Psc in four accumulators, 12
-// MFMAs per K step.
+// MFMAs per K step.  The pieces shared with the other forward kernels are the fragments of fringe_mfma_common.h.
 template <int W, bool SIGNED, bool FLAT>
 __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* smem)
 {
+    const FwdBlock blk = fwd_block(A);
     const int tid = threadIdx.x, lane = tid & 63;
-    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf), ts = blockIdx.x / A.Nf;
-    const int t = __builtin_amdgcn_readfirstlane(ts / A.S), split = __builtin_amdgcn_readfirstlane(ts % A.S);
+    const int f = blk.f, t = blk.t;
 
     const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
     const float scl = A.scale[t * A.Nf + f];
-    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
-    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
-    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
 
     const int pp = lane & 7, ag = lane >> 3;
     constexpr int hf = W & 1;
     constexpr int NGEN = 8;
-    const int orow = 16 * (W >> 1) + 2 * (ag & 3) + (ag >> 2);
-    auto octet_row = [&](int u) { return 32 * (u >> 1) + 8 * (u & 1) + orow; };      // image row of this lane in sweep u
+    const int orow = octet_lane_row(W, ag);
     // sweeps whose octet holds a row of its group (uniform over the wave)
     uint32_t live = 0;
     double ax[NGEN], ay[NGEN], az[NGEN];
 #pragma unroll
     for (int u = 0; u < NGEN; ++u) {
-        const int base = 32 * (u >> 1) + 8 * (u & 1) + 16 * (W >> 1);
+        const int base = octet_row(u, 16 * (W >> 1));
         const bool on = base < XR ? base < A.rows_i : base - XR < A.rows_j;
         live |= (on ? 1u : 0u) << u;
-        const int r = octet_row(u);
+        const int r = octet_row(u, orow);            // image row of this lane in sweep u
         const bool ok = r < XR ? r < A.rows_i : r - XR < A.rows_j;
-        const int an = r < XR ? r : A.rows_i + (r - XR);
-        ax[u] = ok ? nu_c * A.antpos[3 * an] : 0.0;
-        ay[u] = ok ? nu_c * A.antpos[3 * an + 1] : 0.0;
-        az[u] = ok ? nu_c * A.antpos[3 * an + 2] : 0.0;
+        load_ant(A.antpos, r < XR ? r : A.rows_i + (r - XR), ok, nu_c, ax[u], ay[u], az[u]);
     }
     live = __builtin_amdgcn_readfirstlane(live);
 
     f32x16 acc[4];                                   // 0 Pcc, 1 Pss, 2 Pcs, 3 Psc
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
+    for (int s = 0; s < 4; ++s) zero(acc[s]);
 
-    const int npanel = A.Pstride / KP;
-    const int pbeg = __builtin_amdgcn_readfirstlane(split * A.panels_per_split);
-    const int pend = __builtin_amdgcn_readfirstlane(min(npanel, pbeg + A.panels_per_split));
-    if (pbeg >= pend) return;                        // uniform over the block
+    if (blk.pbeg >= blk.pend) return;                // uniform over the block
 
     double2 sx, sy, sz = make_double2(0.0, 0.0); float2 av;
+    // panel source in place, offsets through readfirstlane (bit-stable results, no waterfall loop)
+    const float* arow = A.psky + (size_t)t * A.st_t + (size_t)f * A.st_f;
+    const double* sd = A.sdir + (size_t)t * 3 * A.Pstride;
+    const int st_p = __builtin_amdgcn_readfirstlane((int)A.st_p);
     const uint32_t lo_s = 16u * pp, lo_a0 = 8u * pp * (uint32_t)st_p, lo_a1 = lo_a0 + 4u * (uint32_t)st_p;
-    auto uniform_ptr = [](const void* q) {
-        const unsigned long long a = reinterpret_cast<unsigned long long>(q);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-        return reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-    };
-    // buffer descriptors bound the panel fetch to the row: [3][Pstride] doubles of sdir, Pstride strided floats of psky
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(sd), 0, __builtin_amdgcn_readfirstlane((int)min((long long)3 * A.Pstride * 8, 0x7fffffffLL)), 0x00020000);
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr(arow), 0, __builtin_amdgcn_readfirstlane((int)min((long long)A.Pstride * st_p * 4, 0x7fffffffLL)), 0x00020000);
     auto fetch = [&](int panel) {
         const int p0 = panel * KP + 16 * hf;         // uniform
+        const int oy = __builtin_amdgcn_readfirstlane((A.Pstride + p0) * 8), oz = __builtin_amdgcn_readfirstlane((2 * A.Pstride + p0) * 8);
         sx = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, p0 * 8, 0));
-        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (A.Pstride + p0) * 8, 0));
-        if constexpr (!FLAT) sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, (2 * A.Pstride + p0) * 8, 0));
-        const int so = p0 * st_p * 4;
+        sy = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, oy, 0));
+        if constexpr (!FLAT) sz = __builtin_bit_cast(double2, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)lo_s, oz, 0));
+        const int so = __builtin_amdgcn_readfirstlane(p0 * st_p * 4);
         av = make_float2(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a0, so, 0)),
                          __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, (int)lo_a1, so, 0)));
     };
     auto generate = [&](unsigned char* buf, int next_panel) {
-        const float w0 = __builtin_amdgcn_sqrtf(fabsf(av.x) * scl), w1 = __builtin_amdgcn_sqrtf(fabsf(av.y) * scl);
+        float w0, w1;
+        pixel_weights(av, scl, w0, w1);
         // the weight of group I's rows (sweeps 0..3) carries the sign of psky
         float g0 = w0, g1 = w1;
-        if constexpr (SIGNED) {
-            g0 = __uint_as_float(__float_as_uint(w0) | (__float_as_uint(av.x) & 0x80000000u));
-            g1 = __uint_as_float(__float_as_uint(w1) | (__float_as_uint(av.y) & 0x80000000u));
-        }
+        if constexpr (SIGNED) signed_weights(av, w0, w1, g0, g1);
 #pragma unroll
         for (int u = 0; u < NGEN; ++u) {
             if ((live >> u) & 1u) {
                 const float m0 = u < 4 ? g0 : w0, m1 = u < 4 ? g1 : w1;
-                const double ph0 = phase_of<FLAT>(ax[u], sx.x, ay[u], sy.x, az[u], sz.x);
-                const double ph1 = phase_of<FLAT>(ax[u], sx.y, ay[u], sy.y, az[u], sz.y);
-                const float r0 = turn_frac(ph0), r1 = turn_frac(ph1);
-                const float s0 = __builtin_amdgcn_sinf(r0), c0 = __builtin_amdgcn_cosf(r0);
-                const float s1 = __builtin_amdgcn_sinf(r1), c1 = __builtin_amdgcn_cosf(r1);
+                float c0, s0, c1, s1;
+                phasor_pair<FLAT>(ax[u], ay[u], az[u], sx, sy, sz, c0, s0, c1, s1);
                 float xr0 = m0 * c0, xr1 = m1 * c1, xi0 = m0 * s0, xi1 = m1 * s1;
                 keep_scalar(xr0); keep_scalar(xr1); keep_scalar(xi0); keep_scalar(xi1);
                 uint32_t rh, rl, ih, il;
                 split2(xr0, xr1, rh, rl);
                 split2(xi0, xi1, ih, il);
-                unsigned char* o = buf + octet_row(u) * ROWB + pp * 4 + 32 * hf;
-                *reinterpret_cast<uint32_t*>(o) = rh;
-                *reinterpret_cast<uint32_t*>(o + 2 * KP) = ih;
-                *reinterpret_cast<uint32_t*>(o + IMG) = rl;
-                *reinterpret_cast<uint32_t*>(o + IMG + 2 * KP) = il;
+                store_image<IMG>(buf + octet_row(u, orow) * ROWB + pp * 4 + 32 * hf, rh, rl, ih, il);
             }
         }
         fetch(next_panel);
@@ -196,9 +165,11 @@ __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* 
         }
     };
 
+    fetch(blk.pbeg);
+    // two panels per trip: buffer addresses are compile-time offsets
     unsigned char* const buf0 = smem;
     unsigned char* const buf1 = smem + BUF;
-    fetch(pbeg);
+    const int pbeg = blk.pbeg, pend = blk.pend;
     generate(buf0, min(pbeg + 1, pend - 1));
     __syncthreads();
     for (int panel = pbeg; panel < pend; panel += 2) {
@@ -212,29 +183,23 @@ __device__ __forceinline__ void xpair_fwd_body(const FwdArgs& A, unsigned char* 
         __syncthreads();
     }
 
-    // epilogue: slab ws[split][t][f][re | im][Nbl] through the tables of the virtual 128 x 128 block
-    float* dst = A.ws + (((size_t)split * A.Nt + t) * A.Nf + f) * 2 * A.Nbl;
+    // epilogue: the block's slab through the tables of the virtual 128 x 128 block
+    float* dst = fwd_slab(A, blk);
     const float inv = 1.0f / scl;
-    const int col = lane & 31, rb = 4 * (lane >> 5);
+    const int col = lane & 31;
     RIME_MFMA_SETTLE();
-    auto put = [&](int r, int c, float vr, float vi) {            // V[r, c] = vr + i vi
-        const int bd = A.pair_direct[r * NA + c];
-        if (bd >= 0) { dst[bd] = vr; dst[(size_t)A.Nbl + bd] = vi; }
-        const int bc = A.pair_conj[r * NA + c];
-        if (bc >= 0) { dst[bc] = vr; dst[(size_t)A.Nbl + bc] = -vi; }
-    };
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int i = 32 * ti + (e & 3) + 8 * (e >> 2) + rb, j = 32 * tj + col;
+        const int i = 32 * ti + acc_row(e, lane >> 5), j = 32 * tj + col;
         float ar = acc[0][e] + acc[1][e]; keep_scalar(ar);
         float br = acc[0][e] - acc[1][e]; keep_scalar(br);
         float ai = acc[2][e] - acc[3][e]; keep_scalar(ai);
         float bi = acc[2][e] + acc[3][e]; keep_scalar(bi);
         ar *= inv; keep_scalar(ar); br *= inv; keep_scalar(br); ai *= inv; keep_scalar(ai); bi *= inv; keep_scalar(bi);
-        put(i, j, ar, ai);                           // x  -> y
-        put(XR + i, XR + j, ar, -ai);                // x' -> y'
-        put(XR + i, j, br, bi);                      // x' -> y
-        put(i, XR + j, br, -bi);                     // x  -> y'
+        put(A, dst, i, j, ar, ai);                   // x  -> y
+        put(A, dst, XR + i, XR + j, ar, -ai);        // x' -> y'
+        put(A, dst, XR + i, j, br, bi);              // x' -> y
+        put(A, dst, i, XR + j, br, -bi);             // x  -> y'
     }
 }
 
@@ -243,13 +208,8 @@ __global__ void __launch_bounds__(256, 2)
 fringe_xpair_fwd_kernel(FwdArgs A)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (row_is_signed(A) != SIGNED) return;              // uniform over the block
-    switch (threadIdx.x >> 6) {                          // wave-uniform: every wave runs the same barriers
-        case 0: xpair_fwd_body<0, SIGNED, FLAT>(A, smem); break;
-        case 1: xpair_fwd_body<1, SIGNED, FLAT>(A, smem); break;
-        case 2: xpair_fwd_body<2, SIGNED, FLAT>(A, smem); break;
-        default: xpair_fwd_body<3, SIGNED, FLAT>(A, smem); break;
-    }
+    if (row_is_signed(A, fwd_block(A)) != SIGNED) return;        // uniform over the block
+    for_wave<4>([&](auto w) { xpair_fwd_body<w(), SIGNED, FLAT>(A, smem); });
 }
 
 struct BwdArgs {
