@@ -26,6 +26,16 @@ _ip = ctypes.POINTER(ctypes.c_int)
 _llp = ctypes.POINTER(ctypes.c_longlong)
 _ll = ctypes.c_longlong
 
+
+
+class FringeSegment(ctypes.Structure):
+    """rime_fringe_segment of include/rime_hip.h: what one psky plane of a merged pair launch has of its own"""
+    _fields_ = [('sdir', _vp), ('psky', _vp), ('scale', _vp), ('rowmin', _vp), ('gpsky', _vp),
+                ('st_t', _ll), ('st_f', _ll), ('st_p', _ll), ('Pstride', _i), ('accumulate', _i)]
+
+
+_segp = ctypes.POINTER(FringeSegment)
+
 # symbol -> (restype, argtypes); mirrors include/rime_hip.h one to one
 SIGNATURES = {
     'rime_version': (ctypes.c_char_p, []),
@@ -52,6 +62,11 @@ SIGNATURES = {
     'rime_fringe_pair_bwd_block': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i, _i,
                                         _vp, _vp, _sz, _vp]),
     'rime_fringe_pair_bwd_splits': (_i, [_i, _i, _i]),
+    'rime_fringe_pair_segments_workspace': (_sz, [_i, _i, _i, _ip, _i]),
+    'rime_fringe_pair_segments_map': (_i, [_i, _i, _i, _ip, _i, _ip, ctypes.c_long]),
+    'rime_fringe_pair_fwd_segments': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _segp, _i, _vp, _sz, _vp]),
+    'rime_fringe_pair_segments_finish': (_i, [_vp, _sz, _vp, _i, _i, _i, _ip, _i, _vp]),
+    'rime_fringe_pair_bwd_segments': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _segp, _i, _vp, _sz, _vp]),
     'rime_fringe_pair_cross_fwd_block': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i,
                                               _vp, _sz, _vp]),
     'rime_fringe_pair_cross_bwd_block': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _i, _i,

@@ -891,16 +891,43 @@ fringe_ant_fwd_packed_kernel(AntArgs A)
 // the panel's sign dwords on their L fragments, which toggles: the unsigned side of tile 0's rows, the signed side of tile 1's.
 // The hub's column sums multiply by the weight the row does NOT carry (w on signed rows, +-w on unsigned ones).
 // ---------------------------------------------------------------------------------------
-struct PairArgs : AntArgs {
+struct PairBlock : AntArgs {
     const int* centre;         // CEN: [2][128] baseline slots receiving V[c, r] (first 128) / conj(V[c, r]) (last 128), r = virtual row
+    unsigned block0;           // first block of this block's segment in the grid (0: a launch of one segment)
 };
+// SEGMENTS.  A launch serves nseg <= MF_MAXSEG psky planes on the same rows, tables, times and channels -- the
+// sky components of one RIME call: `base` holds what they share, seg[] what each has of its own, in GRID order (the host puts
+// the segment with the most pixels first, so that the short blocks of the others fill the tail of the grid).  A block finds
+// its segment with scalar compares (segment_of) and copies that segment's fields over `base`: the bodies below read ONE
+// PairBlock as they did when a launch had one plane, all of it in SGPRs.  Slabs: seg.ws is the segment's first slab in the
+// workspace of the whole launch, in the caller's order of segments -- the order reduce_vis_kernel sums in.
+struct PairSeg {
+    const float* psky; const double* sdir; const float* scale; const float* rowmin; float* ws;
+    long long st_t, st_f, st_p;
+    int Pstride, S, panels_per_split;
+    unsigned block0;
+};
+struct PairArgs {
+    PairBlock base;
+    int nseg;
+    PairSeg seg[MF_MAXSEG];
+};
+__device__ __forceinline__ PairBlock pair_block_args(const PairArgs& G)
+{
+    PairBlock A = G.base;
+    const PairSeg& s = G.seg[segment_of(G.seg, G.nseg)];
+    A.psky = s.psky; A.sdir = s.sdir; A.scale = s.scale; A.rowmin = s.rowmin; A.ws = s.ws;
+    A.st_t = s.st_t; A.st_f = s.st_f; A.st_p = s.st_p;
+    A.Pstride = s.Pstride; A.S = s.S; A.panels_per_split = s.panels_per_split; A.block0 = s.block0;
+    return A;
+}
 
 template <int W, bool SIGNED, bool CEN, bool FLAT>
-__device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* smem)
+__device__ __forceinline__ void pair_fwd_body(const PairBlock& A, unsigned char* smem)
 {
     using SH = FwdShape<2, 2, false>;
     constexpr int MF_IMG = SH::IMG, MF_BUF = SH::BUF;
-    const FwdBlock blk = fwd_block(A);
+    const FwdBlock blk = fwd_block_at(A, blockIdx.x - A.block0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int f = blk.f, t = blk.t;
 
@@ -1144,10 +1171,11 @@ __device__ __forceinline__ void pair_fwd_body(const PairArgs& A, unsigned char* 
 
 template <bool SIGNED, bool CEN, bool FLAT>
 __global__ void __launch_bounds__(256, 3)
-fringe_pair_fwd_kernel(PairArgs A)
+fringe_pair_fwd_kernel(PairArgs G)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (row_is_signed(A, fwd_block(A)) != SIGNED) return;        // uniform over the block
+    const PairBlock A = pair_block_args(G);
+    if (row_is_signed(A, fwd_block_at(A, blockIdx.x - A.block0)) != SIGNED) return;        // uniform over the block
     for_wave<4>([&](auto w) { pair_fwd_body<w(), SIGNED, CEN, FLAT>(A, smem); });
 }
 
@@ -1157,12 +1185,12 @@ fringe_pair_fwd_kernel(PairArgs A)
 // waves 2, 3 the two accumulators of Pcs (3); the odd wave of a pair hands its partial tiles to the even one in the epilogue.
 // No hub path: an array whose rows exceed 32 takes the two-tile kernel.
 template <int W, bool SIGNED, bool FLAT>
-__device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char* smem)
+__device__ __forceinline__ void pair_fwd1_body(const PairBlock& A, unsigned char* smem)
 {
     using SH = FwdShape<1, 1, false>;
     constexpr int MF_IMG = SH::IMG, MF_BUF = SH::BUF;
     constexpr int KS = W & 1;
-    const FwdBlock blk = fwd_block(A);
+    const FwdBlock blk = fwd_block_at(A, blockIdx.x - A.block0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int f = blk.f, t = blk.t;
 
@@ -1307,10 +1335,11 @@ __device__ __forceinline__ void pair_fwd1_body(const PairArgs& A, unsigned char*
 
 template <bool SIGNED, bool FLAT>
 __global__ void __launch_bounds__(256, 2)
-fringe_pair_fwd1_kernel(PairArgs A)
+fringe_pair_fwd1_kernel(PairArgs G)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    if (row_is_signed(A, fwd_block(A)) != SIGNED) return;        // uniform over the block
+    const PairBlock A = pair_block_args(G);
+    if (row_is_signed(A, fwd_block_at(A, blockIdx.x - A.block0)) != SIGNED) return;        // uniform over the block
     for_wave<4>([&](auto w) { pair_fwd1_body<w(), SIGNED, FLAT>(A, smem); });
 }
 
@@ -1787,10 +1816,32 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
 // The hub (CEN, see the forward) adds sum_j u_j c_j + v_j s_j with two real vectors: they are the INITIAL values of the
 // accumulators.  G is scaled by gscale / 8: an entry sums up to eight gradients.
 // ---------------------------------------------------------------------------------------
-struct PairBwdArgs : AntBwdArgs {
-    const int* centre;         // CEN: [2][128] slots of the hub's baselines (as PairArgs::centre)
+struct PairBwdBlock : AntBwdArgs {
+    const int* centre;         // CEN: [2][128] slots of the hub's baselines (as PairBlock::centre)
     int ap;                    // 0: no octet is searched for progressions (RIME_PAIR_AP=0)
+    unsigned block0;           // first block of this block's segment in the grid
 };
+// SEGMENTS, as in the forward (PairArgs): the gradient planes of up to MF_MAXSEG sky components from ONE transposed gvis and
+// one gscale table; a segment has its own pixels (sdir, Pstride), output plane and pixel split.
+struct PairBwdSeg {
+    const double* sdir; float* gpsky;
+    long long st_t, st_f, st_p;
+    int Pstride, S, tiles_per_split, accumulate;
+    unsigned block0;
+};
+struct PairBwdArgs {
+    PairBwdBlock base;
+    int nseg;
+    PairBwdSeg seg[MF_MAXSEG];
+};
+__device__ __forceinline__ PairBwdBlock pair_bwd_block_args(const PairBwdArgs& G)
+{
+    PairBwdBlock A = G.base;
+    const PairBwdSeg& s = G.seg[segment_of(G.seg, G.nseg)];
+    A.sdir = s.sdir; A.gpsky = s.gpsky; A.st_t = s.st_t; A.st_f = s.st_f; A.st_p = s.st_p;
+    A.Pstride = s.Pstride; A.S = s.S; A.tiles_per_split = s.tiles_per_split; A.accumulate = s.accumulate; A.block0 = s.block0;
+    return A;
+}
 
 // PROGRESSIONS (round 6).  Antennas of a regular array sit on lattice lines: where rows q .. q + 3 of the block are r, r + d,
 // r + 2d, r + 3d, their phasors are E1 conj(D), E1, E1 D, E1 D D with D = exp(2 pi i nu d.s) -- one evaluation and three complex
@@ -1820,8 +1871,9 @@ template <int TF> constexpr size_t pb_lds() { return 8 * (size_t)pb_plane<TF>() 
 
 template <bool CEN, bool FLAT, int TF>
 __global__ void __launch_bounds__(PB_THREADS, 3)
-fringe_pair_bwd_kernel(PairBwdArgs A)
+fringe_pair_bwd_kernel(PairBwdArgs G)
 {
+    const PairBwdBlock A = pair_bwd_block_args(G);
     constexpr int PB_PLANE = pb_plane<TF>();
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned char* g_img = smem;              // planes: 0 N1, 1 N3, 2 N2, 3 N4 (hi), 4..7 the same (lo)
@@ -1830,7 +1882,8 @@ fringe_pair_bwd_kernel(PairBwdArgs A)
     float* cen_v = cen_u + 64;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int f = blockIdx.x % A.Nf, ts = blockIdx.x / A.Nf;
+    const unsigned bid = blockIdx.x - A.block0;                   // within the segment
+    const int f = bid % A.Nf, ts = bid / A.Nf;
     const int t = ts / A.S, split = ts % A.S;
     const int TA = (A.Nant + 31) / 32;
 
@@ -2436,36 +2489,162 @@ static bool pair_common_ok(int Nrows, int Nbl, int Nt, int Nf, int Pstride, long
     return Nrows > 0 && Nrows <= 64 && ant_common_ok(Nrows, 0, Nbl, Nt, Nf, Pstride, st_p, sign, 0);     // st_p 1, or 2: one plane of a complex buffer
 }
 
+
+// The pair launch layer: every entry below fills ONE segment table and launches once per direction.  The single-plane entry
+// points are the nseg = 1 case of the segment entry points.
+static bool wide_plan()
+{
+    static const bool wide = env_flag("RIME_PAIR_BWD_WIDE", 1);
+    return wide;
+}
+
+static bool segments_ok(const rime_fringe_segment* segs, int nseg, int Nrows, int Nbl, int Nt, int Nf, int sign, bool backward,
+                        int* Pstride)
+{
+    if (!segs || nseg < 1 || nseg > MF_MAXSEG) return false;
+    for (int k = 0; k < nseg; ++k) {
+        const rime_fringe_segment& s = segs[k];
+        if (!s.sdir || (backward ? !s.gpsky : (!s.psky || !s.scale))) return false;
+        if (!pair_common_ok(Nrows, Nbl, Nt, Nf, s.Pstride, s.st_p, sign)) return false;
+        Pstride[k] = s.Pstride;
+    }
+    return true;
+}
+
+extern "C" size_t rime_fringe_pair_segments_workspace(int Nbl, int Nt, int Nf, const int* Pstride, int nseg)
+{
+    SegPlan p;
+    if (!Pstride || Nbl <= 0 || !seg_plan(false, false, Nt, Nf, Pstride, nseg, p)) return 0;
+    return (size_t)p.slabs * Nbl * Nt * Nf * 2 * sizeof(float);
+}
+
+extern "C" int rime_fringe_pair_segments_map(int backward, int Nt, int Nf, const int* Pstride, int nseg, int* out, long capacity)
+{
+    SegPlan p;
+    if (!Pstride || !seg_plan(backward != 0, wide_plan(), Nt, Nf, Pstride, nseg, p)) return RIME_EINVAL;
+    if (!out) return (int)p.grid;
+    if (capacity < p.grid) return RIME_EWORKSPACE;
+    for (long b = 0; b < p.grid; ++b) {
+        const SegBlock r = seg_block(p, Nf, Pstride, backward != 0, b);
+        int* o = out + 6 * b;
+        o[0] = r.seg; o[1] = r.f; o[2] = r.t; o[3] = r.split; o[4] = r.begin; o[5] = r.end;
+    }
+    return (int)p.grid;
+}
+
+extern "C" int rime_fringe_pair_fwd_segments(const double* antpos, int Nrows, const int* centre, int flat, const double* freqs,
+                                             const int* pair_direct, const int* pair_conj, int Nbl, int Nt, int Nf, int sign,
+                                             const rime_fringe_segment* segs, int nseg, void* workspace, size_t workspace_bytes,
+                                             void* stream)
+{
+    int Ps[MF_MAXSEG];
+    if (!antpos || !freqs || !pair_direct || !pair_conj) return RIME_EINVAL;
+    if (!segments_ok(segs, nseg, Nrows, Nbl, Nt, Nf, sign, false, Ps)) return RIME_EINVAL;
+    SegPlan p;
+    if (!seg_plan(false, false, Nt, Nf, Ps, nseg, p)) return RIME_EINVAL;
+    const size_t slab = (size_t)Nbl * Nt * Nf * 2;
+    if (!workspace || workspace_bytes < (size_t)p.slabs * slab * sizeof(float)) return RIME_EWORKSPACE;
+    PairArgs G{};
+    PairBlock& A = G.base;
+    fill_geometry(A, antpos, segs[0].sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Ps[0], 0, 0, 1, sign);
+    A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
+    G.nseg = nseg;
+    bool twin = false;
+    for (int g = 0; g < nseg; ++g) {
+        const int k = p.order[g];
+        const rime_fringe_segment& s = segs[k];
+        PairSeg& d = G.seg[g];
+        d.psky = s.psky; d.sdir = s.sdir; d.scale = s.scale; d.rowmin = s.rowmin; d.ws = (float*)workspace + (size_t)p.slab0[k] * slab;
+        d.st_t = s.st_t; d.st_f = s.st_f; d.st_p = s.st_p;
+        d.Pstride = s.Pstride; d.S = p.S[k]; d.panels_per_split = p.per[k]; d.block0 = (unsigned)p.block0[g];
+        twin = twin || s.rowmin;
+    }
+    const dim3 grid((unsigned)p.grid, 1, 1), threads(256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // one real plane per segment: the SIGNED = true instantiation serves the rows that hold a negative value (and every row of a
+    // segment without row minima), the other one the rest; each returns at once from the other's blocks (launch_real_plane)
+    with_bool(flat != 0, [&](auto FLAT) {
+        if (Nrows <= 32 && !centre) {                    // one row tile
+            // LDS: two image buffers (18.5 KB) during the loop, then the epilogue's transposition tiles + two partial tiles per wave pair
+            constexpr size_t lds1 = 4 * 33 * 32 * 4 + 2 * 2 * 16 * 64 * 4;
+            static_assert(lds1 >= 2 * (size_t)FwdShape<1, 1, false>::BUF, "the image buffers fit into the epilogue's scratch");
+            hipLaunchKernelGGL((fringe_pair_fwd1_kernel<true, FLAT()>), grid, threads, lds1, st, G);
+            if (twin) hipLaunchKernelGGL((fringe_pair_fwd1_kernel<false, FLAT()>), grid, threads, lds1, st, G);
+            return;
+        }
+        using SH = FwdShape<2, 2, false>;
+        static_assert(SH::LDS >= 4 * 33 * 32 * 4 + 2 * 64 * 2 * 4, "epilogue scratch: transposition tiles + the hub's column sums");
+        with_bool(centre != nullptr, [&](auto CEN) {
+            hipLaunchKernelGGL((fringe_pair_fwd_kernel<true, CEN(), FLAT()>), grid, threads, SH::LDS, st, G);
+            if (twin) hipLaunchKernelGGL((fringe_pair_fwd_kernel<false, CEN(), FLAT()>), grid, threads, SH::LDS, st, G);
+        });
+    });
+    return check_launch();
+}
+
+// sums the slabs of all segments in the caller's order of segments, then split order, and transposes into vis
+extern "C" int rime_fringe_pair_segments_finish(const void* workspace, size_t workspace_bytes, float* vis, int Nbl, int Nt, int Nf,
+                                                const int* Pstride, int nseg, void* stream)
+{
+    SegPlan p;
+    if (!vis || Nbl <= 0 || !Pstride || Nt > 65535 || !seg_plan(false, false, Nt, Nf, Pstride, nseg, p)) return RIME_EINVAL;
+    if (!workspace || workspace_bytes < (size_t)p.slabs * Nbl * Nt * Nf * 2 * sizeof(float)) return RIME_EWORKSPACE;
+    hipLaunchKernelGGL(reduce_vis_kernel, dim3((Nbl + 31) / 32, (Nf + 31) / 32, Nt), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), (const float*)workspace, vis, Nbl, Nt, Nf, (int)p.slabs);
+    return check_launch();
+}
+
+extern "C" int rime_fringe_pair_bwd_segments(const double* antpos, int Nrows, const int* centre, int flat, const double* freqs,
+                                             const float* gscale, const int* pair_direct, const int* pair_conj, int Nbl, int Nt,
+                                             int Nf, int sign, const rime_fringe_segment* segs, int nseg, const void* workspace,
+                                             size_t workspace_bytes, void* stream)
+{
+    int Ps[MF_MAXSEG];
+    if (!antpos || !freqs || !gscale || !pair_direct || !pair_conj) return RIME_EINVAL;
+    if (!segments_ok(segs, nseg, Nrows, Nbl, Nt, Nf, sign, true, Ps)) return RIME_EINVAL;
+    if (!workspace || workspace_bytes < rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)) return RIME_EWORKSPACE;
+    SegPlan p;
+    if (!seg_plan(true, wide_plan(), Nt, Nf, Ps, nseg, p)) return RIME_EINVAL;
+    PairBwdArgs G{};
+    PairBwdBlock& A = G.base;
+    fill_geometry(A, antpos, segs[0].sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Ps[0], 0, 0, 1, sign);
+    A.gscale = gscale; A.gvt = (const float*)workspace;
+    A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
+    // RIME_PAIR_AP=0: the pair backward evaluates every phasor (no rotation within progressions; A/B measurements; ops.py reads the
+    // same variable and keeps the plain row order)
+    static const bool ap = env_flag("RIME_PAIR_AP", 1);
+    A.ap = ap ? 1 : 0;
+    G.nseg = nseg;
+    for (int g = 0; g < nseg; ++g) {
+        const int k = p.order[g];
+        const rime_fringe_segment& s = segs[k];
+        PairBwdSeg& d = G.seg[g];
+        d.sdir = s.sdir; d.gpsky = s.gpsky; d.st_t = s.st_t; d.st_f = s.st_f; d.st_p = s.st_p;
+        d.Pstride = s.Pstride; d.S = p.S[k]; d.tiles_per_split = p.per[k]; d.accumulate = s.accumulate ? 1 : 0;
+        d.block0 = (unsigned)p.block0[g];
+    }
+    const dim3 grid((unsigned)p.grid, 1, 1);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    with_bool(flat != 0, [&](auto FLAT) {
+        if (Nrows <= 32 && !centre)                      // one row tile
+            hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, FLAT(), 1>), grid, dim3(PB_THREADS), pb_lds<1>(), st, G);
+        else with_bool(centre != nullptr, [&](auto CEN) {
+            hipLaunchKernelGGL((fringe_pair_bwd_kernel<CEN(), FLAT(), 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, G);
+        });
+    });
+    return check_launch();
+}
+
 extern "C" int rime_fringe_pair_fwd_block(const double* antpos, int Nrows, const int* centre, int flat, const double* sdir,
                                           const double* freqs, const float* psky, const float* scale, const float* rowmin,
                                           const int* pair_direct, const int* pair_conj, int Nbl, int Nt, int Nf, int Pstride,
                                           long long st_t, long long st_f, long long st_p, int sign,
                                           void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!antpos || !sdir || !freqs || !psky || !scale || !pair_direct || !pair_conj) return RIME_EINVAL;
-    if (!pair_common_ok(Nrows, Nbl, Nt, Nf, Pstride, st_p, sign)) return RIME_EINVAL;
-    if (!workspace || workspace_bytes < fwd_workspace_bytes(Nbl, Nt, Nf, Pstride)) return RIME_EWORKSPACE;
-    PairArgs A{};
-    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
-    const dim3 grid = fill_forward(A, psky, scale, rowmin, workspace);
-    A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    with_bool(flat != 0, [&](auto FLAT) {
-        if (Nrows <= 32 && !centre) {                    // one row tile
-            // LDS: two image buffers (18.5 KB) during the loop, then the epilogue's transposition tiles + two partial tiles per wave pair
-            constexpr size_t lds1 = 4 * 33 * 32 * 4 + 2 * 2 * 16 * 64 * 4;
-            static_assert(lds1 >= 2 * (size_t)FwdShape<1, 1, false>::BUF, "the image buffers fit into the epilogue's scratch");
-            launch_real_plane(fringe_pair_fwd1_kernel<true, FLAT()>, fringe_pair_fwd1_kernel<false, FLAT()>, grid, 256, lds1, st, A);
-            return;
-        }
-        using SH = FwdShape<2, 2, false>;
-        static_assert(SH::LDS >= 4 * 33 * 32 * 4 + 2 * 64 * 2 * 4, "epilogue scratch: transposition tiles + the hub's column sums");
-        with_bool(centre != nullptr, [&](auto CEN) {
-            launch_real_plane(fringe_pair_fwd_kernel<true, CEN(), FLAT()>, fringe_pair_fwd_kernel<false, CEN(), FLAT()>, grid, 256,
-                              SH::LDS, st, A);
-        });
-    });
-    return check_launch();
+    rime_fringe_segment s{};
+    s.sdir = sdir; s.psky = psky; s.scale = scale; s.rowmin = rowmin; s.st_t = st_t; s.st_f = st_f; s.st_p = st_p; s.Pstride = Pstride;
+    return rime_fringe_pair_fwd_segments(antpos, Nrows, centre, flat, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, sign, &s, 1,
+                                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const int* centre, int flat, const double* sdir,
@@ -2474,26 +2653,10 @@ extern "C" int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const
                                           long long st_t, long long st_f, long long st_p, int sign, int accumulate,
                                           float* gpsky, const void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!antpos || !sdir || !freqs || !gscale || !pair_direct || !pair_conj || !gpsky) return RIME_EINVAL;
-    if (!pair_common_ok(Nrows, Nbl, Nt, Nf, Pstride, st_p, sign)) return RIME_EINVAL;
-    if (!workspace || workspace_bytes < rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf)) return RIME_EWORKSPACE;
-    PairBwdArgs A{};
-    fill_geometry(A, antpos, sdir, freqs, pair_direct, pair_conj, Nbl, Nt, Nf, Pstride, st_t, st_f, st_p, sign);
-    const dim3 grid = fill_backward(A, gscale, gpsky, workspace, accumulate, pair_bwd_launch_plan);
-    A.Nant = Nrows; A.imsign = 1.f; A.centre = centre;
-    // RIME_PAIR_AP=0: the pair backward evaluates every phasor (no rotation within progressions; A/B measurements; ops.py reads the
-    // same variable and keeps the plain row order)
-    static const bool ap = env_flag("RIME_PAIR_AP", 1);
-    A.ap = ap ? 1 : 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    with_bool(flat != 0, [&](auto FLAT) {
-        if (Nrows <= 32 && !centre)                      // one row tile
-            hipLaunchKernelGGL((fringe_pair_bwd_kernel<false, FLAT(), 1>), grid, dim3(PB_THREADS), pb_lds<1>(), st, A);
-        else with_bool(centre != nullptr, [&](auto CEN) {
-            hipLaunchKernelGGL((fringe_pair_bwd_kernel<CEN(), FLAT(), 2>), grid, dim3(PB_THREADS), pb_lds<2>(), st, A);
-        });
-    });
-    return check_launch();
+    rime_fringe_segment s{};
+    s.sdir = sdir; s.gpsky = gpsky; s.st_t = st_t; s.st_f = st_f; s.st_p = st_p; s.Pstride = Pstride; s.accumulate = accumulate;
+    return rime_fringe_pair_bwd_segments(antpos, Nrows, centre, flat, freqs, gscale, pair_direct, pair_conj, Nbl, Nt, Nf, sign, &s, 1,
+                                         workspace, workspace_bytes, stream);
 }
 
 // Pixel splits of a rime_fringe_pair_bwd_block launch (grid = Nt x splits x Nf); 0 for shapes the entry refuses

@@ -3,8 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 #include "rime_common.h"
 
 namespace rime {
@@ -95,17 +97,34 @@ constexpr int MF_ROWB = 4 * MF_KP + 16;         // image row: [re KP x f16][im K
 // 1. Block coordinates.  1-D grid, channel fastest: blocks that run together share (t, split), i.e. the same pointing vectors
 // (L2 hits), and no grid dimension hits the 65535 cap.  Panels [pbeg, pend) are this block's pixel split.
 struct FwdBlock { int f, t, split, pbeg, pend; };
+// `bid`: the block's index within its launch, or within its segment of a merged launch (blockIdx.x - A.block0)
 template <class Args>
-__device__ __forceinline__ FwdBlock fwd_block(const Args& A)
+__device__ __forceinline__ FwdBlock fwd_block_at(const Args& A, unsigned bid)
 {
     FwdBlock b;
-    b.f = __builtin_amdgcn_readfirstlane(blockIdx.x % A.Nf);
-    const int ts = blockIdx.x / A.Nf;
+    b.f = __builtin_amdgcn_readfirstlane(bid % A.Nf);
+    const int ts = bid / A.Nf;
     b.t = __builtin_amdgcn_readfirstlane(ts / A.S);
     b.split = __builtin_amdgcn_readfirstlane(ts % A.S);
     b.pbeg = __builtin_amdgcn_readfirstlane(b.split * A.panels_per_split);
     b.pend = __builtin_amdgcn_readfirstlane(min(A.Pstride / MF_KP, b.pbeg + A.panels_per_split));
     return b;
+}
+template <class Args>
+__device__ __forceinline__ FwdBlock fwd_block(const Args& A) { return fwd_block_at(A, blockIdx.x); }
+
+// 1b. Segments (the conjugate-pair kernels): one launch serves up to MF_MAXSEG psky planes that share times, channels, rows and
+// slot tables but have their own pixels -- the sky components of one RIME call.  The grid is the concatenation of the
+// segments' grids (SegPlan below); a block finds its segment from blockIdx.x with scalar compares against the segments' first
+// blocks and from then on reads that segment's bases: everything here is wave-uniform (SGPRs), no lane branches on it.
+constexpr int MF_MAXSEG = 4;
+template <class Seg>
+__device__ __forceinline__ int segment_of(const Seg* seg, int nseg)
+{
+    int k = 0;
+#pragma unroll
+    for (int i = 1; i < MF_MAXSEG; ++i) k += (i < nseg && blockIdx.x >= seg[i].block0) ? 1 : 0;
+    return __builtin_amdgcn_readfirstlane(k);
 }
 // A block works on one psky row (t, f): rows without a negative value (beam-weighted emission is non-negative) take the kernel
 // instantiation without sign masks.  Both instantiations are launched over the full grid and a block returns at once when its
@@ -366,6 +385,68 @@ inline PixelSplit pair_bwd_launch_plan(int Nt, int Nf, int Pstride)
 {
     static const bool wide = env_flag("RIME_PAIR_BWD_WIDE", 1);
     return wide ? pair_bwd_split_plan(Nt, Nf, Pstride) : bwd_split_plan(Nt, Nf, Pstride);
+}
+
+// ---- host: the segment plan of a merged pair launch -----------------------------------------------------
+// Segment k (caller's order) has Pstride[k] pixels per (t, f) row.  Forward: every segment keeps fwd_split_plan; its slabs
+// follow those of the segments before it in the CALLER's order (slab0), which is the order reduce_vis_kernel sums in.
+// Backward: every segment starts from bwd_split_plan and widens by the rule of pair_bwd_split_plan with the grid condition
+// taken on the COMBINED grid (the other segments' blocks level the tail as well as its own).  In the grid the segments stand
+// by falling work per block row (pixels), ties in caller order: the short blocks of the small segments fill the tail
+// (order[], block0[] in grid order).  One segment: exactly the plan of the single launch.
+struct SegPlan {
+    int nseg;
+    int S[MF_MAXSEG], per[MF_MAXSEG];           // by segment: splits, panels (forward) / tiles (backward) per split
+    long slab0[MF_MAXSEG];                      // by segment: first slab (forward)
+    int order[MF_MAXSEG];                       // grid position -> segment
+    long block0[MF_MAXSEG];                     // grid position -> first block
+    long grid, slabs;
+};
+struct SegBlock { int seg, f, t, split, begin, end; };      // [begin, end): panels (forward) or pixel tiles (backward)
+
+inline bool seg_plan(bool backward, bool wide, int Nt, int Nf, const int* Pstride, int nseg, SegPlan& p)
+{
+    if (nseg < 1 || nseg > MF_MAXSEG || Nt <= 0 || Nf <= 0) return false;
+    p = SegPlan{};
+    p.nseg = nseg;
+    const long rows = (long)Nt * Nf;
+    for (int k = 0; k < nseg; ++k) {
+        if (Pstride[k] <= 0 || Pstride[k] % 64 != 0) return false;
+        const PixelSplit s = backward ? bwd_split_plan(Nt, Nf, Pstride[k]) : fwd_split_plan(Nt, Nf, Pstride[k]);
+        p.S[k] = s.S; p.per[k] = s.per;
+        p.order[k] = k;
+    }
+    for (int a = 1; a < nseg; ++a)              // stable insertion sort, most pixels first
+        for (int b = a; b > 0 && Pstride[p.order[b]] > Pstride[p.order[b - 1]]; --b) std::swap(p.order[b], p.order[b - 1]);
+    if (backward && wide) {
+        long total = 0;
+        for (int k = 0; k < nseg; ++k) total += rows * p.S[k];
+        for (int g = 0; g < nseg; ++g) {
+            const int k = p.order[g], ntile = Pstride[k] / 32;
+            int per = p.per[k];
+            long others = total - rows * p.S[k];
+            while (per >= 256 && per < 1024 && others + rows * ((ntile + 2 * per - 1) / (2 * per)) >= PAIR_BWD_MIN_GRID) per *= 2;
+            p.per[k] = per; p.S[k] = (ntile + per - 1) / per;
+            total = others + rows * p.S[k];
+        }
+    }
+    for (int k = 0; k < nseg; ++k) { p.slab0[k] = p.slabs; p.slabs += p.S[k]; }
+    for (int g = 0; g < nseg; ++g) { p.block0[g] = p.grid; p.grid += rows * p.S[p.order[g]]; }
+    return p.grid <= 0x7fffffffL;
+}
+
+// the block -> (segment, f, t, split, range) map of the kernels (segment_of, fwd_block_at), on the host
+inline SegBlock seg_block(const SegPlan& p, int Nf, const int* Pstride, bool backward, long b)
+{
+    int g = 0;
+    for (int i = 1; i < p.nseg; ++i) g += b >= p.block0[i] ? 1 : 0;
+    const int k = p.order[g];
+    const long bid = b - p.block0[g], ts = bid / Nf;
+    SegBlock r;
+    r.seg = k; r.f = (int)(bid % Nf); r.t = (int)(ts / p.S[k]); r.split = (int)(ts % p.S[k]);
+    r.begin = r.split * p.per[k];
+    r.end = std::min(Pstride[k] / 32, r.begin + p.per[k]);
+    return r;
 }
 
 // The fields every argument struct of these kernels has, under the same names

@@ -1245,6 +1245,163 @@ def fringe_sum(psky, geom, blvecs=None):
     return _FringeSum.apply(psky, geom)
 
 
+# RIME_FRINGE_MERGE=0: the sky components of a RIME call keep one fringe launch sequence each (A/B measurements)
+FRINGE_MERGE = _env_int('RIME_FRINGE_MERGE', 1) != 0
+MAX_SEGMENTS = 4
+
+
+def _merged_block(pskys, geoms):
+    """
+    The pair block that all components of a fringe_sum_components call run on, or None where they keep their own launches:
+    two to four real float32 planes on ONE conjugate-pair block (the same tables: geometries built with ant_like), the same
+    baselines, times, channels and fringe sign, one beam-model pair.  Anything else -- generic, packed or cross blocks, a
+    complex psky, other dtypes -- is not merged.
+    """
+    if not FRINGE_MERGE or not 2 <= len(geoms) <= MAX_SEGMENTS:
+        return None
+    g0, blk = geoms[0], None
+    for p, g in zip(pskys, geoms):
+        if g.ant is None or p.dtype != torch.float32 or p.dim() != 5 or g.Nmp != 1 or p.shape[2] != pskys[0].shape[2]:
+            return None
+        blocks = g.ant.get('blocks_real', g.ant['blocks'])
+        if len(blocks) != 1 or not blocks[0].get('pair') or blocks[0].get('xpair') or (blk is not None and blocks[0] is not blk):
+            return None
+        blk = blocks[0]
+        if (g.Nbl, g.Nt, g.Nf, g.sign) != (g0.Nbl, g0.Nt, g0.Nf, g0.sign):
+            return None
+        if tuple(p.shape) != (g.Nt, 1, p.shape[2], g.Nf, g.Pstride):
+            return None
+        if g is not g0:
+            same = g.__dict__.get('_same_freqs')               # compared once per pair of geometries (a device sync)
+            if same is None or same[0] is not g0.freqs:
+                same = g.__dict__['_same_freqs'] = (g0.freqs, bool(torch.equal(g.freqs, g0.freqs)))
+            if not same[1]:
+                return None
+    return blk
+
+
+def _segment_table(geoms, planes, pp, backward, scales=None, accumulate=0):
+    """rime_fringe_segment array of the planes `pp` of (Nt, 1, Npp, Nf, Ps) float32 tensors with a contiguous pixel axis"""
+    segs = (_lib.FringeSegment * len(geoms))()
+    for s, g, p in zip(segs, geoms, planes):
+        st = p.stride()
+        s.sdir, s.Pstride, s.st_t, s.st_f, s.st_p = g.sdir.data_ptr(), g.Pstride, max(st[0], 1), max(st[3], 1), 1
+        plane = p.data_ptr() + 4 * pp * st[2]
+        if backward:
+            s.gpsky, s.accumulate = plane, accumulate
+        else:
+            s.psky = plane
+    if scales is not None:
+        for s, (scale, rowmin) in zip(segs, scales):
+            s.scale, s.rowmin = scale[0, pp].data_ptr(), rowmin[0, pp].data_ptr()
+    return segs
+
+
+def _merged_call(blk, geoms, backward, planes, vis_real):
+    """
+    One pair launch per direction over the segment table of the components (csrc/fringe_mfma.hip, SEGMENTS).  Forward:
+    planes = the psky of every component, vis_real (Npp, Nbl, Nt, Nf, 2) is written.  Backward: planes = the gradient buffers
+    of the components that need one (geoms alike), vis_real the gradient of the visibilities: ONE transpose and ONE row scale
+    of it serve all of them.  Recorded in PROFILE under the family names of the per-component calls (below).
+    """
+    g0 = geoms[0]
+    Nbl, Nt, Nf, Npp, dev = g0.Nbl, g0.Nt, g0.Nf, planes[0].shape[2], planes[0].device
+    name, lead, tables, _, mf = _block_launch(blk, backward, 0)
+    name = name.replace('_block', '_segments')
+    Ps = (ctypes.c_int * len(geoms))(*[g.Pstride for g in geoms])
+    family = 'fringe_ant_bwd_kernel' if backward else 'fringe_ant_fwd_kernel'
+    vbytes = vis_real.numel() * vis_real.element_size()
+    work = [(g.elements, mf * Npp * Nt * Nf * (g.Pstride // 16) * 32768,
+             int(p.numel() * p.element_size() + vbytes + g.sdir.numel() * g.sdir.element_size())) for p, g in zip(planes, geoms)]
+    prof = PROFILE
+    with _timed(family, work[0][0]) as late:
+        if not backward:
+            scales = []
+            for p in planes:
+                scale = torch.empty((1, Npp, Nt, Nf), dtype=torch.float32, device=dev)
+                rowmin = torch.empty_like(scale)
+                check(lib.rime_fringe_row_scale(_ptr(p), 1, Npp, Nt, Nf, p.stride(1), p.stride(2), p.stride(0), p.stride(3),
+                                                p.shape[-1], _ptr(scale), _ptr(rowmin), _stream()), 'rime_fringe_row_scale')
+                scales.append((scale, rowmin))
+            ws, nbytes = _workspace(lib.rime_fringe_pair_segments_workspace(Nbl, Nt, Nf, Ps, len(geoms)), dev, 16)
+            for pp in range(Npp):
+                segs = _segment_table(geoms, planes, pp, False, scales)
+                check(getattr(lib, name)(*lead, _ptr(g0.freqs), *tables, Nbl, Nt, Nf, g0.sign, segs, len(geoms), _ptr(ws), nbytes,
+                                         _stream()), name)
+                check(lib.rime_fringe_pair_segments_finish(_ptr(ws), nbytes, _ptr(vis_real[pp]), Nbl, Nt, Nf, Ps, len(geoms),
+                                                           _stream()), 'rime_fringe_pair_segments_finish')
+        else:
+            ws, nbytes = _workspace(lib.rime_fringe_ant_bwd_workspace(Nbl, Nt, Nf), dev, 16)
+            gvt = ws[:Nt * Nf * 2 * Nbl * 4].view(torch.float32).view(Nt * Nf, 2 * Nbl)
+            for pp in range(Npp):
+                check(lib.rime_fringe_ant_bwd_prepare(_ptr(vis_real[pp]), Nbl, Nt, Nf, _ptr(ws), nbytes, _stream()),
+                      'rime_fringe_ant_bwd_prepare')
+                gscale = torch.empty(Nt * Nf, dtype=torch.float32, device=dev)
+                check(lib.rime_fringe_row_scale(_ptr(gvt), 1, 1, 1, Nt * Nf, 0, 0, 0, 2 * Nbl, 2 * Nbl, _ptr(gscale), None,
+                                                _stream()), 'rime_fringe_row_scale')
+                segs = _segment_table(geoms, planes, pp, True)
+                check(getattr(lib, name)(*lead, _ptr(g0.freqs), _ptr(gscale), *tables, Nbl, Nt, Nf, g0.sign, segs, len(geoms),
+                                         _ptr(ws), nbytes, _stream()), name)
+        if late is not None:
+            late += work[0][1:]
+    if prof is not None:
+        # one record per segment under the family name, as the per-component calls leave them: the first holds the time of
+        # the whole launch, the others their elements / flops / bytes with an empty interval, so sums over the family hold
+        for w in work[1:]:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            prof.append((family, e, e) + w)
+
+
+class _FringeSumMerged(torch.autograd.Function):
+    """sum over sky components of fringe_sum(psky_k, geom_k), one node: N psky inputs, N gradients"""
+    @staticmethod
+    def forward(ctx, blk, geoms, *pskys):
+        _require_cuda(*pskys)
+        planes = []
+        for p in pskys:
+            p = p.detach()
+            planes.append(p if _dense_strides(p) is not None else p.contiguous())
+        g0 = geoms[0]
+        vis = torch.empty((planes[0].shape[2], g0.Nbl, g0.Nt, g0.Nf), dtype=torch.complex64, device=planes[0].device)
+        _merged_call(blk, geoms, False, planes, torch.view_as_real(vis))
+        ctx.blk, ctx.geoms = blk, geoms
+        ctx.templates = [(tuple(p.shape), tuple(p.stride())) for p in planes]
+        return vis
+
+    @staticmethod
+    def backward(ctx, gvis):
+        g = gvis.contiguous()
+        need = [k for k in range(len(ctx.geoms)) if ctx.needs_input_grad[2 + k]]
+        grads = [None] * len(ctx.geoms)
+        if need:
+            for k in need:
+                shape, stride = ctx.templates[k]
+                grads[k] = torch.empty_strided(shape, stride, dtype=torch.float32, device=g.device)
+            _merged_call(ctx.blk, [ctx.geoms[k] for k in need], True, [grads[k] for k in need], torch.view_as_real(g))
+        return (None, None) + tuple(grads)
+
+
+def fringe_sum_components(pskys, geoms, blvecs=None):
+    """
+    sum_k fringe_sum(pskys[k], geoms[k]): the visibilities of several sky components seen by one array at the same times and
+    channels (RIME.forward).  Where every component runs on the same conjugate-pair block this is ONE launch per direction
+    over a segment table, one reduction of the slabs and, in the backward, one transpose and row scale of the gradient;
+    otherwise (and with RIME_FRINGE_MERGE=0, or a blvecs that requires a gradient) the per-component calls, added up.
+    A component whose psky does not require a gradient takes no part in the backward launch.
+    """
+    pskys, geoms = list(pskys), list(geoms)
+    assert len(pskys) == len(geoms) and pskys
+    blk = None if (blvecs is not None and blvecs.requires_grad) else _merged_block(pskys, geoms)
+    if blk is not None:
+        return _FringeSumMerged.apply(blk, geoms, *pskys)
+    vis = None
+    for p, g in zip(pskys, geoms):
+        v = fringe_sum(p, g, blvecs)
+        vis = v if vis is None else vis + v
+    return vis
+
+
 def fringe_adjoint(gvis, geom, Npp=None, dtype=None):
     """
     The adjoint of fringe_sum for a REAL psky, without autograd:  out[t, 0, q, f, p] = Re sum_b

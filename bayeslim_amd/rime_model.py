@@ -292,6 +292,7 @@ class RIME(utils.Module):
         start = datetime.now().timestamp()
 
         vis = None
+        parts = []
         node_major = {}
         for i, comp in enumerate(comps):
             sky = comp.data
@@ -339,10 +340,21 @@ class RIME(utils.Module):
             n1, n2, Nmp, Nf = ps.shape[:4]
             # -> (Nt, Nmp, Npp, Nf, Ps) as a strided VIEW: the fringe kernels take the strides
             ps = ps.reshape(n1 * n2, Nmp, Nf, Nt, Ps).permute(3, 1, 0, 2, 4)
-            blv = self._current_blvecs()
-            v = ops.fringe_sum(ps, bg['geom'], blv.to(dev) if blv.requires_grad else None)   # (Npp, Nbl, Nt, Nf)
-            v = v.reshape(n1, n2, v.shape[1], Nt, Nf)
-            vis = v if vis is None else vis + v
+            parts.append((ps, bg['geom'], (n1, n2, Nt, Nf), dev))
+
+        # the fringe sum of all components: one launch per direction where they share a conjugate-pair block
+        # (ops.fringe_sum_components), else one call per component, added up
+        blv = self._current_blvecs()
+        if len({p[2] for p in parts}) == 1 and len({p[3] for p in parts}) == 1:
+            (n1, n2, Nt, Nf), dev = parts[0][2:]
+            v = ops.fringe_sum_components([p[0] for p in parts], [p[1] for p in parts],
+                                          blv.to(dev) if blv.requires_grad else None)          # (Npp, Nbl, Nt, Nf)
+            vis = v.reshape(n1, n2, v.shape[1], Nt, Nf)
+        else:
+            for ps, geom, (n1, n2, Nt, Nf), dev in parts:
+                v = ops.fringe_sum(ps, geom, blv.to(dev) if blv.requires_grad else None)
+                v = v.reshape(n1, n2, v.shape[1], Nt, Nf)
+                vis = v if vis is None else vis + v
 
         idx = self._sim2data[self.bl_group_id]
         if idx is not None:                                          # rime_model.py:436-437

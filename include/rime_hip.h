@@ -228,6 +228,40 @@ int rime_fringe_pair_bwd_block(const double* antpos, int Nrows, const int* centr
  * force.  Host only. */
 int rime_fringe_pair_bwd_splits(int Nt, int Nf, int Pstride);
 
+/* SEGMENTS: the pair blocks of up to 4 psky planes that share rows, slot tables, times and channels -- the sky components of
+ * one RIME call -- in ONE launch per direction.  A segment names what a plane has of its own; the fields of the other
+ * direction are ignored.  rime_fringe_pair_fwd_block / rime_fringe_pair_bwd_block are these entry points with one segment. */
+typedef struct rime_fringe_segment {
+    const double* sdir;          /* [Nt, 3, Pstride] */
+    const float* psky;           /* forward: the plane, strided [t][f][p] */
+    const float* scale;          /* forward: [Nt, Nf] power-of-two pre-scale of its rows */
+    const float* rowmin;         /* forward: [Nt, Nf] row minima, or NULL (every row signed) */
+    float* gpsky;                /* backward: the gradient plane, same strides */
+    long long st_t, st_f, st_p;  /* element strides; st_p 1 or 2 */
+    int Pstride;                 /* multiple of 64 */
+    int accumulate;              /* backward: add to gpsky */
+} rime_fringe_segment;
+/* Forward: the slabs of segment k follow those of segments 0 .. k - 1 in the workspace (_segments_workspace bytes; 0 for a
+ * refused shape) and _segments_finish sums all of them into vis in that order, splits of a segment in split order: the bits of
+ * per-plane launches, finished one by one and added, whenever every segment after the first has one split.  In the GRID the
+ * segment with the most pixels stands first.  Backward: `workspace` is what rime_fringe_ant_bwd_prepare wrote, gscale the
+ * scale of its rows; a segment's pixel split widens by the rule of rime_fringe_pair_bwd_splits with the block count of ALL
+ * segments (pixel tiles are independent outputs: the same bits for every split).
+ * _segments_map (host only): the grid size, and with out != NULL ([grid][6] ints, capacity in blocks) for every block its
+ * (segment, f, t, split, first, end) -- panels (forward) or pixel tiles (backward) of 32 pixels -- as the kernels resolve it. */
+size_t rime_fringe_pair_segments_workspace(int Nbl, int Nt, int Nf, const int* Pstride, int nseg);
+int rime_fringe_pair_segments_map(int backward, int Nt, int Nf, const int* Pstride, int nseg, int* out, long capacity);
+int rime_fringe_pair_fwd_segments(const double* antpos, int Nrows, const int* centre, int flat, const double* freqs,
+                                  const int* pair_direct, const int* pair_conj, int Nbl, int Nt, int Nf, int sign,
+                                  const rime_fringe_segment* segs, int nseg, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int rime_fringe_pair_segments_finish(const void* workspace, size_t workspace_bytes, float* vis, int Nbl, int Nt, int Nf,
+                                     const int* Pstride, int nseg, void* stream);
+int rime_fringe_pair_bwd_segments(const double* antpos, int Nrows, const int* centre, int flat, const double* freqs,
+                                  const float* gscale, const int* pair_direct, const int* pair_conj, int Nbl, int Nt,
+                                  int Nf, int sign, const rime_fringe_segment* segs, int nseg, const void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* Conjugate-pair CROSS block, real psky (csrc/fringe_xpair.hip): the block between two groups I and J of ONE point-symmetric
  * array with more than 128 antennas.  Both groups are closed under the mirror (a group is a set of rows together with their
  * mirror antennas) and are measured from the SAME centre c, so the four quadrants V[x, y], V[x', y'], V[x', y], V[x, y'] follow
