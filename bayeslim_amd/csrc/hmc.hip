@@ -15,35 +15,9 @@
 // (lane l takes partials l, l + 64, ..., then the same butterfly) and halves the sum.  No atomics; the order is a function of
 // (N, dtype) alone: bit-reproducible, and the same for the energy-only pass and the pass fused with the last kick.
 // Vector ALU only; the register arrays are indexed by unrolled loops only (no scratch).
-#include "lane_vec.h"
+#include "hmc_common.h"
 
 namespace rime {
-
-constexpr int HMC_THREADS = 256, HMC_BYTES = 64, HMC_GROUPS = 4, HMC_MAXBLOCKS = 1024;
-
-// the strided layout of lane_vec.h at this file's geometry
-template <typename T>
-__device__ __forceinline__ void hmc_load(const T* p, long long c0, long long N, bool vec, T (&x)[HMC_BYTES / sizeof(T)])
-{
-    lane_load<T, HMC_THREADS, HMC_GROUPS>(p, c0, N, vec, x);
-}
-
-template <typename T>
-__device__ __forceinline__ void hmc_store(T* p, long long c0, long long N, bool vec, const T (&x)[HMC_BYTES / sizeof(T)])
-{
-    lane_store<T, HMC_THREADS, HMC_GROUPS>(p, c0, N, vec, x);
-}
-
-// sum of squares: the lane's chain in T, then float64 across the wave (every lane ends with the wave's sum)
-template <typename T>
-__device__ __forceinline__ double hmc_sumsq(const T (&z)[HMC_BYTES / sizeof(T)])
-{
-    constexpr int E = HMC_BYTES / sizeof(T);
-    T c = (T)0;
-#pragma unroll
-    for (int i = 0; i < E; ++i) c = tfma<T>(z[i], z[i], c);
-    return wave_sum((double)c);
-}
 
 // q, p in place; g, eps, c read only; null pointers as in the header.  partial [gridDim.x] when want_energy
 template <typename T>
@@ -107,21 +81,16 @@ __global__ __launch_bounds__(HMC_THREADS) void hmc_step_kernel(T* q, T* p, const
 // energy[0] = 1/2 sum_b partial[b]; one wave
 __global__ __launch_bounds__(64) void hmc_energy_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ energy)
 {
-    const int lane = threadIdx.x;
-    double s = 0.0;
-    for (int b = lane; b < nb; b += 64) s += partial[b];
-    s = wave_sum(s);
-    if (lane == 0) energy[0] = 0.5 * s;
+    const double s = partial_sum(partial, nb);
+    if (threadIdx.x == 0) energy[0] = 0.5 * s;
 }
-
-static long long hmc_chunks(long long N, int dtype) { return lane_chunks(N, dtype, HMC_THREADS, HMC_BYTES); }
 
 template <typename T>
 static int hmc_step(long long N, void* q, void* p, const void* g, const void* eps, const void* c, double kick, double drift,
                    double* energy, double* part, hipStream_t st, int dtype)
 {
     const long long nchunks = hmc_chunks(N, dtype);
-    const int nb = (int)std::min<long long>(nchunks, HMC_MAXBLOCKS);
+    const int nb = hmc_blocks(N, dtype);
     if (nb > 0)
         hipLaunchKernelGGL((hmc_step_kernel<T>), dim3((unsigned)nb), dim3(HMC_THREADS), 0, st, (T*)q, (T*)p, (const T*)g, (const T*)eps,
                            (const T*)c, (T)kick, (T)drift, energy != nullptr ? 1 : 0, N, nchunks, part);

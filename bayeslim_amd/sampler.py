@@ -20,6 +20,8 @@ Not provided (each raises NotImplementedError naming what is missing):
   * NUTS with TreeInfo (the natural follow-up: it reuses rime_hmc_step with Nstep = 1)
   * StepSize and DynamicStepSize (complex step sizes)
   * HMC.estimate_cov
+The No-U-Turn sampler is bayeslim_amd.nuts (NUTS and TreeInfo on the tree-leaf kernels of csrc/nuts.hip); the two names here
+stay stubs.
 """
 import math
 import os

@@ -675,6 +675,36 @@ int rime_hmc_step(int dtype, long long N, void* q, void* p, const void* g, const
                   double drift, double* energy, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One leaf of the No-U-Turn sampler's tree (nuts.NUTS.build_tree; reference sampler.py:1104-1140 with the criterion of
+ * sampler.py:1402-1430): a leapfrog step of the signed size h from an edge state of the tree, which stays as it is, in two
+ * launches around the evaluation of the potential's gradient at the new position.
+ *   all vectors T [N], flat and real as in rime_hmc_step (complex parameters as their interleaved real views);  eps, c as there,
+ *   each NULL for ones;  h the signed step: direction x step size for a scalar step size, +-1 with eps a vector
+ * rime_nuts_leaf_open, out of place (q0, p0, g0 the edge state and its gradient, read only; q1, p1 written), per element, in T:
+ *     p1 = fma(-(T(h/2) * eps), g0, p0);      q1 = fma(T(h) * eps, c * (c * p1), q0)
+ *   the bits of a copy of q0, p0 followed by rime_hmc_step(kick = h/2, drift = h).
+ * rime_nuts_leaf_close, in place on p1 (g1 the gradient at q1), per element, in T:
+ *     p1 <- fma(-(T(h/2) * eps), g1, p1)
+ *   and, with the updated p1, three doubles on the device:
+ *     out[0] = 1/2 sum (c * p1)^2;    out[1] = sum (q1 - q_far) * p_far;    out[2] = sum (q1 - q_far) * p1
+ *   (q_far, p_far: the state at the far edge of the tree the leaf is tested against; the no-U-turn criterion of Hoffman & Gelman
+ *   is the sign of these two sums, negated for h < 0).  q_far = p_far = NULL skips the two projections: out[1], out[2] are not
+ *   written.  The difference q1 - q_far is rounded once in T; each sum runs as the per-lane chains (64 bytes of a vector) of fused
+ *   multiply-adds in T, then float64 across lanes, waves and work-groups in the order of rime_hmc_step's energy: work-groups
+ *   write partial sums to the workspace (rime_nuts_workspace(N) bytes, either dtype) and a second kernel of the same call adds
+ *   them.  No atomics, bit-reproducible, and out[0] carries the bits of rime_hmc_step's energy for the same p1, g1, eps, c.
+ * Checked before any HIP call: RIME_EINVAL for an unknown dtype, N < 0, a null q0, p0, g0, q1, p1, g1 or out, only one of q_far
+ * and p_far, q1 or p1 of open overlapping one of its inputs or each other, a NaN h, h = 0 or an h whose half rounds to zero in T;
+ * RIME_EWORKSPACE for a null or short workspace (looked at before the rounding of h, as in rime_hmc_step).
+ * ------------------------------------------------------------------------------------- */
+size_t rime_nuts_workspace(long long N);
+int rime_nuts_leaf_open(int dtype, long long N, const void* q0, const void* p0, const void* g0, void* q1, void* p1,
+                        const void* eps, const void* c, double h, void* stream);
+int rime_nuts_leaf_close(int dtype, long long N, const void* q1, void* p1, const void* g1, const void* eps, const void* c,
+                         double h, const void* q_far, const void* p_far, double* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Grouped block mat-vec of a flattened operator tree (hmat.BaseMat.mat_vec_mul / mat_mat_mul; reference hmat.py): y (+)=
  * scalar * A x, A given as a DEVICE table of ntiles tiles of 64 bytes each:
  *     struct rime_hmat_tile { const void* a; long long ld, src_off, dst_off; double scale; int rows, cols, flags, stage;
