@@ -123,6 +123,7 @@ SIGNATURES = {
     'rime_hmat_apply': (_i, [_i, _vp, _i, _vp, _vp, _ip, _i, _ll, _vp, _vp, _i, _d, _i, _vp, _sz, _vp]),
     'rime_vis_timeavg_fwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ip, _ip, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'rime_vis_timeavg_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _ip, _ip, _ip, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'rime_lcone_fwd': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _ip, _d, _i, _i, _i, _i, _i, _i, _i, _i, _ll, _vp, _vp]),
     'rime_coupling_workspace': (_sz, [_i] * 8),
     'rime_coupling_fwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'rime_coupling_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

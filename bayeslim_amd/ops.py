@@ -2999,6 +2999,50 @@ def rephase_phasor(tau, freqs, dtype=torch.complex64):
 
 
 # ---------------------------------------------------------------------------------------
+# lightcone sampling of periodic simulation boxes in one launch (csrc/lcone.hip)
+# ---------------------------------------------------------------------------------------
+LCONE_INTERP = {'nearest': 0, 'linear': 1}
+_LCONE_SPHERE, _LCONE_PLANE = 0, 1
+
+
+def lcone_sample(sims, dc, cube_idx, weight, S, sim_res, vec=None, roll=(0, 0, 0), interp='nearest'):
+    """
+    out[i, p] = sum_{s < S} weight[i, s] sample(sims[cube_idx[i, s]], vec[:, p] * dc[i] / sim_res) in one launch of
+    rime_lcone_fwd: sims (Nsim, Nx, Ny, Nz) float32 / float64 on the GPU; dc (Nr,) float64, cube_idx (Nr, 3) int32 and weight
+    (Nr, 3) float64 host arrays (the radial stencil table, S = 1 ... 3 columns used); vec (3, Npix) float64 host array or GPU
+    tensor, or None for the plane mode (out (Nr, Nx, Ny), only z = dc / sim_res sampled); roll: three ints, any sign; interp
+    'nearest' or 'linear'.  Returns (Nr, Npix) in the dtype of sims.  Not differentiable (the reference function is not
+    either).  No CPU path.
+    """
+    _require_cuda(sims)
+    assert sims.ndim == 4 and sims.dtype in (torch.float32, torch.float64)
+    dev = sims.device
+    sims = _dense(sims)
+    code, _ = _real_dtype(sims)
+    Nsim, Nx, Ny, Nz = sims.shape
+    dc = np.ascontiguousarray(dc, dtype=np.float64).reshape(-1)
+    Nr = dc.size
+    cube_idx = np.ascontiguousarray(cube_idx, dtype=np.int32).reshape(Nr, 3)
+    weight = np.ascontiguousarray(weight, dtype=np.float64).reshape(Nr, 3)
+    if vec is None:
+        mode, Npix, vdev, shape = _LCONE_PLANE, Nx * Ny, None, (Nr, Nx, Ny)
+    else:
+        vdev = torch.as_tensor(vec, dtype=torch.float64).to(dev).contiguous()
+        assert vdev.ndim == 2 and vdev.shape[0] == 3
+        mode, Npix, shape = _LCONE_SPHERE, vdev.shape[1], (Nr, vdev.shape[1])
+    rx, ry, rz = (int(r) % n for r, n in zip(roll, (Nx, Ny, Nz)))
+    out = torch.empty(shape, dtype=sims.dtype, device=dev)
+    if out.numel() == 0:
+        return out
+    d_dc, d_idx, d_w = torch.as_tensor(dc).to(dev), torch.as_tensor(cube_idx).to(dev), torch.as_tensor(weight).to(dev)
+    rc = lib.rime_lcone_fwd(code, mode, LCONE_INTERP[interp], int(S), _ptr(sims), _ptr(vdev), _ptr(d_dc), _ptr(d_idx),
+                            _ptr(d_w), _host_ip(cube_idx), float(sim_res), rx, ry, rz, Nsim, Nx, Ny, Nz, Nr, Npix,
+                            _ptr(out), _stream())
+    check(rc, 'rime_lcone_fwd')
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # antenna mutual coupling: W = E V E^H on one batched complex product kernel (csrc/coupling.hip)
 # ---------------------------------------------------------------------------------------
 COUPLING_CONJ = 1 << 30                          # table word: the row is read conjugated (ftab: no conjugated reader)

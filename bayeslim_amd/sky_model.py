@@ -149,10 +149,10 @@ class PixelSkyResponse:
     params (Nstokes, 1, Nfreq_coeff, Npix_coeff) -> sky (Nstokes, 1, Nfreqs, Npix)
     (sky_model.py:503-720).  spatial_mode 'pixel' | 'linear' | 'alm' (spat_LM = linear_model.LinearModel /
     AlmModel); freq_mode 'channel' | 'linear' (freq_LM = linear_model.LinearModel along dim=-2, e.g.
-    LinearModel('poly', dim=-2, x=freqs, Ndeg=6, basis='legendre')) | 'powerlaw'.  freq_mode='bessel' (which builds its radial basis from the
-    cosmology module) raises; a spherical Fourier-Bessel sky is composed instead from the pieces that are built, with the
-    comoving distance r of every channel as an input:
-        sfb = sph_harm.SFBModel(); sfb.setup_gln(l, r=r, m=m, r_min=..., r_max=..., kmax=..., r_crit=...)
+    LinearModel('poly', dim=-2, x=freqs, Ndeg=6, basis='legendre')) | 'powerlaw'.  freq_mode='bessel' (a legacy branch that
+    sph_harm.SFBModel supersedes) raises; a spherical Fourier-Bessel sky is composed from the pieces that are built, with the
+    comoving distance of every channel from the cosmology module (which also fills `cosmo`):
+        r = cosmology.Cosmology().f2r(freqs); sfb = sph_harm.SFBModel(); sfb.setup_gln(l, r=r, m=m, r_min=..., r_max=..., kmax=..., r_crit=...)
         R = PixelSkyResponse(freqs, spatial_mode='alm', spat_LM=alm_model, LM=sfb)      # params: complex (Nstokes, 1, Nlmn)
     """
     def __init__(self, freqs, comp_params=False, spatial_mode='pixel', freq_mode='channel',
@@ -160,8 +160,9 @@ class PixelSkyResponse:
                  gln=None, kbins=None, log=False, real_output=True, abs_output=False, LM=None,
                  sky0=None):
         if freq_mode == 'bessel':
-            raise NotImplementedError("freq_mode='bessel' is not built (it needs the cosmology module); use spatial_mode='alm' "
-                                      "with spat_LM=AlmModel and LM=sph_harm.SFBModel set up on the channels' comoving distances")
+            raise NotImplementedError("freq_mode='bessel' is not built (sph_harm.SFBModel supersedes it); use spatial_mode='alm' "
+                                      "with spat_LM=AlmModel and LM=sph_harm.SFBModel set up on the channels' comoving distances "
+                                      "(cosmology.Cosmology().f2r(freqs))")
         self.freqs = freqs
         self.comp_params = comp_params
         self.Nfreqs = len(freqs)

@@ -8,8 +8,8 @@ kernel `rime_sfb_fwd/bwd` (one launch for all degrees).
 
 Out of scope (one-off host setup in the reference): cut-sky (cap / stripe)
 non-integer-degree bases built from hypergeometric functions, HDF5 Ylm files; of the SFB layer
-`SFBModel.least_squares` (needs the reference's linalg module), boundary condition 3 and the cosmology
-(frequency -> comoving distance: r is an input).
+`SFBModel.least_squares` (needs the reference's linalg module) and boundary condition 3.  The comoving distance r of
+every channel, an input of `SFBModel.setup_gln`, comes from `cosmology.Cosmology().f2r(freqs)`.
 """
 import copy
 import math

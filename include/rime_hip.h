@@ -909,6 +909,34 @@ int rime_partred_bwd_coeff(int dtype, int NP, const void* V, const void* G, cons
                            long long vst_t, long long vst_f, void* gc, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Lightcone sampling of periodic simulation boxes (cosmology.cube2lcone / cube2map; reference cosmology.py:237-427;
+ * csrc/lcone.hip): every (radius i, pixel p) output in one launch,
+ *     out[i, p] = sum over s < S of  weight[i, s] sample(sims[cube_idx[i, s]], position(i, p))
+ *   sims      T [Nsim][Nx][Ny][Nz], contiguous (z fastest);  out  T [Nr][Npix]
+ *   mode      RIME_LCONE_SPHERE: position = (vec[:, p] * dc[i]) / sim_res per axis, vec DEVICE float64 [3][Npix];
+ *             RIME_LCONE_PLANE: pixel p = x Ny + y is the cube's own column (x, y), only z = dc[i] / sim_res is sampled;
+ *             Npix must be Nx Ny and vec is not read (may be null)
+ *   interp    RIME_LCONE_NEAREST: the voxel at rint(position) (half to even);  RIME_LCONE_LINEAR: trilinear (PLANE: linear
+ *             in z) between floor(position) and floor(position) + 1, fraction position - floor(position) rounded once to T
+ *   dc        DEVICE float64 [Nr];  cube_idx DEVICE int32 [Nr][3], weight DEVICE float64 [Nr][3]: the radial stencil of
+ *             every radius, its first S (1 ... 3) columns used, weights rounded once to T;  cube_idx_host: a HOST copy
+ *   rx ry rz  the roll of the cube along its axes, reduced to [0, N): the rolled cube at i is the cube at (i - r) mod N
+ * Positions are float64 for either T; indices are taken modulo the extents, non-negative, the box tiling all space; offsets
+ * are 64-bit.  One lane per output, a fixed operation order (csrc/lcone.hip), no atomics: bit-reproducible.
+ * Checked before any HIP call (RIME_EINVAL): an unknown dtype, mode or interp, S outside [1, 3], an extent, Nr or Npix < 1, a
+ * null sims, dc, cube_idx, weight, cube_idx_host or out, a null vec in SPHERE mode, Npix != Nx Ny in PLANE mode, sim_res not
+ * positive and finite, a roll outside [0, N), a cube_idx_host entry (of the first S columns) outside [0, Nsim).  The device
+ * table is not inspected by the host (the kernel clamps its entries).
+ * ------------------------------------------------------------------------------------- */
+#define RIME_LCONE_SPHERE 0
+#define RIME_LCONE_PLANE 1
+#define RIME_LCONE_NEAREST 0
+#define RIME_LCONE_LINEAR 1
+int rime_lcone_fwd(int dtype, int mode, int interp, int S, const void* sims, const double* vec, const double* dc,
+                   const int* cube_idx, const double* weight, const int* cube_idx_host, double sim_res, int rx, int ry,
+                   int rz, int Nsim, int Nx, int Ny, int Nz, int Nr, long long Npix, void* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Collectives of the sharded RIME step over RCCL (the replacement of DistributedLogProb.closure's per-device
  * Python loop, optim.py:1539-1566).  Thin wrappers: raw device pointers, the caller's stream, no allocation.
  * RCCL is resolved at first use (the copy already loaded into the process wins); without it every call
