@@ -119,6 +119,9 @@ SIGNATURES = {
     'rime_nuts_workspace': (_sz, [_ll]),
     'rime_nuts_leaf_open': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp]),
     'rime_nuts_leaf_close': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'rime_mass_workspace': (_sz, [_ll]),
+    'rime_mass_project': (_i, [_i, _ll, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp]),
+    'rime_mass_drift': (_i, [_i, _ll, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'rime_hmat_workspace': (_sz, [_i, _ll, _i]),
     'rime_hmat_apply': (_i, [_i, _vp, _i, _vp, _vp, _ip, _i, _ll, _vp, _vp, _i, _d, _i, _vp, _sz, _vp]),
     'rime_vis_timeavg_fwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _ip, _ip, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

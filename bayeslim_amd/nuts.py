@@ -27,6 +27,7 @@ Not provided:
   * Betancourt's generalised (momentum-sum) no-U-turn criterion, which the reference names as a TODO: the criterion is
     Hoffman & Gelman's
 and what sampler.HMC refuses is refused here in the same words: dense and hmat mass matrices, pmask, complex step sizes.
+Dense mass matrices per key are massmat.NUTS, which replaces the leaf by the launches of csrc/massmat.hip.
 """
 import math
 
@@ -124,6 +125,8 @@ class NUTS(sampler.HMC):
     track_states : keep (q, p, U) of every state of a move's tree in TreeInfo.states;  sample_direction : draw the direction of
     every doubling (False: always forward).  After a move that ends in its Metropolis test `_base_tree` is its tree.
     """
+    _kinetic_launches = 1                                    # launches of the move's starting energy (massmat.NUTS: two)
+
     def __init__(self, potential_fn, x0, eps, cov_L=None, hess_L=None, diag_mass=True, pdist=None, pmask=None, dHmax=1000,
                  record_divergences=False, max_tree_depth=6, biased=True, track_states=False, sample_direction=True):
         super().__init__(potential_fn, x0, eps, cov_L=cov_L, hess_L=hess_L, diag_mass=diag_mass, Nstep=1, pdist=pdist, pmask=pmask,
@@ -233,7 +236,7 @@ class NUTS(sampler.HMC):
         else:
             lay.pack(self.p, tr.p)
         K_start = tr.kinetic(self._c) + self._logdetM
-        self.launches += 1
+        self.launches += self._kinetic_launches
         q0 = lay.pack(self.x, lay.new())
         start = _State(lay, q0, tr.p.clone(), lay.new())
         with torch.enable_grad():

@@ -22,6 +22,7 @@ Not provided (each raises NotImplementedError naming what is missing):
   * HMC.estimate_cov
 The No-U-Turn sampler is bayeslim_amd.nuts (NUTS and TreeInfo on the tree-leaf kernels of csrc/nuts.hip); the two names here
 stay stubs.
+Dense mass matrices per key are bayeslim_amd.massmat (leapfrog, HMC and NUTS on the triangular kernels of csrc/massmat.hip).
 """
 import math
 import os
@@ -384,17 +385,13 @@ class HMC(SamplerBase):
             _missing('pmask (momentum masks)')
         if not isinstance(x0, ParamDict):
             raise TypeError('sampler.HMC: x0 must be a ParamDict')
-        _check_diag(diag_mass, None)
+        self._judge_diag(diag_mass)
         self._lay = _Layout(x0)
-        for L, what in ((eps, 'eps'), (cov_L, 'cov_L'), (hess_L, 'hess_L')):
-            if isinstance(L, (dict, ParamDict)) or what == 'eps':
-                self._lay.classify(L, what)
-            elif L is not None:
-                raise NotImplementedError(_HMAT % what + ' [got %s]' % type(L).__name__)
+        self._judge_mass(eps, cov_L, hess_L, diag_mass)
         self._lay.require_cuda()                                 # the arguments are judged first, then the device
         super().__init__(x0)
         self._lists += ['_divergences']
-        self._traj = _Trajectory(self._lay)
+        self._traj = self._new_trajectory()
         self.potential_fn = potential_fn
         self.fn_evals = 0
         self.Nstep = Nstep
@@ -411,6 +408,20 @@ class HMC(SamplerBase):
         self.pmask = None
         self._last = {}
         self.set_chol(cov_L=cov_L, hess_L=hess_L, diag_mass=diag_mass)
+
+    # ------------------------------------------------------------------ what a subclass with another mass replaces (massmat)
+    def _judge_diag(self, diag_mass):
+        _check_diag(diag_mass, None)
+
+    def _judge_mass(self, eps, cov_L, hess_L, diag_mass):
+        for L, what in ((eps, 'eps'), (cov_L, 'cov_L'), (hess_L, 'hess_L')):
+            if isinstance(L, (dict, ParamDict)) or what == 'eps':
+                self._lay.classify(L, what)
+            elif L is not None:
+                raise NotImplementedError(_HMAT % what + ' [got %s]' % type(L).__name__)
+
+    def _new_trajectory(self):
+        return _Trajectory(self._lay)
 
     # ------------------------------------------------------------------ step size and mass
     @property

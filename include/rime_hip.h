@@ -705,6 +705,49 @@ int rime_nuts_leaf_close(int dtype, long long N, const void* q1, void* p1, const
                          size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One leapfrog stage with a block-dense mass matrix (massmat.leapfrog, massmat.HMC, massmat.NUTS; reference sampler.py:260-450,
+ * 489-546, 1516-1554): the flat real vector of rime_hmc_step, with a DEVICE table of nblocks blocks of 64 bytes each:
+ *     struct rime_mass_block { const void* L; long long ld, off; int n, nrhs; long long reserved[4]; };
+ *   L      real T [n][ld], ld >= n: the lower-triangular Cholesky factor of one key's covariance; only L[i][j], j <= i, is read.
+ *          A base and an ld that are multiples of 16 bytes take 16-byte loads (of groups wholly at or below the diagonal), any
+ *          other placement element loads of the same elements: same bits.
+ *   off    first flat element of the block, which covers off ... off + n nrhs - 1;  nrhs 1 (a real key) or 2 (the interleaved
+ *          real view of a complex key: the same real L acts on both components).  Blocks do not overlap.  Elements that no
+ *          block covers are diagonal with the factor c (NULL: ones), as in rime_hmc_step.
+ * rime_mass_project, per element and in T:
+ *     p_out = fma(-(T(kick) * eps), g, p_in)        (kick = 0: p_in is used as it is; g and p_out may be NULL)
+ *     z = L^T p_out on every block,  z = c * p_out elsewhere
+ *   With kick != 0, p_out must not overlap p_in; z must overlap neither.
+ * rime_mass_drift, per element and in T:
+ *     q_out = fma(T(drift) * eps, L z, q_in) on every block,  fma(T(drift) * eps, c * z, q_in) elsewhere     (drift != 0)
+ *   q_out may be q_in; with drift = 0 nothing is written and q_in, q_out may be NULL.  out, double [3] on the device or NULL:
+ *     out[0] = 1/2 sum z^2;   out[1] = sum (q - q_far) * p_far;   out[2] = sum (q - q_far) * p
+ *   with q the position after the call (q_out, or q_in when q_out is NULL); out[1], out[2] only when p, q_far and p_far are
+ *   given (all three or none).  The three sums run in the order of rime_hmc_step's energy / rime_nuts_leaf_close over ALL
+ *   elements; partial sums go to the workspace (rime_mass_workspace(N) bytes, either dtype; needed only with out).
+ * Summation order of the triangular products, all in T, W = 16 / sizeof(T):
+ *   L z     row i: lane l of a wave runs one chain acc = fma(L[i][j], z[j], acc) from 0 over its columns j <= i ascending -- the
+ *           columns 256 W q + (64 g + l) W + e, q = 0, 1, ..., g = 0 .. 3, e < W -- then the butterfly over the 64 lanes
+ *           (partners 32, 16, 8, 4, 2, 1 apart).
+ *   L^T p   column j: slot s of 32 runs one chain acc = fma(L[i][j], p[i], acc) from 0 over the rows i >= j, i = s (mod 32),
+ *           ascending; slots 8 w + u are added by a butterfly over u (partners 4, 2, 1), then ((w0 + w1) + w2) + w3 over w.
+ *   An output element's bits depend on its own block's L, n and the vector alone: not on ld, the alignment, the other blocks or
+ *   the launch.  No atomics; each call is a fixed sequence of kernels on `stream`, and no work-group waits for another.  With
+ *   nblocks = 0, project then drift give the bits of rime_hmc_step (p, q, energy) and of rime_nuts_leaf_close (the three sums).
+ * Checked before any HIP call: RIME_EINVAL for an unknown dtype, N < 0, nblocks < 0, a null table with nblocks > 0, a null p_in
+ * or z, a null g or p_out with kick != 0, a null q_in or q_out with drift != 0, the overlaps named above, only some of p, q_far,
+ * p_far, a NaN kick or drift or one that rounds to zero in T; RIME_EWORKSPACE for a null or short workspace with out (looked at
+ * before the rounding, as in rime_hmc_step).  The device table is not inspected by the host; an entry that does not fit the
+ * vector (n < 1, nrhs outside {1, 2}, ld < n, off < 0, off + n nrhs > N) is skipped on the device.
+ * ------------------------------------------------------------------------------------- */
+size_t rime_mass_workspace(long long N);
+int rime_mass_project(int dtype, long long N, const void* blocks, int nblocks, const void* p_in, const void* g, const void* eps,
+                      const void* c, double kick, void* p_out, void* z, void* stream);
+int rime_mass_drift(int dtype, long long N, const void* blocks, int nblocks, const void* z, const void* q_in, const void* eps,
+                    const void* c, double drift, void* q_out, const void* p, const void* q_far, const void* p_far, double* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Grouped block mat-vec of a flattened operator tree (hmat.BaseMat.mat_vec_mul / mat_mat_mul; reference hmat.py): y (+)=
  * scalar * A x, A given as a DEVICE table of ntiles tiles of 64 bytes each:
  *     struct rime_hmat_tile { const void* a; long long ld, src_off, dst_off; double scale; int rows, cols, flags, stage;
