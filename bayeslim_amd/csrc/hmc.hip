@@ -81,8 +81,7 @@ __global__ __launch_bounds__(HMC_THREADS) void hmc_step_kernel(T* q, T* p, const
 // energy[0] = 1/2 sum_b partial[b]; one wave
 __global__ __launch_bounds__(64) void hmc_energy_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ energy)
 {
-    const double s = partial_sum(partial, nb);
-    if (threadIdx.x == 0) energy[0] = 0.5 * s;
+    hmc_final(partial, nb, 1, energy);
 }
 
 template <typename T>
@@ -103,23 +102,18 @@ static int hmc_step(long long N, void* q, void* p, const void* g, const void* ep
 
 using namespace rime;
 
-// one partial per work-group of the smaller span (float64), so that the workspace serves either dtype
-extern "C" size_t rime_hmc_workspace(long long N)
-{
-    if (N < 0 || N > 0x3fffffffffffffffLL) return 0;
-    const long long nb = std::max<long long>(1, std::min<long long>(hmc_chunks(N, RIME_F64), HMC_MAXBLOCKS));
-    return (size_t)nb * sizeof(double);
-}
+// one partial per work-group
+extern "C" size_t rime_hmc_workspace(long long N) { return hmc_workspace_bytes(N, 1); }
 
 extern "C" int rime_hmc_step(int dtype, long long N, void* q, void* p, const void* g, const void* eps, const void* c, double kick,
                              double drift, double* energy, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (!real_dtype_ok(dtype) || N < 0 || N > 0x3fffffffffffffffLL || !p) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype) || !hmc_size_ok(N) || !p) return RIME_EINVAL;
     if (!(kick == kick) || !(drift == drift)) return RIME_EINVAL;                      // NaN flags
     if ((kick != 0.0 && !g) || (drift != 0.0 && !q)) return RIME_EINVAL;
     if (energy != nullptr && (!workspace || workspace_bytes < rime_hmc_workspace(N))) return RIME_EWORKSPACE;
     // a flag that rounds to zero in the working type would skip its pass: refuse it
-    if (dtype == RIME_F32 && ((kick != 0.0 && (float)kick == 0.0f) || (drift != 0.0 && (float)drift == 0.0f))) return RIME_EINVAL;
+    if (hmc_flag_underflows(dtype, kick) || hmc_flag_underflows(dtype, drift)) return RIME_EINVAL;
     if (kick == 0.0 && drift == 0.0 && energy == nullptr) return RIME_OK;               // nothing to do
     return with_real(dtype, [&](auto t) {
         return hmc_step<decltype(t)>(N, q, p, g, eps, c, kick, drift, energy, (double*)workspace, as_stream(stream), dtype);

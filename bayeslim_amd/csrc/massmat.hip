@@ -327,10 +327,7 @@ __global__ __launch_bounds__(HMC_THREADS) void mass_drift_kernel(const mass_bloc
 // wave k of `nsums`: out[k] = sum_b partial[k nb + b], the first halved
 __global__ __launch_bounds__(192) void mass_final_kernel(const double* __restrict__ partial, int nb, int nsums, double* __restrict__ out)
 {
-    const int k = threadIdx.x >> 6;
-    if (k >= nsums) return;
-    const double s = partial_sum(partial + (size_t)k * nb, nb);
-    if ((threadIdx.x & 63) == 0) out[k] = k == 0 ? 0.5 * s : s;
+    hmc_final(partial, nb, nsums, out);
 }
 
 template <typename T>
@@ -368,32 +365,17 @@ static int mass_drift(long long N, const mass_block* blocks, int nblocks, const 
     return check_launch();
 }
 
-// [a, a + bytes) and [b, b + bytes) share a byte (null: no)
-static bool mass_overlap(const void* a, const void* b, size_t bytes)
-{
-    if (!a || !b) return false;
-    const unsigned long long x = (unsigned long long)a, y = (unsigned long long)b;
-    return x < y + bytes && y < x + bytes;
-}
-
 static bool mass_size_ok(long long N, int nblocks)
 {
-    return N >= 0 && N <= 0x3fffffffffffffffLL && nblocks >= 0 && mass_grid(N, nblocks, MASS_ROWS) <= 0x7fffffffLL;
+    return hmc_size_ok(N) && nblocks >= 0 && mass_grid(N, nblocks, MASS_ROWS) <= 0x7fffffffLL;
 }
-
-// a flag that is not zero but rounds to zero in the working type would skip its pass
-static bool mass_flag_underflows(int dtype, double f) { return dtype == RIME_F32 && f != 0.0 && (float)f == 0.0f; }
 
 } // namespace rime
 
 using namespace rime;
 
-// three partials per work-group of the smaller span (float64), so that the workspace serves either dtype
-extern "C" size_t rime_mass_workspace(long long N)
-{
-    if (N < 0 || N > 0x3fffffffffffffffLL) return 0;
-    return 3 * (size_t)std::max(1, hmc_blocks(N, RIME_F64)) * sizeof(double);
-}
+// three partials per work-group
+extern "C" size_t rime_mass_workspace(long long N) { return hmc_workspace_bytes(N, 3); }
 
 extern "C" int rime_mass_project(int dtype, long long N, const void* blocks, int nblocks, const void* p_in, const void* g,
                                  const void* eps, const void* c, double kick, void* p_out, void* z, void* stream)
@@ -402,9 +384,9 @@ extern "C" int rime_mass_project(int dtype, long long N, const void* blocks, int
     if (!(kick == kick)) return RIME_EINVAL;
     if (kick != 0.0 && (!g || !p_out)) return RIME_EINVAL;
     const size_t bytes = (size_t)N * real_bytes(dtype);
-    if (kick != 0.0 && mass_overlap(p_out, p_in, bytes)) return RIME_EINVAL;
-    if (mass_overlap(z, p_in, bytes) || (kick != 0.0 && mass_overlap(z, p_out, bytes))) return RIME_EINVAL;
-    if (mass_flag_underflows(dtype, kick)) return RIME_EINVAL;
+    if (kick != 0.0 && hmc_overlap(p_out, p_in, bytes)) return RIME_EINVAL;
+    if (hmc_overlap(z, p_in, bytes) || (kick != 0.0 && hmc_overlap(z, p_out, bytes))) return RIME_EINVAL;
+    if (hmc_flag_underflows(dtype, kick)) return RIME_EINVAL;
     return with_real(dtype, [&](auto t) {
         return mass_project<decltype(t)>(N, (const mass_block*)blocks, nblocks, p_in, g, eps, c, kick, p_out, z, as_stream(stream), dtype);
     });
@@ -421,9 +403,9 @@ extern "C" int rime_mass_drift(int dtype, long long N, const void* blocks, int n
     if (given != 0 && given != 3) return RIME_EINVAL;
     if (given == 3 && out != nullptr && !q_in && !q_out) return RIME_EINVAL;           // projections of no position
     const size_t bytes = (size_t)N * real_bytes(dtype);
-    if (drift != 0.0 && (mass_overlap(q_out, z, bytes) || (q_out != q_in && mass_overlap(q_out, q_in, bytes)))) return RIME_EINVAL;
+    if (drift != 0.0 && (hmc_overlap(q_out, z, bytes) || (q_out != q_in && hmc_overlap(q_out, q_in, bytes)))) return RIME_EINVAL;
     if (out != nullptr && (!workspace || workspace_bytes < rime_mass_workspace(N))) return RIME_EWORKSPACE;
-    if (mass_flag_underflows(dtype, drift)) return RIME_EINVAL;
+    if (hmc_flag_underflows(dtype, drift)) return RIME_EINVAL;
     if (drift == 0.0 && out == nullptr) return RIME_OK;                                  // nothing to do
     return with_real(dtype, [&](auto t) {
         return mass_drift<decltype(t)>(N, (const mass_block*)blocks, nblocks, z, q_in, eps, c, drift, q_out, p, q_far, p_far, out,

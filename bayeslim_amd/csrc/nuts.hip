@@ -122,10 +122,7 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_leaf_close_kernel(const T* _
 // wave k of `nsums`: out[k] = sum_b partial[k nb + b], the first halved
 __global__ __launch_bounds__(192) void nuts_leaf_final_kernel(const double* __restrict__ partial, int nb, int nsums, double* __restrict__ out)
 {
-    const int k = threadIdx.x >> 6;
-    if (k >= nsums) return;
-    const double s = partial_sum(partial + (size_t)k * nb, nb);
-    if ((threadIdx.x & 63) == 0) out[k] = k == 0 ? 0.5 * s : s;
+    hmc_final(partial, nb, nsums, out);
 }
 
 template <typename T>
@@ -159,37 +156,25 @@ static int nuts_close(long long N, const void* q1, void* p1, const void* g1, con
     return check_launch();
 }
 
-// [a, a + bytes) and [b, b + bytes) share a byte (null: no)
-static bool nuts_overlap(const void* a, const void* b, size_t bytes)
-{
-    if (!a || !b) return false;
-    const unsigned long long x = (unsigned long long)a, y = (unsigned long long)b;
-    return x < y + bytes && y < x + bytes;
-}
-
-// the signed step: a number, not zero, and with a half that is not zero in T
+// the signed step: a number, not zero, and with a half that is not zero in T (nor in float64)
 static int nuts_step_ok(double h) { return h == h && h != 0.0; }
-static bool nuts_step_underflows(int dtype, double h) { return dtype == RIME_F32 ? (float)(h / 2) == 0.0f : h / 2 == 0.0; }
+static bool nuts_step_underflows(int dtype, double h) { return h / 2 == 0.0 || hmc_flag_underflows(dtype, h / 2); }
 
 } // namespace rime
 
 using namespace rime;
 
-// three partials per work-group of the smaller span (float64), so that the workspace serves either dtype
-extern "C" size_t rime_nuts_workspace(long long N)
-{
-    if (N < 0 || N > 0x3fffffffffffffffLL) return 0;
-    return 3 * (size_t)std::max(1, hmc_blocks(N, RIME_F64)) * sizeof(double);
-}
+// three partials per work-group
+extern "C" size_t rime_nuts_workspace(long long N) { return hmc_workspace_bytes(N, 3); }
 
 extern "C" int rime_nuts_leaf_open(int dtype, long long N, const void* q0, const void* p0, const void* g0, void* q1, void* p1,
                                    const void* eps, const void* c, double h, void* stream)
 {
-    if (!real_dtype_ok(dtype) || N < 0 || N > 0x3fffffffffffffffLL || !q0 || !p0 || !g0 || !q1 || !p1) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype) || !hmc_size_ok(N) || !q0 || !p0 || !g0 || !q1 || !p1) return RIME_EINVAL;
     const size_t bytes = (size_t)N * real_bytes(dtype);
     for (const void* in : {q0, p0, g0, eps, c})
-        if (nuts_overlap(q1, in, bytes) || nuts_overlap(p1, in, bytes)) return RIME_EINVAL;
-    if (nuts_overlap(q1, p1, bytes)) return RIME_EINVAL;
+        if (hmc_overlap(q1, in, bytes) || hmc_overlap(p1, in, bytes)) return RIME_EINVAL;
+    if (hmc_overlap(q1, p1, bytes)) return RIME_EINVAL;
     if (!nuts_step_ok(h) || nuts_step_underflows(dtype, h)) return RIME_EINVAL;
     return with_real(dtype, [&](auto t) {
         return nuts_open<decltype(t)>(N, q0, p0, g0, q1, p1, eps, c, h, as_stream(stream), dtype);
@@ -200,7 +185,7 @@ extern "C" int rime_nuts_leaf_close(int dtype, long long N, const void* q1, void
                                     double h, const void* q_far, const void* p_far, double* out, void* workspace,
                                     size_t workspace_bytes, void* stream)
 {
-    if (!real_dtype_ok(dtype) || N < 0 || N > 0x3fffffffffffffffLL || !q1 || !p1 || !g1 || !out) return RIME_EINVAL;
+    if (!real_dtype_ok(dtype) || !hmc_size_ok(N) || !q1 || !p1 || !g1 || !out) return RIME_EINVAL;
     if ((q_far == nullptr) != (p_far == nullptr)) return RIME_EINVAL;
     if (!nuts_step_ok(h)) return RIME_EINVAL;
     if (!workspace || workspace_bytes < rime_nuts_workspace(N)) return RIME_EWORKSPACE;

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib, hmat, nuts, sampler
-from .ops import _require_cuda, _stream, _ptr, _dtype_code
+from .ops import _require_cuda, _stream, _ptr
 from .paramdict import ParamDict
 
 # rows of a strip of the L z kernel, columns of a strip of the L^T p kernel (8 x 16 bytes), per precision
@@ -137,10 +137,7 @@ class BlockTable:
 
     def diagonal(self):
         """the flat diagonal factor (None: ones everywhere)"""
-        c = self.lay.expand(self._diag, self._what)
-        if isinstance(c, float):
-            c = None if c == 1.0 else torch.full((self.lay.N,), c, dtype=self.lay.rdtype, device=self.lay.device)
-        return c
+        return self.lay.factor(self._diag, self._what)
 
     def table(self):
         if self._table is None:
@@ -152,20 +149,9 @@ class BlockTable:
         return len(self.entries)
 
 
-def _check(first, others, what):
-    _require_cuda(first)
-    N = first.numel()
-    for t in others:
-        if t is not None and (t.dtype != first.dtype or t.numel() != N or t.device != first.device or not t.is_contiguous()):
-            raise ValueError('massmat: contiguous vectors of %s [%d] on %s are needed' % (first.dtype, N, first.device))
-    if first.is_complex() or not first.is_contiguous():
-        raise ValueError('massmat: %s takes contiguous real vectors (complex parameters as their interleaved views)' % what)
-    return N, _dtype_code(sampler._real_dtype(first.dtype))
-
-
 def project(table, p_in, g, eps, c, kick, p_out, z):
     """one call of rime_mass_project on flat real vectors (see include/rime_hip.h); table from make_table or None"""
-    N, code = _check(p_in, (g, eps, c, p_out, z), 'project')
+    N, code = sampler._check_vectors('massmat', 'project', p_in, (g, eps, c, p_out, z))
     with torch.cuda.device(p_in.device):
         _lib.check(_lib.lib.rime_mass_project(code, N, _ptr(table), 0 if table is None else table.shape[0], _ptr(p_in), _ptr(g),
                                               _ptr(eps), _ptr(c), float(kick), _ptr(p_out), _ptr(z), _stream()), 'rime_mass_project')
@@ -173,19 +159,16 @@ def project(table, p_in, g, eps, c, kick, p_out, z):
 
 def drift(table, z, q_in, eps, c, drift, q_out, p=None, q_far=None, p_far=None, out=None, ws=None):
     """one call of rime_mass_drift on flat real vectors (see include/rime_hip.h); out a float64 tensor of three elements or None"""
-    N, code = _check(z, (q_in, eps, c, q_out, p, q_far, p_far), 'drift')
-    nbytes = 0
-    if out is not None:
-        if out.dtype != torch.float64 or out.numel() < 3 or out.device != z.device or not out.is_contiguous():
-            raise ValueError('massmat: out must be a contiguous float64 tensor of three elements on %s' % z.device)
-        need = int(_lib.lib.rime_mass_workspace(N))
-        if ws is None or ws.numel() * 8 < need:
-            ws = torch.empty(need // 8, dtype=torch.float64, device=z.device)
-        nbytes = ws.numel() * 8
+    N, code = sampler._check_vectors('massmat', 'drift', z, (q_in, eps, c, q_out, p, q_far, p_far))
+    if out is None:
+        ws = None
+    else:
+        sampler._check_out('massmat', out, z.device)
+        ws = sampler._workspace(_lib.lib.rime_mass_workspace(N), z.device, ws)
     with torch.cuda.device(z.device):
         _lib.check(_lib.lib.rime_mass_drift(code, N, _ptr(table), 0 if table is None else table.shape[0], _ptr(z), _ptr(q_in), _ptr(eps),
                                             _ptr(c), float(drift), _ptr(q_out), _ptr(p), _ptr(q_far), _ptr(p_far), _ptr(out),
-                                            _ptr(ws if out is not None else None), nbytes, _stream()), 'rime_mass_drift')
+                                            _ptr(ws), 0 if ws is None else ws.numel() * 8, _stream()), 'rime_mass_drift')
 
 
 class _Trajectory(sampler._Trajectory):
@@ -196,7 +179,7 @@ class _Trajectory(sampler._Trajectory):
         self.owner = owner                                        # holds _blocks (a BlockTable), set before the first stage
         self.p2, self.z = layout.new(), layout.new()
         self.out = torch.zeros(3, dtype=torch.float64, device=layout.device)
-        self.ws = torch.empty(int(_lib.lib.rime_mass_workspace(layout.N)) // 8, dtype=torch.float64, device=layout.device)
+        self.ws = sampler._workspace(_lib.lib.rime_mass_workspace(layout.N), layout.device)
 
     def stage(self, eps, c, kick, drift_, energy=False):
         """two launches; eps a float (folded into kick and drift) or a flat vector; returns the kinetic energy if asked"""
@@ -242,9 +225,8 @@ def leapfrog(q, p, dUdq, eps, N, cov_L=None, diag_mass=True, dUdq0=None, states=
         lay.pack(q, traj.q)
         lay.pack(p, traj.p)
         traj.run(dUdq, e, blocks.diagonal(), N, dUdq0=dUdq0, states=states)
-        for k in lay.keys:
-            (q if lay.tensor else q[k]).copy_(lay.view(traj.q, k))
-            (p if lay.tensor else p[k]).copy_(lay.view(traj.p, k))
+        lay.unpack(traj.q, q)
+        lay.unpack(traj.p, p)
     return q, p
 
 

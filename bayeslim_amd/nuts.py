@@ -35,19 +35,8 @@ import numpy as np
 import torch
 
 from . import _lib, sampler
-from .ops import _require_cuda, _stream, _ptr, _dtype_code
+from .ops import _stream, _ptr
 from .paramdict import ParamDict
-
-
-def _check_vectors(first, others, what):
-    _require_cuda(first)
-    N = first.numel()
-    for t in others:
-        if t is not None and (t.dtype != first.dtype or t.numel() != N or t.device != first.device or not t.is_contiguous()):
-            raise ValueError('nuts: contiguous vectors of %s [%d] on %s are needed' % (first.dtype, N, first.device))
-    if first.is_complex() or not first.is_contiguous():
-        raise ValueError('nuts: %s takes contiguous real vectors (complex parameters as their interleaved views)' % what)
-    return N, _dtype_code(sampler._real_dtype(first.dtype))
 
 
 def leaf_open(q0, p0, g0, q1, p1, eps, c, h):
@@ -55,7 +44,7 @@ def leaf_open(q0, p0, g0, q1, p1, eps, c, h):
     One launch of rime_nuts_leaf_open on flat real vectors (see include/rime_hip.h): q0, p0, g0 read only; q1, p1 written;
     eps, c may be None; h the signed step.
     """
-    N, code = _check_vectors(p0, (q0, g0, q1, p1, eps, c), 'leaf_open')
+    N, code = sampler._check_vectors('nuts', 'leaf_open', p0, (q0, g0, q1, p1, eps, c))
     with torch.cuda.device(p0.device):
         _lib.check(_lib.lib.rime_nuts_leaf_open(code, N, _ptr(q0), _ptr(p0), _ptr(g0), _ptr(q1), _ptr(p1), _ptr(eps), _ptr(c),
                                                 float(h), _stream()), 'rime_nuts_leaf_open')
@@ -67,12 +56,9 @@ def leaf_close(q1, p1, g1, eps, c, h, q_far, p_far, out, ws=None):
     only (q_far and p_far both None: no projections); out a float64 tensor of three elements on the device; ws the workspace
     (allocated if None or short).
     """
-    N, code = _check_vectors(p1, (q1, g1, eps, c, q_far, p_far), 'leaf_close')
-    if out.dtype != torch.float64 or out.numel() < 3 or out.device != p1.device or not out.is_contiguous():
-        raise ValueError('nuts: out must be a contiguous float64 tensor of three elements on %s' % p1.device)
-    need = int(_lib.lib.rime_nuts_workspace(N))
-    if ws is None or ws.numel() * 8 < need:
-        ws = torch.empty(need // 8, dtype=torch.float64, device=p1.device)
+    N, code = sampler._check_vectors('nuts', 'leaf_close', p1, (q1, g1, eps, c, q_far, p_far))
+    sampler._check_out('nuts', out, p1.device)
+    ws = sampler._workspace(_lib.lib.rime_nuts_workspace(N), p1.device, ws)
     with torch.cuda.device(p1.device):
         _lib.check(_lib.lib.rime_nuts_leaf_close(code, N, _ptr(q1), _ptr(p1), _ptr(g1), _ptr(eps), _ptr(c), float(h), _ptr(q_far),
                                                  _ptr(p_far), _ptr(out), _ptr(ws), ws.numel() * 8, _stream()),
@@ -137,7 +123,7 @@ class NUTS(sampler.HMC):
         self.sample_direction = sample_direction
         self.launches = 0
         self._out = torch.zeros(3, dtype=torch.float64, device=self._lay.device)
-        self._ws = torch.empty(int(_lib.lib.rime_nuts_workspace(self._lay.N)) // 8, dtype=torch.float64, device=self._lay.device)
+        self._ws = sampler._workspace(_lib.lib.rime_nuts_workspace(self._lay.N), self._lay.device)
 
     # ------------------------------------------------------------------ the criterion and the merge
     def is_turning(self, tree):

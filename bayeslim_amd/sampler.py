@@ -56,28 +56,47 @@ def _real_dtype(dtype):
     raise TypeError('sampler: float32 / float64 (or complex64 / complex128) parameters only, got %s' % dtype)
 
 
+def _check_vectors(module, what, first, others, dtype_first=False):
+    """
+    The call layer of the flat-vector kernels (hmc_step here, nuts.leaf_open / leaf_close, massmat.project / drift): `first`, a
+    contiguous real vector on the GPU, sets dtype, length and device, and every other vector that is given agrees with it.
+    Returns (N, dtype code); raises in the words of `module`.  A dtype that is not provided is named after the operands have
+    been judged, or before them with dtype_first (hmc_step's order).
+    """
+    _require_cuda(first)
+    code = _dtype_code(_real_dtype(first.dtype)) if dtype_first else None
+    N = first.numel()
+    for t in others:
+        if t is not None and (t.dtype != first.dtype or t.numel() != N or t.device != first.device or not t.is_contiguous()):
+            raise ValueError('%s: contiguous vectors of %s [%d] on %s are needed' % (module, first.dtype, N, first.device))
+    if first.is_complex() or not first.is_contiguous():
+        raise ValueError('%s: %s takes contiguous real vectors (complex parameters as their interleaved views)' % (module, what))
+    return N, (_dtype_code(_real_dtype(first.dtype)) if code is None else code)
+
+
+def _check_out(module, out, device):
+    """the three doubles (energy and the two projections) a kernel writes"""
+    if out.dtype != torch.float64 or out.numel() < 3 or out.device != device or not out.is_contiguous():
+        raise ValueError('%s: out must be a contiguous float64 tensor of three elements on %s' % (module, device))
+
+
+def _workspace(need, device, ws=None):
+    """ws if it holds at least `need` bytes (what a rime_*_workspace call answered), else a fresh workspace of that size"""
+    if ws is None or ws.numel() * 8 < need:
+        ws = torch.empty(int(need) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
 def hmc_step(q, p, g, eps, c, kick, drift, energy=None, ws=None):
     """
     One launch of rime_hmc_step on flat real vectors (see include/rime_hip.h): q, p in place; g, eps, c may be None as the
     header allows; energy a float64 tensor of one element or None; ws the workspace for the energy (allocated if None).
     """
-    _require_cuda(p)
-    N, code = p.numel(), _dtype_code(_real_dtype(p.dtype))
-    for t in (q, g, eps, c):
-        if t is not None and (t.dtype != p.dtype or t.numel() != N or t.device != p.device or not t.is_contiguous()):
-            raise ValueError('sampler: contiguous vectors of %s [%d] on %s are needed' % (p.dtype, N, p.device))
-    if p.is_complex() or not p.is_contiguous():
-        raise ValueError('sampler: hmc_step takes contiguous real vectors (complex parameters as their interleaved views)')
-    nbytes = 0
-    if energy is not None:
-        need = int(_lib.lib.rime_hmc_workspace(N))
-        if ws is None or ws.numel() * 8 < need:
-            ws = torch.empty(need // 8, dtype=torch.float64, device=p.device)
-        nbytes = ws.numel() * 8
+    N, code = _check_vectors('sampler', 'hmc_step', p, (q, g, eps, c), dtype_first=True)
+    ws = None if energy is None else _workspace(_lib.lib.rime_hmc_workspace(N), p.device, ws)
     with torch.cuda.device(p.device):
         _lib.check(_lib.lib.rime_hmc_step(code, N, _ptr(q), _ptr(p), _ptr(g), _ptr(eps), _ptr(c), float(kick), float(drift),
-                                          _ptr(energy), _ptr(ws if energy is not None else None), nbytes, _stream()),
-                   'rime_hmc_step')
+                                          _ptr(energy), _ptr(ws), 0 if ws is None else ws.numel() * 8, _stream()), 'rime_hmc_step')
 
 
 class _Layout:
@@ -132,6 +151,18 @@ class _Layout:
             self.view(buf, k).copy_(x if self.tensor else x[k])
         return buf
 
+    def unpack(self, buf, x):
+        """copy the buffer back into a container (same keys and shapes)"""
+        for k in self.keys:
+            (x if self.tensor else x[k]).copy_(self.view(buf, k))
+
+    def factor(self, val, what):
+        """expand(val, what) as a launch takes it: None when the factor is 1 everywhere, a flat vector otherwise"""
+        c = self.expand(val, what)
+        if isinstance(c, float):
+            c = None if c == 1.0 else torch.full((self.N,), c, dtype=self.rdtype, device=self.device)
+        return c
+
     def classify(self, val, what):
         """
         Judge a step size or Cholesky factor -- None, a number, a real tensor, or a dict / ParamDict of those by key: returns
@@ -183,7 +214,7 @@ class _Trajectory:
         self.g = layout.new()
         self.qv, self.pv = layout.views(self.q), layout.views(self.p)
         self.energy = torch.zeros(1, dtype=torch.float64, device=layout.device)
-        self.ws = torch.empty(int(_lib.lib.rime_hmc_workspace(layout.N)) // 8, dtype=torch.float64, device=layout.device)
+        self.ws = _workspace(_lib.lib.rime_hmc_workspace(layout.N), layout.device)
         self.launches = 0
 
     def stage(self, eps, c, kick, drift, energy=False):
@@ -276,15 +307,12 @@ def leapfrog(q, p, dUdq, eps, N, cov_L=None, diag_mass=True, dUdq0=None, states=
     e = lay.expand(eps, 'eps')
     if e is None:
         raise ValueError('sampler.leapfrog: eps is None')
-    c = lay.expand(cov_L, 'cov_L')
-    if isinstance(c, float):
-        c = None if c == 1.0 else torch.full((lay.N,), c, dtype=lay.rdtype, device=lay.device)
+    c = lay.factor(cov_L, 'cov_L')
     with torch.no_grad():
         traj.run(dUdq, e, c, N, dUdq0=dUdq0, states=states)
         if not direct:
-            for k in lay.keys:
-                (q if lay.tensor else q[k]).copy_(lay.view(traj.q, k))
-                (p if lay.tensor else p[k]).copy_(lay.view(traj.p, k))
+            lay.unpack(traj.q, q)
+            lay.unpack(traj.p, p)
     return q, p
 
 
@@ -465,10 +493,7 @@ class HMC(SamplerBase):
             cov_L, hess_L = {k: None for k in keys}, {k: None for k in keys}
         self.cov_L, self.hess_L = cov_L, hess_L
         self.diag_mass = {k: True for k in keys}
-        c = self._lay.expand(cov_L, 'cov_L')
-        if isinstance(c, float):
-            c = None if c == 1.0 else torch.full((self._lay.N,), c, dtype=self._lay.rdtype, device=self._lay.device)
-        self._c = c
+        self._c = self._lay.factor(cov_L, 'cov_L')
         self.logdetM = torch.zeros((), dtype=torch.float64, device=self._lay.device)
         for k in keys:
             if hess_L[k] is not None:

@@ -234,6 +234,37 @@ def test_calls_with_nothing_to_do_return_ok_without_a_launch():
     assert _lib.lib.rime_mass_workspace(10 ** 7) == _lib.lib.rime_nuts_workspace(10 ** 7)
 
 
+BOUND = 0x3fffffffffffffff                                  # the largest N the entry points take
+
+
+@pytest.mark.parametrize('bad', [dict(N=BOUND + 1), dict(N=1 << 35), dict(nblocks=0x7fffffff), dict(kick=-1e-60), dict(kick=0.0, z=PTR(1)),
+                                 dict(kick=0.0, z=ctypes.c_void_p(4096 * 2 - 396)), dict(z=ctypes.c_void_p(4096 * 4 + 396)),
+                                 dict(kick=0.0, g=None, p_out=None, dtype=7)],
+                         ids=lambda b: '-'.join(b))
+def test_project_rejects_the_rest(bad):
+    """the size bound, a grid beyond 2^31 - 1 work-groups, z on the momentum with and without a kick, z on one element of p_out"""
+    assert _project(**bad) == EINVAL
+
+
+@pytest.mark.parametrize('bad,code', [(dict(N=BOUND + 1), EINVAL), (dict(N=1 << 35), EINVAL), (dict(drift=-1e-60), EINVAL),
+                                      (dict(q_out=ctypes.c_void_p(4096 * 6 + 396)), EINVAL),          # q_out on part of q_in, not on it
+                                      (dict(q_out=ctypes.c_void_p(4096 * 5 - 396)), EINVAL),          # q_out on the last element of z
+                                      (dict(drift=0.0, q_in=None, q_out=None), EINVAL),               # projections of no position
+                                      (dict(p=None, q_far=None), EINVAL), (dict(p_far=None), EINVAL), # one or two of the three
+                                      (dict(drift=0.0, workspace=None), EWORKSPACE),
+                                      (dict(drift=0.0, out=None, dtype=7), EINVAL),                   # nothing to do, but judged first
+                                      (dict(drift=0.0, out=None, N=-1), EINVAL), (dict(drift=0.0, out=None, p=None), EINVAL)],
+                         ids=lambda b: '-'.join(b) if isinstance(b, dict) else str(b))
+def test_drift_rejects_the_rest(bad, code):
+    assert _drift(**bad) == code
+
+
+def test_nothing_to_do_is_ok_only_after_every_check():
+    assert _drift(drift=0.0, out=None) == 0 and _drift(drift=0.0, out=None, dtype=1, workspace=None, workspace_bytes=0) == 0
+    assert _drift(drift=-0.0, out=None, q_in=None, q_out=None) == 0
+    assert _lib.lib.rime_mass_workspace(BOUND + 1) == 0 and _lib.lib.rime_mass_workspace(BOUND) == _lib.lib.rime_nuts_workspace(BOUND) > 0
+
+
 def test_strip_sizes_match_the_kernels():
     src = open(kernel_asm.os.path.join(kernel_asm.ROOT, 'bayeslim_amd', 'csrc', 'massmat.hip')).read()
     assert 'MASS_ROWS = %d' % massmat.LOWER_ROWS in src and 'CS = 8 * W' in src

@@ -127,6 +127,35 @@ def test_entry_points_reject_bad_arguments_without_launching():
     assert [lib.rime_nuts_workspace(N) for N in Ns] == [3 * lib.rime_hmc_workspace(N) for N in Ns]
 
 
+def test_entry_points_remaining_return_paths():
+    """the size bound, every pair of an output with an input of open, and the step whose half is zero: in float64, of either sign,
+    and against the workspace of close"""
+    from bayeslim_amd._lib import lib
+    P = [ctypes.c_void_p(4096 * (i + 1)) for i in range(8)]
+    bound = 0x3fffffffffffffff                                                   # the largest N the entry points take
+
+    def opn(dtype=0, N=100, q0=P[0], p0=P[1], g0=P[2], q1=P[3], p1=P[4], eps=None, c=None, h=0.5):
+        return lib.rime_nuts_leaf_open(dtype, N, q0, p0, g0, q1, p1, eps, c, h, None)
+
+    def cls(dtype=0, N=100, h=0.5, ws=P[6], nbytes=1 << 20):
+        return lib.rime_nuts_leaf_close(dtype, N, P[0], P[1], P[2], None, None, h, P[3], P[4], P[5], ws, nbytes, None)
+
+    assert opn(N=bound + 1) == -1 and cls(N=bound + 1) == -1 and opn(N=1 << 62, dtype=1) == -1
+    assert lib.rime_nuts_workspace(bound + 1) == 0 and lib.rime_hmc_workspace(bound + 1) == 0 and lib.rime_hmc_workspace(-1) == 0
+    ins = dict(q0=0, p0=1, g0=2, eps=5, c=6)
+    for out in ('q1', 'p1'):
+        for name, i in ins.items():
+            assert opn(**{name: P[i], out: P[i]}) == -1, (out, name)                                  # the same buffer
+            assert opn(**{name: P[i], out: ctypes.c_void_p(P[i].value + 396)}) == -1, (out, name)    # its last element
+            assert opn(**{name: P[i], out: ctypes.c_void_p(P[i].value - 396)}) == -1, (out, name)
+    assert opn(p1=ctypes.c_void_p(P[3].value + 396)) == -1                       # the two outputs share one element
+    for dtype in (0, 1):
+        for h in (5e-324, -5e-324):                                              # h / 2 is zero in float64 already
+            assert opn(dtype=dtype, h=h) == -1 and cls(dtype=dtype, h=h) == -1
+            assert cls(dtype=dtype, h=h, ws=None) == -2 and cls(dtype=dtype, h=h, nbytes=0) == -2     # ... judged after the workspace
+    assert opn(h=1e-46) == -1 and cls(h=-1e-46) == -1                            # float32: half of it is below the smallest subnormal
+
+
 # ------------------------------------------------------------------------------------------------------- what the sampler refuses
 def test_nuts_names_what_it_does_not_provide_and_has_no_cpu_path():
     import bayeslim_amd

@@ -157,7 +157,8 @@ BAD = {
     'rime_lm_apply': [dict(out_real=1), dict(K_in=3), dict(m_rs=0), dict(xcplx=2), dict(idx=PTR, K_in=0)],
     'rime_fft_apply': [dict(N=0), dict(shift_in=8), dict(radix=IP(4)), dict(scale=NAN), dict(epilogue=-1),
                        dict(inverse=2), dict(nlines=-1)],
-    'rime_hmc_step': [dict(N=-1), dict(kick=NAN), dict(kick=1e-60), dict(drift=1e-60)],
+    'rime_hmc_step': [dict(N=-1), dict(kick=NAN), dict(kick=1e-60), dict(drift=1e-60), dict(drift=NAN), dict(N=(1 << 62)), dict(kick=-1e-60),
+                      dict(drift=0.0, q=None, kick=NAN), dict(kick=0.0, g=None, drift=-1e-60)],
     'rime_hmat_apply': [dict(nstages=0), dict(nrhs=0), dict(stage_first=IP(1, 0)), dict(stage_first=IP(-1, 0))],
     'rime_lbfgs_dots': [dict(k=1), dict(m=0), dict(N=0)],
     'rime_lbfgs_combine': [dict(m=0), dict(N=0)],
@@ -182,7 +183,7 @@ TOO_LONG = {'rime_stokes2coh_fwd': dict(R=BIG, P=1), 'rime_stokes2coh_bwd': dict
 EMPTY = {'rime_fft_apply': [dict(nlines=0)], 'rime_vis_timeavg_fwd': [dict(Npp=0), dict(Nbin=0, Nmem=0, bin_ptr_host=IP(0))],
          'rime_vis_timeavg_bwd': [dict(Nbl=0)], 'rime_filt_apply': [dict(Ntile=0), dict(Nlines=0), dict(Ntile=0, x=None)],
          'rime_sfb_fwd': [dict(Ntile=0), dict(B=0)], 'rime_sfb_bwd': [dict(Ntile=0), dict(B=0, gout=None)],
-         'rime_hmc_step': [dict(kick=0.0, drift=0.0, energy=None)]}
+         'rime_hmc_step': [dict(kick=0.0, drift=0.0, energy=None), dict(kick=0.0, drift=-0.0, energy=None, q=None, g=None, workspace=None)]}
 
 
 def _required(entry):
@@ -226,6 +227,9 @@ def _rows():
             add(e, EINVAL, **short, **BAD[e][0])                     # sizes and flags ahead of the workspace
     add('rime_hmc_step', EWORKSPACE, kick=1e-60, workspace=None)     # ... but the step that underflows in float32 after it
     add('rime_hmc_step', EINVAL, dtype=7, kick=1e-60)
+    add('rime_hmc_step', EINVAL, kick=0.0, drift=0.0, energy=None, N=-1)       # nothing to do is RIME_OK only after every check
+    add('rime_hmc_step', EINVAL, kick=0.0, drift=0.0, energy=None, p=None)
+    add('rime_hmc_step', EWORKSPACE, kick=0.0, drift=0.0, workspace_bytes=0)
     add('rime_beam_sky_bwd', EINVAL, dtype=7, workspace=None, workspace_bytes=0)
     # the generic fringe sum: a full-polarisation complex psky of two feeds is refused before dtype is looked at; the
     # workspace is looked at after it (one (t, f) row of 2^20 pixels is split, so that it needs one)
