@@ -1394,9 +1394,7 @@ template <bool CPLX, int NT>
 __device__ __forceinline__ void bwd_stage_diag(const AntBwdArgs& A, unsigned char* g_img, double* ant_lds, int t, int f, int TA, float& gs)
 {
     const int tid = threadIdx.x;
-    const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
-    for (int i = tid; i < MF_NA * 3; i += NT)
-        ant_lds[i] = (i < A.Nant * 3) ? nu_c * A.antpos[i] : 0.0;
+    stage_ant<NT>(ant_lds, A.antpos, MF_NA * 3, A.Nant * 3, scaled_freq(A, f));
 
     // stage G: fragment element (tile, ks, h, row, jj) <-> pair (i = 32 ti + row,
     // j = 32 tj + (jj & 3) + 8 (2 ks + (jj >> 2)) + 4 h); a thread packs the (jj, jj + 1) pair
@@ -1416,12 +1414,7 @@ __device__ __forceinline__ void bwd_stage_diag(const AntBwdArgs& A, unsigned cha
             const float* gre = A.gvt + ((size_t)t * A.Nf + f) * 2 * A.Nbl;
             const float* gim = gre + A.Nbl;
 #pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int bd = A.pair_direct[i * MF_NA + j0 + q];
-                if (bd >= 0) { gr[q] += gre[bd]; gi[q] += gim[bd]; }
-                const int bc = A.pair_conj[i * MF_NA + j0 + q];
-                if (bc >= 0) { gr[q] += gre[bc]; gi[q] -= gim[bc]; }
-            }
+            for (int q = 0; q < 2; ++q) gather_g(gre, gim, A.pair_direct, A.pair_conj, i * MF_NA + j0 + q, gr[q], gi[q]);
             if constexpr (!CPLX) {
                 if (ti == tj) {
                     // diagonal tile, real psky: Re(E^H conj(G) E) = 1/2 E^H H E with H = conj(G) + conj(G)^H Hermitian
@@ -1431,10 +1424,7 @@ __device__ __forceinline__ void bwd_stage_diag(const AntBwdArgs& A, unsigned cha
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         float tr = 0.f, ti_ = 0.f;               // G[j, i]
-                        const int bd = A.pair_direct[(j0 + q) * MF_NA + i];
-                        if (bd >= 0) { tr += gre[bd]; ti_ += gim[bd]; }
-                        const int bc = A.pair_conj[(j0 + q) * MF_NA + i];
-                        if (bc >= 0) { tr += gre[bc]; ti_ -= gim[bc]; }
+                        gather_g(gre, gim, A.pair_direct, A.pair_conj, (j0 + q) * MF_NA + i, tr, ti_);
                         const float s_ = 0.5f * (gr[q] + tr), a_ = ti_ - gi[q];
                         gr[q] = s_; gi[q] = -a_;                 // the "-Gi" plane (ih ^ sign) then holds +A
                     }
@@ -1444,13 +1434,7 @@ __device__ __forceinline__ void bwd_stage_diag(const AntBwdArgs& A, unsigned cha
         uint32_t rh, rl, ih, il;
         split2(gr[0] * gs, gr[1] * gs, rh, rl);
         split2(gi[0] * gs, gi[1] * gs, ih, il);
-        const int off = ((((tile * 2 + ks) * 2 + h) * 32 + row) * 4 + jp) * 4;
-        *reinterpret_cast<uint32_t*>(g_img + 0 * MB_PLANE + off) = rh;
-        *reinterpret_cast<uint32_t*>(g_img + 1 * MB_PLANE + off) = ih;
-        *reinterpret_cast<uint32_t*>(g_img + 2 * MB_PLANE + off) = ih ^ 0x80008000u;
-        *reinterpret_cast<uint32_t*>(g_img + 3 * MB_PLANE + off) = rl;
-        *reinterpret_cast<uint32_t*>(g_img + 4 * MB_PLANE + off) = il;
-        *reinterpret_cast<uint32_t*>(g_img + 5 * MB_PLANE + off) = il ^ 0x80008000u;
+        store_planes<MB_PLANE, true>(g_img, g_off(tile, ks, h, row, jp), rh, rl, ih, il);
     }
 }
 
@@ -1492,12 +1476,11 @@ fringe_ant_bwd_kernel(AntBwdArgs A)
     asm volatile("" : "+v"(gl1));                     // opaque: keeps gl1 a second base register
     for (int pt = tbeg + wave; pt < tend; pt += 8) {
         const int p = pt * 32 + (lane & 31);
-        const double sx = sd[p], sy = sd[A.Pstride + p], sz = sd[2 * (size_t)A.Pstride + p];
+        double sx, sy, sz;
+        load_dir<false>(sd, A.Pstride, p, sx, sy, sz);
         f32x16 accR[TAMAX], accI[TAMAX];
 #pragma unroll
-        for (int q = 0; q < TAMAX; ++q)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { accR[q][e] = 0.f; accI[q][e] = 0.f; }
+        for (int q = 0; q < TAMAX; ++q) { zero(accR[q]); zero(accI[q]); }
         float part = 0.f, parti = 0.f;
 #pragma unroll
         for (int tjr = 0; tjr < TAMAX; ++tjr) {
@@ -1536,11 +1519,7 @@ fringe_ant_bwd_kernel(AntBwdArgs A)
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int jj = 4 * jq + u;
-                            const int an = 32 * tj + (jj & 3) + 8 * (2 * ks + (jj >> 2)) + 4 * h;
-                            const double ph = phase3(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
-                            const float rr = turn_frac(ph);
-                            ec[8 * ks + jj] = __builtin_amdgcn_cosf(rr);
-                            es[8 * ks + jj] = __builtin_amdgcn_sinf(rr);
+                            phasor<false>(ant_lds, bwd_row_of(tj, ks, jj, h), sx, sy, sz, ec[8 * ks + jj], es[8 * ks + jj]);
                         }
                     }
 #pragma unroll
@@ -1667,9 +1646,7 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
     const int t = ts / A.S, split = ts % A.S;
     const int TI = A.rows_i / 32, TJ = (A.Nant - A.rows_i) / 32, JB = A.rows_i;      // uniform
 
-    const double nu_c = A.sign * A.freqs[f] * (1.0 / 2.99792458e8);
-    for (int i = tid; i < 2 * MF_NA * 3; i += 512)
-        ant_lds[i] = (i < A.Nant * 3) ? nu_c * A.antpos[i] : 0.0;
+    stage_ant<512>(ant_lds, A.antpos, 2 * MF_NA * 3, A.Nant * 3, scaled_freq(A, f));
 
     const float gs = A.gscale[t * A.Nf + f];
     const float* gre = A.gvt + ((size_t)t * A.Nf + f) * 2 * A.Nbl;
@@ -1679,23 +1656,14 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
         const int ti = tile >> 2, tj = tile & 3;
         if (ti >= TI || tj >= TJ) continue;               // tiles outside the block's shape are never read
         const int i = 32 * ti + row;
-        const int j0 = 32 * tj + ((2 * jp) & 3) + 8 * (2 * ks + (jp >> 1)) + 4 * h;
+        const int j0 = bwd_row_of_pair(tj, ks, jp, h);
         float gr[2] = {0.f, 0.f}, gi[2] = {0.f, 0.f};
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int bd = A.pair_direct[i * MF_NA + j0 + q];
-            if (bd >= 0) { gr[q] += gre[bd]; gi[q] += gim[bd]; }
-            const int bc = A.pair_conj[i * MF_NA + j0 + q];
-            if (bc >= 0) { gr[q] += gre[bc]; gi[q] -= gim[bc]; }
-        }
+        for (int q = 0; q < 2; ++q) gather_g(gre, gim, A.pair_direct, A.pair_conj, i * MF_NA + j0 + q, gr[q], gi[q]);
         uint32_t rh, rl, ih, il;
         split2(gr[0] * gs, gr[1] * gs, rh, rl);
         split2(gi[0] * gs, gi[1] * gs, ih, il);
-        const int off = ((((tile * 2 + ks) * 2 + h) * 32 + row) * 4 + jp) * 4;
-        *reinterpret_cast<uint32_t*>(g_img + 0 * MX_PLANE + off) = rh;
-        *reinterpret_cast<uint32_t*>(g_img + 1 * MX_PLANE + off) = ih;
-        *reinterpret_cast<uint32_t*>(g_img + 2 * MX_PLANE + off) = rl;
-        *reinterpret_cast<uint32_t*>(g_img + 3 * MX_PLANE + off) = il;
+        store_planes<MX_PLANE, false>(g_img, g_off(tile, ks, h, row, jp), rh, rl, ih, il);
     }
     __syncthreads();
 
@@ -1709,12 +1677,11 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
 
     for (int pt = tbeg + wave; pt < tend; pt += 8) {
         const int p = pt * 32 + (lane & 31);
-        const double sx = sd[p], sy = sd[A.Pstride + p], sz = sd[2 * (size_t)A.Pstride + p];
+        double sx, sy, sz;
+        load_dir<false>(sd, A.Pstride, p, sx, sy, sz);
         f32x16 accR[4], accI[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { accR[q][e] = 0.f; accI[q][e] = 0.f; }
+        for (int q = 0; q < 4; ++q) { zero(accR[q]); zero(accI[q]); }
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) {
             if (tj >= TJ) continue;                                     // uniform
@@ -1725,13 +1692,7 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
                 uint32_t* eih = reinterpret_cast<uint32_t*>(&Eih); uint32_t* eil = reinterpret_cast<uint32_t*>(&Eil);
                 float ec[8], es[8];
 #pragma unroll
-                for (int jj = 0; jj < 8; ++jj) {
-                    const int an = JB + 32 * tj + (jj & 3) + 8 * (2 * ks + (jj >> 2)) + 4 * h;
-                    const double ph = phase3(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
-                    const float rr = turn_frac(ph);
-                    ec[jj] = __builtin_amdgcn_cosf(rr);
-                    es[jj] = __builtin_amdgcn_sinf(rr);
-                }
+                for (int jj = 0; jj < 8; ++jj) phasor<false>(ant_lds, JB + bwd_row_of(tj, ks, jj, h), sx, sy, sz, ec[jj], es[jj]);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     split2_plain(ec[2 * q], ec[2 * q + 1], erh[q], erl[q]);
@@ -1774,10 +1735,8 @@ fringe_ant_bwd_cross_kernel(AntBwdArgs A)
             float pa = 0.f, pb = 0.f;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int an = 32 * ti + (e & 3) + 8 * (e >> 2) + 4 * h;
-                const double ph = phase3(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
-                const float rr = turn_frac(ph);
-                const float ce = __builtin_amdgcn_cosf(rr), se = __builtin_amdgcn_sinf(rr);
+                float ce, se;
+                phasor<false>(ant_lds, bwd_row_of(ti, e >> 3, e & 7, h), sx, sy, sz, ce, se);
                 part = fmaf(ce, accR[ti][e], part);
                 part = fmaf(se, accI[ti][e], part);
                 if constexpr (CPLX) {
@@ -1913,12 +1872,9 @@ fringe_pair_bwd_kernel(PairBwdArgs G)
     const float gs = A.gscale[t * A.Nf + f] * 0.125f;
     const float* gre = A.gvt + ((size_t)t * A.Nf + f) * 2 * A.Nbl;
     const float* gim = gre + A.Nbl;
-    // gradient with respect to V[r, c] of the virtual 128-row block: direct slot + conjugate of the conj slot
+    // gradient with respect to V[r, c] of the virtual 128-row block (scalar adds: see keep_scalar)
     auto grad_of = [&](int r, int c, float& vr, float& vi) {
-        const int bd = A.pair_direct[r * MF_NA + c];
-        if (bd >= 0) { vr += gre[bd]; keep_scalar(vr); vi += gim[bd]; keep_scalar(vi); }      // (scalar adds: see keep_scalar)
-        const int bc = A.pair_conj[r * MF_NA + c];
-        if (bc >= 0) { vr += gre[bc]; keep_scalar(vr); vi -= gim[bc]; keep_scalar(vi); }
+        gather_g<true>(gre, gim, A.pair_direct, A.pair_conj, r * MF_NA + c, vr, vi);
     };
     // a[i,j] = conj(g V[i,j]) + g V[i',j'];  b[i,j] = g V[j,i'] (+ g V[i,j'] on the off-diagonal tile): what the forward wrote where
     auto entry = [&](int i, int j, bool off, float& ar, float& ai, float& br, float& bi) {
@@ -1999,15 +1955,16 @@ fringe_pair_bwd_kernel(PairBwdArgs G)
     const uint32_t gl0 = (h * 32 + (lane & 31)) * 16;    // one lane base + 16-bit immediates reach all eight planes (48 KB)
     for (int pt = tbeg + wave; pt < tend; pt += PB_THREADS / 64) {
         const int p = pt * 32 + (lane & 31);
-        const double sx = sd[p], sy = sd[A.Pstride + p], sz = FLAT ? 0.0 : sd[2 * (size_t)A.Pstride + p];
+        double sx, sy, sz;
+        load_dir<FLAT>(sd, A.Pstride, p, sx, sy, sz);
         f32x16 accR[TF], accI[TF];
 #pragma unroll
         for (int q = 0; q < TF; ++q)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 if constexpr (CEN) {
-                    accR[q][e] = cen_u[32 * q + (e & 3) + 8 * (e >> 2) + 4 * h];
-                    accI[q][e] = cen_v[32 * q + (e & 3) + 8 * (e >> 2) + 4 * h];
+                    accR[q][e] = cen_u[32 * q + acc_row(e, h)];
+                    accI[q][e] = cen_v[32 * q + acc_row(e, h)];
                 } else { accR[q][e] = 0.f; accI[q][e] = 0.f; }
             }
         float part = 0.f;
@@ -2040,13 +1997,9 @@ fringe_pair_bwd_kernel(PairBwdArgs G)
                         }
                         if ((apmask >> (4 * tj + 2 * ks + jq)) & 1u) {   // uniform: octet of two progressions -- this half-wave's
                             // quad from its second row: E0 = E1 conj(D), E2 = E1 D, E3 = E2 D
-                            const int an = 32 * tj + 8 * (2 * ks + jq) + 4 * h + 1;
-                            const double ph = phase_of<FLAT>(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
-                            const float rr = turn_frac(ph);
                             float* c4 = ec + 8 * ks + 4 * jq;
                             float* s4 = es + 8 * ks + 4 * jq;
-                            c4[1] = __builtin_amdgcn_cosf(rr);
-                            s4[1] = __builtin_amdgcn_sinf(rr);
+                            phasor<FLAT>(ant_lds, bwd_row_of(tj, ks, 4 * jq + 1, h), sx, sy, sz, c4[1], s4[1]);
                             rotate_scalar(c4[1], s4[1], Dc, -Ds, c4[0], s4[0]);
                             rotate_scalar(c4[1], s4[1], Dc, Ds, c4[2], s4[2]);
                             rotate_scalar(c4[2], s4[2], Dc, Ds, c4[3], s4[3]);
@@ -2055,11 +2008,7 @@ fringe_pair_bwd_kernel(PairBwdArgs G)
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             const int jj = 4 * jq + u;
-                            const int an = 32 * tj + (jj & 3) + 8 * (2 * ks + (jj >> 2)) + 4 * h;
-                            const double ph = phase_of<FLAT>(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
-                            const float rr = turn_frac(ph);
-                            ec[8 * ks + jj] = __builtin_amdgcn_cosf(rr);
-                            es[8 * ks + jj] = __builtin_amdgcn_sinf(rr);
+                            phasor<FLAT>(ant_lds, bwd_row_of(tj, ks, jj, h), sx, sy, sz, ec[8 * ks + jj], es[8 * ks + jj]);
                         }
                     }
 #pragma unroll

@@ -324,6 +324,71 @@ __device__ __forceinline__ void for_wave(F&& go)
     }
 }
 
+// ---- device fragments of the backward kernels -----------------------------------------------------------
+// What the four backward kernels (fringe_mfma.hip, fringe_xpair.hip) share, once each, all forced inline.  A kernel takes a fragment
+// only where every one of its instantiations compiles to the instruction stream it had without it (tools/compare_kernel_asm.py);
+// DESIGN.md 5.1g lists what was tried and stays written out where, with the figures.
+// 1. Antenna staging: coordinates x sign nu / c into LDS, zero for the padding rows (NT = threads of the block)
+template <class Args> __device__ __forceinline__ double scaled_freq(const Args& A, int f) { return A.sign * A.freqs[f] * (1.0 / 2.99792458e8); }
+template <int NT>
+__device__ __forceinline__ void stage_ant(double* ant_lds, const double* antpos, int nlds, int nlive, double nu_c)
+{
+    for (int i = threadIdx.x; i < nlds; i += NT) ant_lds[i] = (i < nlive) ? nu_c * antpos[i] : 0.0;
+}
+
+// 2. G gather: the gradient with respect to V[r, c] of the block, slot = r * MF_NA + c -- the direct slot plus the conjugate
+// of the conj slot, ADDED to (gr, gi).  SCALAR: every sum fenced (the conjugate-pair kernels, see keep_scalar).
+template <bool SCALAR = false>
+__device__ __forceinline__ void gather_g(const float* gre, const float* gim, const int* direct, const int* conj, int slot,
+                                         float& gr, float& gi)
+{
+    const int bd = direct[slot];
+    if (bd >= 0) {
+        gr += gre[bd]; if constexpr (SCALAR) keep_scalar(gr);
+        gi += gim[bd]; if constexpr (SCALAR) keep_scalar(gi);
+    }
+    const int bc = conj[slot];
+    if (bc >= 0) {
+        gr += gre[bc]; if constexpr (SCALAR) keep_scalar(gr);
+        gi -= gim[bc]; if constexpr (SCALAR) keep_scalar(gi);
+    }
+}
+
+// 3. Plane stores.  A staging thread packs the (jj, jj + 1) pair of fragment element (tile, ks, h, row), g_off bytes into a plane;
+// store_planes: the complex entry (rh + rl) + i (ih + il) into planes [re, im, (-im)] hi, then lo (NEG: with the negated copy)
+__device__ __forceinline__ int g_off(int tile, int ks, int h, int row, int jp) { return ((((tile * 2 + ks) * 2 + h) * 32 + row) * 4 + jp) * 4; }
+template <int PLANE, bool NEG>
+__device__ __forceinline__ void store_planes(unsigned char* g_img, int off, uint32_t rh, uint32_t rl, uint32_t ih, uint32_t il)
+{
+    constexpr int NP = NEG ? 3 : 2;
+    *reinterpret_cast<uint32_t*>(g_img + 0 * PLANE + off) = rh;
+    *reinterpret_cast<uint32_t*>(g_img + 1 * PLANE + off) = ih;
+    if constexpr (NEG) *reinterpret_cast<uint32_t*>(g_img + 2 * PLANE + off) = ih ^ 0x80008000u;
+    *reinterpret_cast<uint32_t*>(g_img + NP * PLANE + off) = rl;
+    *reinterpret_cast<uint32_t*>(g_img + (NP + 1) * PLANE + off) = il;
+    if constexpr (NEG) *reinterpret_cast<uint32_t*>(g_img + 5 * PLANE + off) = il ^ 0x80008000u;
+}
+
+// 4. K index -> row: element jj of K step ks of column tile tj, in half-wave h = 32 tj + acc_row(8 ks + jj, h), the accumulator rows a lane holds
+__device__ __forceinline__ int bwd_row_of(int tj, int ks, int jj, int h) { return 32 * tj + (jj & 3) + 8 * (2 * ks + (jj >> 2)) + 4 * h; }
+// ... of the pair (jj, jj + 1) = (2 jp, 2 jp + 1) a staging thread packs: the row of its first element
+__device__ __forceinline__ int bwd_row_of_pair(int tj, int ks, int jp, int h) { return 32 * tj + ((2 * jp) & 3) + 8 * (2 * ks + (jp >> 1)) + 4 * h; }
+
+// 5. Directions of the lane's pixel, and the phasor c + i s of row `an` of ant_lds ([row][3], scaled) towards it
+template <bool FLAT>
+__device__ __forceinline__ void load_dir(const double* sd, int Pstride, int p, double& sx, double& sy, double& sz)
+{
+    sx = sd[p]; sy = sd[Pstride + p]; sz = FLAT ? 0.0 : sd[2 * (size_t)Pstride + p];
+}
+template <bool FLAT>
+__device__ __forceinline__ void phasor(const double* ant_lds, int an, double sx, double sy, double sz, float& c, float& s)
+{
+    const double ph = phase_of<FLAT>(ant_lds[3 * an], sx, ant_lds[3 * an + 1], sy, ant_lds[3 * an + 2], sz);
+    const float rr = turn_frac(ph);
+    c = __builtin_amdgcn_cosf(rr);
+    s = __builtin_amdgcn_sinf(rr);
+}
+
 // ---- host: from the arguments of a block entry point to its launches -----------------------------------------------------
 // An A/B switch of the environment: atoi of the variable, `dflt` where it is not set.  A caller keeps the answer in a
 // function-local static, so that the variable is read once, on first use.

@@ -258,19 +258,16 @@ fringe_xpair_bwd_kernel(BwdArgs A)
     const float gs = A.gscale[t * A.Nf + f] * 0.125f;
     const float* gre = A.gvt + ((size_t)t * A.Nf + f) * 2 * A.Nbl;
     const float* gim = gre + A.Nbl;
-    // gradient with respect to V[r, c] of the virtual block: direct slot + conjugate of the conj slot
+    // gradient with respect to V[r, c] of the virtual block (scalar adds: see keep_scalar)
     auto grad_of = [&](int r, int c, float& vr, float& vi) {
         vr = 0.f; vi = 0.f;
-        const int bd = A.pair_direct[r * NA + c];
-        if (bd >= 0) { vr += gre[bd]; keep_scalar(vr); vi += gim[bd]; keep_scalar(vi); }
-        const int bc = A.pair_conj[r * NA + c];
-        if (bc >= 0) { vr += gre[bc]; keep_scalar(vr); vi -= gim[bc]; keep_scalar(vi); }
+        gather_g<true>(gre, gim, A.pair_direct, A.pair_conj, r * NA + c, vr, vi);
     };
     for (int e = tid; e < 4 * 2 * 2 * 32 * 4; e += XB_THREADS) {
         const int jp = e & 3, row = (e >> 2) & 31, h = (e >> 7) & 1, ks = (e >> 8) & 1, tile = e >> 9;
         const int ti = tile >> 1, tj = tile & 1;
         const int i = 32 * ti + row;
-        const int j0 = 32 * tj + ((2 * jp) & 3) + 8 * (2 * ks + (jp >> 1)) + 4 * h;
+        const int j0 = bwd_row_of_pair(tj, ks, jp, h);
         float ncc[2] = {0.f, 0.f}, ncs[2] = {0.f, 0.f}, nsc[2] = {0.f, 0.f}, nss[2] = {0.f, 0.f};
         if (i < rows_i) {
 #pragma unroll
@@ -322,7 +319,8 @@ fringe_xpair_bwd_kernel(BwdArgs A)
     const uint32_t gl0 = (h * 32 + (lane & 31)) * 16;
     for (int pt = tbeg + wave; pt < tend; pt += XB_THREADS / 64) {
         const int p = pt * 32 + (lane & 31);                     // < Pstride: pt < ntile
-        const double sx = sd[p], sy = sd[A.Pstride + p], sz = FLAT ? 0.0 : sd[2 * (size_t)A.Pstride + p];
+        double sx, sy, sz;
+        load_dir<FLAT>(sd, A.Pstride, p, sx, sy, sz);
         f32x16 accC[2], accS[2];                                 // T1 = Ncc Cy + Ncs Sy,  T2 = Nsc Cy + Nss Sy, per row tile of I
 #pragma unroll
         for (int q = 0; q < 2; ++q)
