@@ -14,6 +14,7 @@ from . import paramdict            # noqa: F401,E402
 from . import sampler              # noqa: F401,E402
 from . import nuts                 # noqa: F401,E402
 from . import massmat              # noqa: F401,E402
+from . import recycled             # noqa: F401,E402
 from . import cosmology            # noqa: F401,E402
 
 __version__ = '0.1.0'

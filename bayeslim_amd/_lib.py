@@ -116,6 +116,7 @@ SIGNATURES = {
     'rime_bfgs_rank2': (_i, [_i, _vp, _ll, _ll, _vp, _vp, _d, _d, _vp]),
     'rime_hmc_workspace': (_sz, [_ll]),
     'rime_hmc_step': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _sz, _vp]),
+    'rime_hmc_recycle': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _d, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
     'rime_nuts_workspace': (_sz, [_ll]),
     'rime_nuts_leaf_open': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp]),
     'rime_nuts_leaf_close': (_i, [_i, _ll, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _sz, _vp]),

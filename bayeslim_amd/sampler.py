@@ -23,6 +23,8 @@ Not provided (each raises NotImplementedError naming what is missing):
 The No-U-Turn sampler is bayeslim_amd.nuts (NUTS and TreeInfo on the tree-leaf kernels of csrc/nuts.hip); the two names here
 stay stubs.
 Dense mass matrices per key are bayeslim_amd.massmat (leapfrog, HMC and NUTS on the triangular kernels of csrc/massmat.hip).
+RecycledHMC, StepSize, DynamicStepSize, pmask and estimate_cov are bayeslim_amd.recycled (on the fused kernel of csrc/recycle.hip);
+the names here stay stubs.
 """
 import math
 import os

@@ -675,6 +675,26 @@ int rime_hmc_step(int dtype, long long N, void* q, void* p, const void* g, const
                   double drift, double* energy, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * One step of a recycled HMC trajectory (recycled.RecycledHMC; reference sampler.py:799-893), which keeps every intermediate
+ * state: the closing half kick of step i with its kinetic energy, the snapshot of the state, and the opening half kick and
+ * drift of step i + 1 in one pass.  Vectors, eps and c as in rime_hmc_step; q_out, p_out T [N] (row i of the trajectory).
+ * Per element, in T, in this order:
+ *     p1 = fma(-(T(half) * eps), g, p);      energy[0] = 1/2 sum (c * p1)^2;      q_out = q;   p_out = p1
+ *     drift != 0:   p2 = fma(-(T(half) * eps), g, p1);   p <- p2;   q <- fma(T(drift) * eps, c * (c * p2), q)
+ *     drift == 0:   p <- p1
+ *   The energy is summed in the order of rime_hmc_step's, through the workspace of rime_hmc_workspace(N) bytes.
+ * Bit contract: q, p, q_out, p_out and energy carry the bits of rime_hmc_step(kick = half, drift = 0, energy), a copy of q and
+ *   p to q_out and p_out, and rime_hmc_step(kick = half, drift) when drift != 0 -- two half kicks, never one full kick -- for
+ *   every N, dtype, alignment and null combination.
+ * Checked before any HIP call: RIME_EINVAL for an unknown dtype, N < 0, a null q, p, g, q_out, p_out or energy, a NaN flag,
+ * half = 0, q_out or p_out overlapping q, p, g, eps, c or each other, a non-zero flag that rounds to zero in T; RIME_EWORKSPACE for a
+ * null or short workspace (looked at before the rounding, as in rime_hmc_step).
+ * ------------------------------------------------------------------------------------- */
+int rime_hmc_recycle(int dtype, long long N, void* q, void* p, const void* g, const void* eps, const void* c, double half,
+                     double drift, void* q_out, void* p_out, double* energy, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * One leaf of the No-U-Turn sampler's tree (nuts.NUTS.build_tree; reference sampler.py:1104-1140 with the criterion of
  * sampler.py:1402-1430): a leapfrog step of the signed size h from an edge state of the tree, which stays as it is, in two
  * launches around the evaluation of the potential's gradient at the new position.
