@@ -91,6 +91,10 @@ SIGNATURES = {
     'rime_chisq_workspace': (_sz, []),
     'rime_chisq_fwd': (_i, [_i, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     'rime_chisq_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    'rime_icov_plan': (_i, [_i, _ll, _i, _ll, _ip]),
+    'rime_icov_workspace': (_sz, [_i, _ll, _i, _ll]),
+    'rime_icov_fwd': (_i, [_i, _vp, _vp, _vp, _ll, _i, _ll, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'rime_icov_bwd': (_i, [_i, _vp, _vp, _i, _ll, _i, _ll, _vp, _vp]),
     'rime_apply_cal_fwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _vp]),
     'rime_apply_cal_bwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp]),
     'rime_redvis_fwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _i, _vp, _vp]),

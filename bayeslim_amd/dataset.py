@@ -44,6 +44,12 @@ class TensorData:
         self.cov_ndim = int(np.prod(self.data.shape)) if self.data is not None else None
         self.cov_logdet = logdet if logdet is not None else torch.tensor(0.0)
 
+    def compute_icov(self, inv='pinv', **kwargs):
+        """compute the inverse covariance from self.cov and set it as self.icov (dataset.py:126-140); inv and kwargs:
+        optim.compute_icov"""
+        from . import optim
+        self.icov = optim.compute_icov(self.cov, self.cov_axis, inv=inv, **kwargs)
+
     def get_data(self, **kwargs):
         return self.data
 

@@ -12,6 +12,7 @@ tensors and raises otherwise -- there is no CPU path in the product.
 import contextlib
 import ctypes
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -1771,6 +1772,124 @@ def chisq(pred, data=None, icov=None):
     w.r.t. pred.  The fused form of LogProb.forward_chisq's residual + apply_icov(cov_axis=None) + sum.
     """
     return _Chisq.apply(pred, data, icov)
+
+
+# data axis a covariance couples, per (mode, cov_axis); the data are (Npol, Npol, Nbl, Nt, Nf) or (Npol, 1, Nf, Npix)
+_COV_AXES = {('vis', 'bl'): 2, ('vis', 'time'): 3, ('vis', 'freq'): 4, ('map', 'freq'): 2, ('map', 'pix'): 3}
+ICOV_PLAN_FIELDS = ('lanes', 'vec', 'tile', 'splits', 'rows_per_split', 'grid', 'stage_bytes', 'lds_bytes', 'stage_limit',
+                    'tile_along_outer')
+
+
+def cov_axis_layout(shape, cov_axis, mode='vis'):
+    """
+    The one mapping of the axis covariances ("Axis covariances"): data of `shape` seen as (O, n, I) with the covariance axis in
+    the middle, its inverse covariance as (O I, n, n) with batch index o I + i.  Returns (axis, O, n, I, icov_shape,
+    out_shape): the data axis, the three extents, the documented shape of icov (batch axes in data order, then n, n) and the
+    shape of the per-batch chi-square (the data's without that axis).  NameError for an unknown cov_axis / mode pair.
+    """
+    if (mode, cov_axis) not in _COV_AXES:
+        raise NameError("didn't recognize cov_axis %r for mode %r" % (cov_axis, mode))
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != (5 if mode == 'vis' else 4):
+        raise ValueError("mode %r takes data of %d axes, got shape %s" % (mode, 5 if mode == 'vis' else 4, shape))
+    axis = _COV_AXES[(mode, cov_axis)]
+    O, n, I = int(np.prod(shape[:axis], dtype=np.int64)), shape[axis], int(np.prod(shape[axis + 1:], dtype=np.int64))
+    out_shape = shape[:axis] + shape[axis + 1:]
+    return axis, O, n, I, out_shape + (n, n), out_shape
+
+
+def icov_plan(dtype, O, n, I):
+    """the launch plan of rime_icov_fwd for a shape, as a dict of ICOV_PLAN_FIELDS (no GPU needed); ValueError when n
+    is too long for the LDS staging (RIME_EUNSUPPORTED) -- callers then take the torch path"""
+    out = (ctypes.c_int * len(ICOV_PLAN_FIELDS))()
+    rc = lib.rime_icov_plan(_dtype_code(dtype), int(O), int(n), int(I), out)
+    if rc == -4:
+        raise ValueError('covariance axis of %d elements does not fit the LDS staging of the fused kernel' % n)
+    check(rc, 'rime_icov_plan')
+    return dict(zip(ICOV_PLAN_FIELDS, out))
+
+
+def chisq_axis_fits(shape, dtype, cov_axis, mode='vis'):
+    """whether chisq_axis serves data of `shape` and complex `dtype`: False when the covariance axis is too long for the
+    kernel's LDS staging -- the one fall-back rule of its callers (no GPU needed)"""
+    _, O, n, I, _, _ = cov_axis_layout(shape, cov_axis, mode)
+    try:
+        icov_plan(dtype, O, n, I)
+    except ValueError:
+        return False
+    return True
+
+
+def _icov_fwd_call(p, d, w, O, n, I, y, q, out):
+    code, _ = _real_dtype(p)
+    ws, nws = _workspace(lib.rime_icov_workspace(code, O, n, I), p.device)
+    with _timed('icov_fwd_kernel', O * I * n * n):
+        rc = lib.rime_icov_fwd(code, _cptr(p), _cptr(d), _cptr(w), O, n, I, _cptr(y), _ptr(q), _ptr(out), _ptr(ws), nws, _stream())
+        if rc == -4:
+            raise ValueError('covariance axis of %d elements does not fit the LDS staging of the fused kernel' % n)
+        check(rc, 'rime_icov_fwd')
+
+
+class _ChisqAxis(torch.autograd.Function):
+    """r^H W r along one data axis and its backward 2 g W r from the saved W r (see rime_icov_fwd)"""
+    _warned = False
+    @staticmethod
+    def forward(ctx, pred, data, icov, cov_axis, mode, sum_chisq, keep):
+        _require_cuda(pred, data, icov)
+        assert pred.is_complex(), 'prediction must be complex'
+        axis, O, n, I, icov_shape, out_shape = cov_axis_layout(pred.shape, cov_axis, mode)
+        if tuple(icov.shape) != icov_shape:
+            raise ValueError("cov_axis %r, mode %r, data %s: icov must be %s, got %s"
+                             % (cov_axis, mode, tuple(pred.shape), icov_shape, tuple(icov.shape)))
+        p = _dense(pred)
+        code, rdt = _real_dtype(p)
+        d = None if data is None else _dense(data.expand_as(p), p.dtype)
+        if icov.dtype != p.dtype and not _ChisqAxis._warned:
+            _ChisqAxis._warned = True
+            warnings.warn('chisq_axis: icov is %s, the prediction %s: the whole inverse covariance is converted on every '
+                          'call; store it in the prediction\'s dtype' % (icov.dtype, p.dtype))
+        w = _dense(icov, p.dtype)
+        if w.data_ptr() % 16:
+            w = w.clone()
+        y = torch.empty_like(p) if keep else None
+        if sum_chisq:
+            out = torch.empty((), dtype=rdt, device=p.device)
+            _icov_fwd_call(p, d, w, O, n, I, y, None, out)
+        else:
+            out = torch.empty(out_shape, dtype=rdt, device=p.device)
+            _icov_fwd_call(p, d, w, O, n, I, y, out, None)
+        ctx.saved = (y, O, n, I, bool(sum_chisq))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        y, O, n, I, summed = ctx.saved
+        code, rdt = _real_dtype(y)
+        gg = g.detach().to(rdt).reshape(1 if summed else O * I).contiguous()
+        gp = torch.empty_like(y)
+        rc = lib.rime_icov_bwd(code, _cptr(y), _ptr(gg), int(not summed), O, n, I, _cptr(gp), _stream())
+        check(rc, 'rime_icov_bwd')
+        return gp, None, None, None, None, None, None
+
+
+def chisq_axis(pred, data, icov, cov_axis, mode='vis', sum_chisq=True):
+    """
+    (pred - data)^H icov (pred - data) with an inverse covariance along ONE data axis, on the fused kernel: pred complex,
+    (Npol, Npol, Nbl, Nt, Nf) for mode 'vis' or (Npol, 1, Nf, Npix) for 'map'; data complex and broadcastable to pred, or
+    None (0); icov complex in the shape optim.apply_icov documents for cov_axis ('bl', 'time', 'freq'; 'freq', 'pix' for a
+    map) -- see cov_axis_layout.  icov must be HERMITIAN in its last two axes (it is an inverse covariance): the backward,
+    2 g icov (pred - data) from the product the forward saved, relies on it, and nothing checks it.  Returns the real 0-d
+    sum, or with sum_chisq=False the real per-batch values in the data's shape without the covariance axis.
+    Differentiable w.r.t. pred only: data and icov are constants and must not require grad.  The product icov (pred - data)
+    is kept only when pred requires grad.  ValueError when the axis is too long for the kernel's LDS staging
+    (chisq_axis_fits).  Store icov in pred's dtype: another dtype is converted whole on every call (warned once).
+    """
+    for name, t in (('data', data), ('icov', icov)):
+        if t is not None and t.requires_grad:
+            raise ValueError('chisq_axis is differentiable in pred only: %s requires grad' % name)
+    keep = pred.requires_grad and torch.is_grad_enabled()      # read here: grad mode is off inside forward
+    return _ChisqAxis.apply(pred, data, icov, cov_axis, mode, bool(sum_chisq), keep)
 
 
 # ---------------------------------------------------------------------------------------

@@ -7,9 +7,13 @@ minibatch iteration, main-parameter tensor, priors, closure) with the likelihood
 Trainer loop around it (optim.py:1631-1833).  Optimisers, samplers, Hessians and the single-process DistributedLogProb (replaced by dist.py) are out of scope
 (SURVEY.md section 2).
 
-Only the diagonal inverse covariance (cov_axis=None) runs on the fused HIP kernel; the reference's
-'bl' / 'time' / 'freq' / 'pix' branches reference an undefined name (`d`, optim.py:1899-1913) and
-cannot run there either, and 'full' is a dense matrix product left to torch.
+The diagonal inverse covariance (cov_axis=None) runs on the fused chi-square kernel (ops.chisq), and an inverse
+covariance along one data axis ('bl' / 'time' / 'freq' for visibilities, 'freq' / 'pix' for maps) on the fused
+quadratic-form kernel (ops.chisq_axis), which reads the matrices once and keeps icov (pred - data) for the backward.
+The reference's own branches for these axes name an undefined variable (`d`, optim.py:1899-1913); here they are its
+documented einsums with `d` read as `data`, and for 'time' with the documented icov shape
+(Npol, Npol, Nbl, Nfreqs, Ntimes, Ntimes), which the reference's equation does not match ("Axis covariances").
+'full' is a dense matrix product left to torch.
 """
 import time
 
@@ -17,30 +21,99 @@ import numpy as np
 import torch
 
 from . import ops, utils
-from .dataset import TensorData
+from .dataset import MapData, TensorData
+
+
+# einsum of data^H icov data per (mode, cov_axis): the reference's (optim.py:1899-1913), 'time' by its documented shape
+_ICOV_EINSUM = {('vis', 'bl'): "ijklm,ijlmkn,ijnlm->ijlm", ('vis', 'time'): "ijklm,ijkmln,ijknm->ijkm",
+                ('vis', 'freq'): "ijklm,ijklmn,ijkln->ijkl", ('map', 'freq'): "ijkl,ijlkn,ijnl->ijl",
+                ('map', 'pix'): "ijkl,ijkln,ijkn->ijk"}
 
 
 def apply_icov(data, icov, cov_axis=None, mode='vis'):
-    """data^dagger Sigma^-1 data, elementwise for cov_axis=None (optim.py:1889-1894)"""
+    """
+    data^dagger Sigma^-1 data (optim.py:1836-1915), on any device, as torch computes it.  Data are
+    (Npol, Npol, Nbl, Ntimes, Nfreqs) for mode 'vis', (Npol, 1, Nfreqs, Npix) for mode 'map'.
+      cov_axis None : icov data-shaped (inverse variances) or None; returns the data-shaped products
+      'full'        : icov (data.size, data.size); returns the scalar
+      'bl'          : icov (Npol, Npol, Ntimes, Nfreqs, Nbl, Nbl)      -> (Npol, Npol, Ntimes, Nfreqs)
+      'time'        : icov (Npol, Npol, Nbl, Nfreqs, Ntimes, Ntimes)   -> (Npol, Npol, Nbl, Nfreqs)
+      'freq'        : vis: icov (Npol, Npol, Nbl, Ntimes, Nfreqs, Nfreqs) -> (Npol, Npol, Nbl, Ntimes)
+                      map: icov (Npol, 1, Npix, Nfreqs, Nfreqs)        -> (Npol, 1, Npix)
+      'pix'         : icov (Npol, 1, Nfreqs, Npix, Npix)               -> (Npol, 1, Nfreqs)
+    The first operand is conjugated.  The reference's branches for the axis covariances name an undefined `d` and cannot
+    run; these are its einsums with `d` as `data`.  For 'time' its equation (icov indexed `ijkln`) disagrees with its own
+    documented shape; the documented shape is used, as cov_get_diag, TensorData.set_cov and VisData.get_cov assume it.
+    NameError for any other cov_axis.
+    """
     if cov_axis is None:
         out = data.conj() * data
         return out if icov is None else out * icov
     if cov_axis == 'full':
         return data.ravel().conj() @ icov @ data.ravel()
-    raise NotImplementedError("cov_axis=%r: not runnable in the reference either (optim.py:1899-1913)" % (cov_axis,))
+    if (mode, cov_axis) not in _ICOV_EINSUM:
+        raise NameError("didn't recognize cov_axis {} for mode {}".format(cov_axis, mode))
+    dt = torch.promote_types(data.dtype, icov.dtype)
+    return torch.einsum(_ICOV_EINSUM[(mode, cov_axis)], data.conj().to(dt), icov.to(dt), data.to(dt))
 
 
-def forward_chisq(prediction, data=None, icov=None, cov_axis=None, sum_chisq=True):
+def cov_get_diag(cov, cov_axis, mode='vis', shape=None):
+    """
+    The diagonal of a covariance (or inverse covariance) in the shape of the data (optim.py:1918-1971): cov itself for
+    cov_axis None, reshaped to `shape` for 'full', and for the axis covariances (shapes: apply_icov) the diagonal of the
+    last two axes moved to the data axis it belongs to.  NameError for an unknown cov_axis.
+    """
+    if cov_axis is None:
+        return cov
+    diag = cov.diagonal(dim1=-2, dim2=-1)
+    if cov_axis == 'full':
+        return diag.reshape(shape)
+    axis = ops.cov_axis_layout((1,) * (5 if mode == 'vis' else 4), cov_axis, mode)[0]
+    return diag.moveaxis(-1, axis)
+
+
+def compute_icov(cov, cov_axis, inv='pinv', **kwargs):
+    """
+    The inverse covariance (optim.py:1974-2005).  cov_axis None: 1 / cov.clip(1e-40).  'full' and the axis covariances
+    ('bl', 'time', 'freq', 'pix'): every trailing (n, n) matrix inverted with torch.linalg, inv = 'pinv' (pseudo-inverse
+    with hermitian=True; kwargs such as rtol go to torch.linalg.pinv), 'inv' (torch.linalg.inv) or 'chol' (Cholesky factor
+    and cholesky_inverse; positive definite matrices).  In the reference the axis case fails with an unbound name;
+    inverting each matrix is this project's extension.
+    """
+    if cov_axis is None:
+        return 1 / cov.clip(1e-40)
+    if cov_axis != 'full':
+        ops.cov_axis_layout((1,) * (cov.ndim - 1), cov_axis, 'vis' if cov.ndim == 6 else 'map')      # NameError / ValueError
+    if inv == 'pinv':
+        return torch.linalg.pinv(cov, hermitian=True, **kwargs)
+    if inv == 'inv':
+        return torch.linalg.inv(cov, **kwargs)
+    if inv == 'chol':
+        return torch.cholesky_inverse(torch.linalg.cholesky(cov, **kwargs))
+    raise ValueError("inv must be 'pinv', 'inv' or 'chol', got %r" % (inv,))
+
+
+def _axis_kernel_ok(pred, cov_axis, mode, sum_chisq):
+    """whether forward_chisq takes the fused axis kernel: summed output, a complex prediction on the GPU, an axis
+    covariance that the kernel serves (ops.chisq_axis_fits; else the torch path)"""
+    return bool(sum_chisq and cov_axis not in (None, 'full') and pred.is_cuda and pred.is_complex()
+                and ops.chisq_axis_fits(pred.shape, pred.dtype, cov_axis, mode))
+
+
+def forward_chisq(prediction, data=None, icov=None, cov_axis=None, sum_chisq=True, mode='vis'):
     """
     chi-square of a model prediction against target data (optim.py:1019-1027): returns (chisq, res).
-    With sum_chisq and a diagonal (or absent) icov on the GPU the residual, weighting and sum are one
-    fused pass (ops.chisq); `res` is then None -- the reference returns it only for diagnostics.
+    With sum_chisq and a complex prediction on the GPU the residual, weighting and sum are one fused pass -- ops.chisq
+    for a diagonal (or absent) icov, ops.chisq_axis for an icov along one data axis (cov_axis 'bl', 'time', 'freq',
+    'pix'; mode 'vis' or 'map' as in apply_icov); `res` is then None -- the reference returns it only for diagnostics.
     """
     pred = prediction.data if hasattr(prediction, 'data') and not isinstance(prediction, torch.Tensor) else prediction
     if sum_chisq and cov_axis is None and pred.is_cuda and pred.is_complex():
         return ops.chisq(pred, data, icov), None
+    if _axis_kernel_ok(pred, cov_axis, mode, sum_chisq):
+        return ops.chisq_axis(pred, data, icov, cov_axis, mode=mode), None
     res = pred if data is None else pred - data
-    chisq = apply_icov(res, icov, cov_axis)
+    chisq = apply_icov(res, icov, cov_axis, mode=mode)
     if sum_chisq:
         chisq = torch.sum(chisq)
     if torch.is_complex(chisq):
@@ -147,7 +220,8 @@ class LogProb(utils.Module):
     log-priors attached to the model's modules (or given in prior_dict), evaluated once per pass at batch 0.
     Same constructor, batching protocol, main-parameter tensor, closure and gradient modifiers as the reference
     (optim.py:385-1389); a linear preconditioner `LM` may be any callable R^N -> R^N.  With a diagonal (or absent)
-    inverse covariance the residual, weighting and sum run as ONE fused kernel pass over the prediction (ops.chisq).
+    inverse covariance the residual, weighting and sum run as ONE fused kernel pass over the prediction (ops.chisq); with an
+    inverse covariance along one data axis (target.cov_axis 'bl', 'time', 'freq', 'pix') as one pass over it (ops.chisq_axis).
     """
     def __init__(self, model, target, start_inp=None, cov_parameter=False, prior_dict=None, device=None,
                  compute='post', negate=True, grad_type='accumulate', complex_circular=True):
@@ -301,7 +375,13 @@ class LogProb(utils.Module):
         the fused kernel produced the sum directly"""
         target, inp = self.get_batch_data(idx)
         data = target.get_data()
-        icov, cov_axis = (target.get_icov(), target.cov_axis) if hasattr(target, 'icov') else (None, None)
+        cov_axis = target.cov_axis if hasattr(target, 'icov') else None
+        if not hasattr(target, 'icov'):
+            icov = None
+        elif cov_axis in (None, 'full'):
+            icov = target.get_icov()
+        else:                                  # an axis covariance: whole, in its documented shape, never copied
+            icov = target.get_icov(squeeze=False, try_view=True)
         if self.batch_idx == 0:
             self.clear_prior_cache()
         main_params = main_params if main_params is not None else self.main_params
@@ -316,8 +396,13 @@ class LogProb(utils.Module):
             d = data.to(prediction.device).expand(prediction.shape)
             ic = None if icov is None else icov.to(prediction.device).expand(prediction.shape)
             return ops.chisq(prediction, d, ic), None
+        mode = 'map' if isinstance(target, MapData) else 'vis'
+        if _axis_kernel_ok(prediction, cov_axis, mode, sum_chisq):
+            d = data.to(prediction.device)
+            d = d.reshape(prediction.shape) if d.numel() == prediction.numel() else d.expand(prediction.shape)
+            return ops.chisq_axis(prediction, d, icov.to(prediction.device), cov_axis, mode=mode), None
         res = prediction - data
-        chisq = apply_icov(res, icov, cov_axis)
+        chisq = apply_icov(res, icov, cov_axis, mode=mode)
         if sum_chisq:
             chisq = torch.sum(chisq)
         return (chisq.real if torch.is_complex(chisq) else chisq), res

@@ -558,6 +558,29 @@ int rime_chisq_bwd(int dtype, const void* pred, const void* data, const void* ic
                    size_t N, void* gpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Correlated-noise likelihood: the quadratic form of the residual with an inverse covariance along ONE data axis
+ * (optim.apply_icov, cov_axis 'bl' / 'time' / 'freq' / 'pix'; the reference's own branches cannot run, optim.py:1899-1913).
+ * The data are viewed as (O, n, I) complex with the covariance axis in the middle; icov is (O*I, n, n) complex, batch
+ * b = o*I + i, each matrix row-major and HERMITIAN (an inverse covariance; not checked: the backward relies on it).
+ *     r = pred - data;  y[o,a,i] = sum_c icov[b][a][c] r[o,c,i];  q[b] = Re sum_a conj(r[o,a,i]) y[o,a,i];  out = sum_b q[b]
+ *     backward: gpred[o,a,i] = 2 g y[o,a,i],  g T [1] (g_per_batch 0) or T [O*I] (g_per_batch 1)
+ *   pred, data (NULL -> 0), y, gpred: T [O, n, I, 2], aligned to one complex number (8 bytes RIME_F32, 16 RIME_F64);
+ *   icov T [O*I, n, n, 2], 16-byte aligned;  q T [O*I];  out T [1]
+ *   y, q, out: each may be NULL (not wanted), not all three.  icov is read once; y makes the backward a scaling of y.
+ * Deterministic: row terms and partial sums in double, added in a fixed order (workspace: rime_icov_workspace bytes).
+ * rime_icov_plan: the launch plan of a shape without a device, plan_host[10] = {lanes per row, complex per load, tile T,
+ *   row splits, rows per split, grid, LDS bytes of the staged residual, LDS bytes in all, the limit of the former, tile
+ *   along o (I = 1)}.  RIME_EUNSUPPORTED: n too long for the LDS staging even at T = 1 (callers fall back to torch).
+ * RIME_EINVAL: unknown dtype, O, n or I <= 0, a null pred / icov, no output, a misaligned pointer; RIME_EWORKSPACE after these.
+ * ------------------------------------------------------------------------------------- */
+int rime_icov_plan(int dtype, long long O, int n, long long I, int* plan_host);
+size_t rime_icov_workspace(int dtype, long long O, int n, long long I);
+int rime_icov_fwd(int dtype, const void* pred, const void* data, const void* icov, long long O, int n, long long I,
+                  void* y, void* q, void* out, void* workspace, size_t workspace_bytes, void* stream);
+int rime_icov_bwd(int dtype, const void* y, const void* g, int g_per_batch, long long O, int n, long long I,
+                  void* gpred, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gain application  V' = G1 V G2^dagger  per (baseline, time, channel) -- the post-RIME calibration
  * step, calibration._apply_cal (calibration.py:2412-2487; complex visibilities, no undo / covariance),
  * SURVEY section 8(f) item 3.  NP = 1 (1-pol) or 2; diag != 0 with NP = 2 is the reference's '2pol' mode
