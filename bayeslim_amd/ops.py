@@ -1893,6 +1893,111 @@ def chisq_axis(pred, data, icov, cov_axis, mode='vis', sum_chisq=True):
 
 
 # ---------------------------------------------------------------------------------------
+# log-priors on the fused prior kernel (csrc/prior.hip; DESIGN.md, "Log-priors")
+# ---------------------------------------------------------------------------------------
+PRIOR_KINDS = {'laplace': 0, 'taper_sigmoid': 1, 'taper_tanh': 2}
+PRIOR_SIDES = {'both': 0, 'upper': 1, 'lower': 2}
+PRIOR_OPERANDS = ('mean', 'scale', 'lower', 'upper', 'coeff')
+PRIOR_THREADS, PRIOR_LANE_BYTES = 256, 32        # rime::PRIOR_THREADS, rime::PRIOR_BYTES: a chunk is their product in bytes
+PRIOR_MAX_BLOCKS = lib.rime_prior_workspace() // 8      # one double per work-group: the grid's cap
+
+
+def prior_grid_span(dtype):
+    """elements of `dtype` that one full grid of the prior kernels covers: above it the grid-stride loop takes a second trip"""
+    return PRIOR_MAX_BLOCKS * PRIOR_THREADS * PRIOR_LANE_BYTES // torch.empty((), dtype=dtype).element_size()
+
+
+def _prior_period(shape, op):
+    """the kernel's address mode of an operand against x of `shape`: 0 absent (None), 1 one value, N a full tensor, the
+    product of the trailing axes it spans for a trailing broadcast; None for what the kernel does not serve"""
+    if op is None:
+        return 0
+    if not torch.is_tensor(op):
+        return 1 if isinstance(op, (int, float)) and not isinstance(op, bool) else None
+    if op.is_complex() or not op.is_floating_point():
+        return None
+    if op.numel() == 1:
+        return 1
+    s = tuple(op.shape)
+    while s and s[0] == 1:
+        s = s[1:]
+    if len(s) > len(shape) or tuple(shape[len(shape) - len(s):]) != s:
+        return None
+    return int(np.prod(s, dtype=np.int64))
+
+
+def prior_fits(x, operands):
+    """
+    Whether prior_eval serves x with these operands (a sequence; None entries are absent operands): x a real float32 or
+    float64 tensor on the GPU with at least one element, every operand a real number or real floating tensor that is one
+    value, x's own shape, or the shape of trailing axes of x (leading axes of length 1 ignored).  Complex tensors, CPU
+    tensors and broadcasts along a middle axis or beyond x's shape are refused: their callers compose the law in torch.
+    """
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.numel() > 0):
+        return False
+    return all(_prior_period(x.shape, o) is not None for o in operands)
+
+
+def _prior_fwd_call(kind, side, x, operands, out, dx):
+    """rime_prior_fwd on a contiguous x with its five operands (PRIOR_OPERANDS order; dense tensors of x's dtype or None);
+    dx None: no derivative is stored"""
+    code, _ = _real_dtype(x)
+    args = []
+    for o in operands:
+        args += [_ptr(o), 0 if o is None else _prior_period(x.shape, o)]
+    ws, nws = _workspace(lib.rime_prior_workspace(), x.device)
+    with _timed('prior_fwd_kernel', x.numel()):
+        rc = lib.rime_prior_fwd(code, PRIOR_KINDS[kind], PRIOR_SIDES[side], _ptr(x), x.numel(), *args, _ptr(out), _ptr(dx),
+                                _ptr(ws), nws, _stream())
+        check(rc, 'rime_prior_fwd')
+
+
+class _PriorEval(torch.autograd.Function):
+    """sum of the prior's terms with the per-element derivative from the same pass; backward g dx (see rime_prior_fwd)"""
+    @staticmethod
+    def forward(ctx, x, kind, side, operands, keep):
+        _require_cuda(x)
+        xc = x.detach().contiguous()
+        _, rdt = _real_dtype(xc)
+        ops_ = [None if o is None else _dense(torch.as_tensor(o).to(xc.device), rdt) for o in operands]
+        out = torch.empty((), dtype=rdt, device=xc.device)
+        dx = torch.empty_like(xc) if keep else None
+        _prior_fwd_call(kind, side, xc, ops_, out, dx)
+        ctx.saved = dx
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        dx = ctx.saved
+        code, rdt = _real_dtype(dx)
+        gx = torch.empty_like(dx)
+        gg = g.detach().to(rdt).reshape(1).contiguous()
+        rc = lib.rime_prior_bwd(code, _ptr(dx), _ptr(gg), dx.numel(), _ptr(gx), _stream())
+        check(rc, 'rime_prior_bwd')
+        return gx, None, None, None, None
+
+
+def prior_eval(kind, x, mean=None, scale=None, lower=None, upper=None, coeff=None, side='both'):
+    """
+    The summed log-prior of a real GPU tensor x on the fused kernel, a 0-d tensor of x's dtype:
+      'laplace'        sum -|r| / scale, r = x - mean; side 'upper' drops r < 0, 'lower' drops r > 0
+      'taper_sigmoid'  sum logsig(coeff (x - lower)) + logsig(-coeff (x - upper)), logsig(z) = min(z, 0) - log1p(exp(-|z|))
+      'taper_tanh'     sum log tanh(coeff (x - lower)) + log tanh(-coeff (x - upper)); NaN outside a bound
+    lower or upper None drops its term.  The operands are constants, cast to x's dtype, in the shapes of prior_fits (the
+    caller checks it; ValueError otherwise).  Differentiable w.r.t. x: the derivative is computed in the forward pass and kept
+    only when x requires grad; the backward scales it by the upstream gradient.
+    """
+    operands = (mean, scale, lower, upper, coeff)
+    if kind not in PRIOR_KINDS or side not in PRIOR_SIDES:
+        raise ValueError('unknown prior kind %r or side %r' % (kind, side))
+    if not prior_fits(x, operands):
+        raise ValueError('prior_eval: x or an operand is not served by the fused kernel (see prior_fits)')
+    keep = x.requires_grad and torch.is_grad_enabled()           # read here: grad mode is off inside forward
+    return _PriorEval.apply(x, kind, side, operands, keep)
+
+
+# ---------------------------------------------------------------------------------------
 def _antenna_incidence(idx, Nant, dtype):
     """dense 0/1 [Nant, Nbl] matrix of which baselines an antenna slot takes part in (cached on idx)"""
     tag = getattr(idx, '_rime_incidence', None)

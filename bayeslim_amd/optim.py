@@ -14,6 +14,21 @@ The reference's own branches for these axes name an undefined variable (`d`, opt
 documented einsums with `d` read as `data`, and for 'time' with the documented icov shape
 (Npol, Npol, Nbl, Nfreqs, Ntimes, Ntimes), which the reference's equation does not match ("Axis covariances").
 'full' is a dense matrix product left to torch.
+
+The log-priors (optim.py:17-382).  LogUniformPrior and LogGaussPrior are torch compositions.  LogLaplacePrior and
+LogTaperedUniformPrior evaluate, per element x of the (indexed) parameter with mean m, scale s, bounds l / u and
+coefficient c = alpha / (u - l),
+    laplace        t = -|r| / s, r = x - m ('upper': r < 0 -> 0, 'lower': r > 0 -> 0)   dt/dx = -sign(r) / s, 0 at r = 0
+    taper sigmoid  t = logsig(c (x - l)) + logsig(-c (x - u))                           dt/dx = c sig(-c (x - l)) - c sig(c (x - u))
+    taper tanh     t = log tanh(c (x - l)) + log tanh(-c (x - u))                       dt/dx = 2c / sinh(2c (x - l)) - 2c / sinh(-2c (x - u))
+and sum them; an absent bound drops its term.  logsig(z) = min(z, 0) - log1p(exp(-|z|)), the stable form: the reference's
+literal log(sigmoid(z)) is -inf below z = -88 in float32; the two agree wherever the reference is finite, and this one
+stays finite.  The tanh taper is NaN outside its bounds, as in the reference.  Eligibility for the fused kernel
+(ops.prior_fits): a real float32 / float64 parameter on the GPU, every operand (cast to its dtype) one value, a tensor of
+its shape, or a tensor shaped as its trailing axes.  Then value and derivative come from ONE pass over the parameter
+(ops.prior_eval, csrc/prior.hip) and the backward is a scaling; otherwise (CPU, complex Laplace residuals, a broadcast along
+a middle axis) the same laws are composed in torch (log_laplace, log_tapered_uniform).  Error bound of the fused path:
+DESIGN.md, "Log-priors".
 """
 import time
 
@@ -205,6 +220,86 @@ class LogGaussPrior(BaseLogPrior):
             chisq = torch.sum(res @ self.icov.to(res.dtype) @ res.conj())
         out = -0.5 * chisq.real
         return out - self.norm if self.density else out
+
+
+def log_laplace(params, mean, scale, side='both'):
+    """sum -|r| / scale, r = params - mean, with the one-sided masks of LogLaplacePrior, as torch composes it (any device,
+    complex residuals with side 'both'); params is not modified"""
+    res = params - mean
+    if side == 'upper':
+        res = torch.where(res < 0, torch.zeros_like(res), res)
+    elif side == 'lower':
+        res = torch.where(res > 0, torch.zeros_like(res), res)
+    return -torch.sum(torch.abs(res) / scale)
+
+
+def log_tapered_uniform(params, lower_bound, upper_bound, coeff, kind='sigmoid'):
+    """sum over the given bounds of log f(coeff (params - lower_bound)) and log f(-coeff (params - upper_bound)), f the
+    sigmoid (as the stable log-sigmoid) or tanh (NaN outside a bound), as torch composes it (any device)"""
+    if kind not in ('sigmoid', 'tanh'):
+        raise ValueError("kind must be 'sigmoid' or 'tanh', got %r" % (kind,))
+    logf = torch.nn.functional.logsigmoid if kind == 'sigmoid' else (lambda z: torch.log(torch.tanh(z)))
+    out = 0.0
+    if lower_bound is not None:
+        out = out + logf(coeff * (params - lower_bound))
+    if upper_bound is not None:
+        out = out + logf(-coeff * (params - upper_bound))
+    return torch.sum(out)
+
+
+class LogTaperedUniformPrior(BaseLogPrior):
+    """
+    log of a uniform density with tapered edges (optim.py:134-214): with c = alpha / (upper_bound - lower_bound) (the
+    difference taken as 1 when one bound is absent, which leaves that side open),
+        kind 'sigmoid':  sum logsig(c (x - lower_bound)) + logsig(-c (x - upper_bound))   smooth on all of R
+        kind 'tanh':     sum log tanh(c (x - lower_bound)) + log tanh(-c (x - upper_bound))   NaN outside the bounds
+    alpha -> infinity approaches the top hat, alpha -> 1 an inverted parabola.  logsig is evaluated in its stable form
+    min(z, 0) - log1p(exp(-|z|)): the reference's log(sigmoid(z)) is -inf below z = -88 in float32; the two agree wherever
+    the reference is finite.  A real float32 / float64 parameter on the GPU whose bounds and coefficient are scalars,
+    parameter-shaped or shaped as its trailing axes takes one fused pass (ops.prior_eval: value and derivative together);
+    anything else the torch composition log_tapered_uniform.
+    """
+    def __init__(self, lower_bound=None, upper_bound=None, kind='sigmoid', alpha=10000., index=None, func=None, fkwargs=None):
+        super().__init__(index, func, fkwargs, attrs=['coeff', 'lower_bound', 'upper_bound'])
+        assert lower_bound is not None or upper_bound is not None
+        self.lower_bound = None if lower_bound is None else torch.as_tensor(lower_bound)
+        self.upper_bound = None if upper_bound is None else torch.as_tensor(upper_bound)
+        self.alpha = torch.as_tensor(alpha)
+        both = self.lower_bound is not None and self.upper_bound is not None
+        self.dbound = self.upper_bound - self.lower_bound if both else 1.0
+        self.coeff = self.alpha / self.dbound
+        self.kind = kind
+
+    def forward(self, params):
+        params = self._index_func(params)
+        if self.kind in ('sigmoid', 'tanh') and ops.prior_fits(params, (self.lower_bound, self.upper_bound, self.coeff)):
+            return ops.prior_eval('taper_' + self.kind, params, lower=self.lower_bound, upper=self.upper_bound, coeff=self.coeff)
+        return log_tapered_uniform(params, self.lower_bound, self.upper_bound, self.coeff, self.kind)
+
+
+class LogLaplacePrior(BaseLogPrior):
+    """
+    log of a Laplace density, the L1 regulariser (optim.py:314-382): -sum |x - mean| / scale, minus
+    norm = sum log(2 scale) when `density` is set; side 'upper' sets the residuals below the mean to zero, 'lower' those
+    above it; the derivative at a zero residual is zero.  A real float32 / float64 parameter on the GPU whose mean and scale
+    are scalars, parameter-shaped or shaped as its trailing axes takes one fused pass (ops.prior_eval); anything else
+    (CPU, a complex residual with side 'both', other broadcasts) the torch composition log_laplace.  params is never
+    modified: the reference's masked assignment writes into its own temporary, here it is a torch.where.
+    """
+    def __init__(self, mean, scale, side='both', density=True, index=None, func=None, fkwargs=None):
+        super().__init__(index, func, fkwargs, attrs=['mean', 'scale'])
+        self.mean = torch.atleast_1d(torch.as_tensor(mean))
+        self.scale = torch.atleast_1d(torch.as_tensor(scale))
+        self.norm = torch.sum(torch.log(2 * self.scale))
+        self.side, self.density = side, density
+
+    def forward(self, params):
+        params = self._index_func(params)
+        if self.side in ops.PRIOR_SIDES and ops.prior_fits(params, (self.mean, self.scale)):
+            out = ops.prior_eval('laplace', params, mean=self.mean, scale=self.scale, side=self.side)
+        else:
+            out = log_laplace(params, self.mean, self.scale, self.side)
+        return out - self.norm.to(out.dtype) if self.density else out
 
 
 # ---------------------------------------------------------------------------------------

@@ -558,6 +558,28 @@ int rime_chisq_bwd(int dtype, const void* pred, const void* data, const void* ic
                    size_t N, void* gpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Log-priors over a real parameter tensor x of N elements (optim.LogLaplacePrior, optim.LogTaperedUniformPrior): out = sum_i t(x_i)
+ * and, in the same pass, dx[i] = dt/dx_i, so that the backward is gx = g[0] dx (rime_prior_bwd).
+ *   kind 0 laplace        t = -|r| / s, r = x - m; side 0 both, 1 upper (r < 0 -> 0), 2 lower (r > 0 -> 0);  d = -sign(r) / s
+ *   kind 1 taper_sigmoid  t = logsig(c (x - l)) + logsig(-c (x - u)),  logsig(z) = min(z, 0) - log1p(exp(-|z|))
+ *   kind 2 taper_tanh     t = log tanh(c (x - l)) + log tanh(-c (x - u));  NaN outside a bound
+ *   m, s, l, u, c: T, each with a period: 1 one scalar, N a full tensor, 1 < period < N dividing N: element i % period
+ *   (an operand shaped as the trailing axes of x).  NULL l or u: that term is dropped.  x, full operands, dx, gx: aligned to
+ *   sizeof(T); 16-byte aligned ones take 16-byte accesses, the result does not depend on it.
+ *   out T [1]; dx T [N] or NULL (not wanted: nothing is stored); g T [1] (device scalar: upstream gradient)
+ * Deterministic two-pass reduction (double partial sums in a caller-owned workspace of rime_prior_workspace bytes).
+ * RIME_EINVAL before any launch: null x / out (dx / g / gx), N == 0, unknown dtype / kind / side, a period of a given operand
+ * that is 0, above N, or between 1 and N without dividing N, laplace without m and s, a taper without l and u or without c;
+ * RIME_EWORKSPACE after these.
+ * ------------------------------------------------------------------------------------- */
+size_t rime_prior_workspace(void);
+int rime_prior_fwd(int dtype, int kind, int side, const void* x, size_t N, const void* m, size_t m_period,
+                   const void* s, size_t s_period, const void* l, size_t l_period, const void* u, size_t u_period,
+                   const void* c, size_t c_period, void* out, void* dx, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int rime_prior_bwd(int dtype, const void* dx, const void* g, size_t N, void* gx, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Correlated-noise likelihood: the quadratic form of the residual with an inverse covariance along ONE data axis
  * (optim.apply_icov, cov_axis 'bl' / 'time' / 'freq' / 'pix'; the reference's own branches cannot run, optim.py:1899-1913).
  * The data are viewed as (O, n, I) complex with the covariance axis in the middle; icov is (O*I, n, n) complex, batch
