@@ -98,6 +98,8 @@ SIGNATURES = {
     'rime_prior_workspace': (_sz, []),
     'rime_prior_fwd': (_i, [_i, _i, _i, _vp, _sz] + [_vp, _sz] * 5 + [_vp, _vp, _vp, _sz, _vp]),
     'rime_prior_bwd': (_i, [_i, _vp, _vp, _sz, _vp, _vp]),
+    'rime_psf_gram': (_i, [_i, _vp, _vp, _vp, _ll, _ll, _i, _i, _vp, _ll, _i, _vp, _ll, _i, _vp, _vp, _vp, _vp, _vp, _ll, _ll,
+                           _i, _vp]),
     'rime_apply_cal_fwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _vp]),
     'rime_apply_cal_bwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _vp, _vp, _vp, _vp]),
     'rime_redvis_fwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _i, _vp, _vp]),

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rime_common.h"
+#include "turns.h"
 
 namespace rime {
 
@@ -59,29 +60,7 @@ struct FringeArgs {
     double freq0_c, dfreq_c;      // freq0 / c, dfreq / c   [turns per metre]
 };
 
-// ---------------------------------------------------------------------------------------
-// sin / cos of an angle given in TURNS, |r| <= 1/2: the hardware v_sin_f32 / v_cos_f32 take
-// their argument in revolutions; measured max abs error on gfx950 over [-1/2, 1/2] is 1.24e-7
-// (profiles/r01_microbench_gfx950.txt) at ~3.2 FMA issue slots each -- versus ~20 slots for a
-// quadrant-reduced polynomial of the same accuracy.
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void sincos_turns(float r, float& s, float& c)
-{
-    s = __builtin_amdgcn_sinf(r);
-    c = __builtin_amdgcn_cosf(r);
-}
-
-__device__ __forceinline__ void sincos_turns(double r, double& s, double& c)
-{
-    sincospi(2.0 * r, &s, &c);
-}
-
-// phase (turns, f64) -> reduced T in [-1/2, 1/2]
-template <typename T>
-__device__ __forceinline__ T reduce_turns(double ph)
-{
-    return (T)(ph - rint(ph));
-}
+// sincos_turns / reduce_turns (phase in turns -> one sincos of the working precision): turns.h, shared with psf.hip
 
 // One (baseline, pixel) pair: generate the CH fringe values of the chunk and hand each to
 // `sink(k, x, y)` (x = Re F, y = Im F).  `tau` = sign * b.s [m]; nu_c = anchor freq / c;

@@ -3,7 +3,10 @@ Map-making arithmetic of the reference's imaging.py (SURVEY.md section 8(f) item
 kernels: the imaging matrix A = conj(fringe) * beam of VisMapper.build_A (imaging.py:251-296) is never
 materialised -- (Nbl, Nf, Npix) complex, C4: 1.6 TB per time step.  `make_map` is the adjoint of the
 RIME fringe sum (the backward kernels, including the antenna-factored matrix-core path), `compute_Am`
-its forward, `compute_Pm` their composition.
+its forward, `compute_Pm` their composition.  The full PSF matrix (`compute_P(contract=None)`, imaging.py:845-847) is the
+fused phasor-Gram kernel of csrc/psf.hip (ops.psf_gram; DESIGN.md, "Full PSF matrix"): a real Gram product over phasors
+generated in the kernel, accumulated per time step straight into the cut rows and columns of the matrix; `pix_inds`
+selects columns of it when Npix^2 does not fit.  `deconvolve_map` (:739-752) and `VisData2MapData` (:864-930) consume it.
 
 `VisMapper` (imaging.py:12-714) is the reference's container around them -- time / baseline / channel selection,
 the three diagonal normalisations, the PSF contractions -- with the per-time-step A replaced by a fused operator
@@ -67,12 +70,19 @@ def compute_Pm(geom, w, m, beam=None, D=None):
     return Pm if D is None else Pm * D
 
 
-def compute_P(geom, w, beam=None, D=None, contract=None):
+def _scale(a, b):
+    """a * b where None stands for 1 (None when both are)"""
+    return b if a is None else a if b is None else a * b
+
+
+def compute_P(geom, w, beam=None, D=None, contract=None, geom_q=None, beam_q=None):
     """
     PSF matrix P = D A^T w conj(A) of one time step (imaging.py:818-861) without A:
       'diag'   : sum_b w |A|^2 = beam^2 sum_b w            (|fringe| = 1: closed form)
       'rowsum' : P @ 1 = compute_Pm of a map of ones
-      None     : P[f, p, q] = (P @ e_q)[f, p]: the unit maps through compute_Pm -- (Nf, P, P), small problems only
+      None     : P[f, p, q] = D[f, p] beam[f, p] beam[f, q] sum_b w[b, f] cos(phase[b, f, p] - phase[b, f, q]): the fused
+                 phasor-Gram kernel (ops.psf_gram), (Nf, P, P); with geom_q (a geometry of other pixels over the same
+                 baselines and channels) and their beam_q the columns are those pixels: (Nf, P, Pq)
     """
     Nf, P = geom.Nf, geom.P
     rdt = w.dtype
@@ -82,13 +92,45 @@ def compute_P(geom, w, beam=None, D=None, contract=None):
     elif contract == 'rowsum':
         out = compute_Pm(geom, w, torch.ones(Nf, P, dtype=rdt, device=w.device), beam)
     elif contract is None:
-        eye = torch.eye(P, dtype=rdt, device=w.device)[:, None, :].expand(P, Nf, P)
-        out = compute_Pm(geom, w, eye, beam).permute(1, 2, 0).contiguous()          # [q, f, p] -> [f, p, q]
+        return ops.psf_gram(geom, w, rs=_scale(beam, D), cs=beam if geom_q is None else beam_q, geom_q=geom_q)
     else:
         raise ValueError("contract must be None, 'diag' or 'rowsum'")
     if D is not None:
-        out = out * (D[:, :, None] if contract is None else D)
+        out = out * D
     return out
+
+
+def deconvolve_map(m, P, pinv=True, rcond=1e-15, hermitian=True):
+    """
+    deconvolved map dm[f, p] = sum_q Pinv[f, p, q] m[f, q] (imaging.py:739-752, experimental there): Pinv the
+    pseudo-inverse of P (Nf, Npix, Npix), or with pinv=False the inverse of its diagonal alone.  m (Nf, Npix).
+    """
+    if pinv:
+        Pinv = torch.linalg.pinv(P, rcond=rcond, hermitian=hermitian)
+    else:
+        Pinv = torch.diag_embed(1 / torch.diagonal(P, dim1=1, dim2=2))
+    return torch.einsum('ijk,ik->ij', Pinv, m)
+
+
+def VisData2MapData(vd, data=None, angs=None, cov=None, icov=None, cov_axis=None, norm=None, df=None, name=None):
+    """
+    MapData of the maps made from a VisData, all of whose channels were imaged (imaging.py:864-930): data
+    (Npols, 1, Nfreqs, Npix), angs (2, Npix) (ra, dec), norm (Nfreqs, Npix), df the channel widths [Hz].  A channel is
+    flagged when it is flagged on all baselines and times; the flags are (Npol, Npol, Nfreqs, Npix) for any Npix.
+    """
+    md = MapData()
+    md.setup_meta(name=name)
+    pols = ['ee', 'nn'] if vd.pol is None else [vd.pol]
+    Npix = angs.shape[1] if angs is not None else 1
+    flags = None
+    if vd.flags is not None:
+        # (Npol, Npol, Nfreqs) -> (Npol, Npol, Nfreqs, Npix).  The reference expands without the new axis, which puts the
+        # channel flags on the pixel axis and runs only for Npix == Nfreqs; this is the shape its comment states.
+        flags = vd.flags.all(dim=(2, 3))[..., None]
+        flags = flags.expand(flags.shape[:-1] + (Npix,))
+    md.setup_data(vd.freqs, df=df, data=data, pols=pols, angs=angs, flags=flags, cov=cov, icov=icov, cov_axis=cov_axis,
+                  norm=norm)
+    return md
 
 
 def get_visdata(vd, bl_inds=None, time_inds=None, freq_inds=None, squeeze=False, **kwargs):
@@ -317,11 +359,7 @@ class VisMapper:
             w = self.build_w(i).to(rdt)
             maps[..., cut] += make_map(v, w, geom, beam)
             if return_P:
-                _P = compute_P(geom, w, beam, contract=contract)
-                if contract is not None:
-                    P[:, cut] += _P
-                else:
-                    P[:, cut[:, None], cut[None, :]] += _P
+                self._add_P(P, op, w, contract)
             self._add_Aw(Aw, self._norm_term(w, op, quirk=True), cut)
         self.D = 1 / Aw.clip(self.clip)
         maps *= self.D
@@ -368,22 +406,54 @@ class VisMapper:
             D = 1 / Aw.clip(self.clip)
         return Pm * D
 
+    def _add_P(self, P, op, w, contract, pix_inds=None):
+        """this time step's addend to P: a contraction (Nfreqs, Npix) into the cut pixels; the full matrix straight into
+        P[:, cut, cut] by the phasor-Gram kernel (no (Nf, P, P) temporary); with pix_inds (contract None) the columns
+        pix_inds of it into P (Nfreqs, Npix, len(pix_inds)): the rectangular form over cut x (pix_inds in cut)"""
+        geom, _, beam, cut = op
+        if contract is not None:
+            P[:, cut] += compute_P(geom, w, beam, contract=contract)
+        elif len(cut) == 0:
+            return
+        elif pix_inds is None:
+            ops.psf_gram(geom, w, rs=beam, cs=beam, out=P, rows=cut, cols=cut, accumulate=True)
+        else:
+            pos = torch.full((self.Npix,), -1, dtype=torch.long, device=self.device)
+            pos[cut] = torch.arange(len(cut), device=self.device)
+            loc = pos[pix_inds]                                    # place of each chosen pixel in this time's cut, or -1
+            cols = torch.where(loc >= 0)[0]
+            if len(cols) == 0:
+                return
+            loc = loc[cols]
+            sdir = torch.zeros(1, 3, ops.pad_to_tile(len(loc)), dtype=torch.float64, device=self.device)
+            sdir[0, :, :len(loc)] = geom.sdir[0][:, loc]
+            geom_q = ops.FringeGeometry(geom.blvecs, sdir, geom.freqs, npix=[len(loc)], mfma=False)
+            geom_q.P = len(loc)
+            ops.psf_gram(geom, w, rs=beam, cs=None if beam is None else beam[:, loc], geom_q=geom_q, out=P, rows=cut,
+                         cols=cols, accumulate=True)
+
     @torch.no_grad()
-    def compute_P(self, D=None, contract='diag'):
-        """PSF matrix over all pixels, summed over the selected times: (Nfreqs, Npix[, Npix]) (imaging.py:608-687)"""
+    def compute_P(self, D=None, contract='diag', pix_inds=None):
+        """PSF matrix over all pixels, summed over the selected times: (Nfreqs, Npix[, Npix]) (imaging.py:608-687).
+        pix_inds (with contract None): only the columns pix_inds of it, (Nfreqs, Npix, len(pix_inds)) -- the response
+        of every map pixel to the chosen ones, for maps whose Npix^2 does not fit; a pixel outside a time step's cut
+        gets nothing from that step."""
         rdt = self._real()
-        P = torch.zeros((self.Nfreqs, self.Npix) + (() if contract is not None else (self.Npix,)), dtype=rdt,
-                        device=self.device)
+        if pix_inds is not None:
+            if contract is not None:
+                raise ValueError("pix_inds selects columns of the full PSF matrix: contract must be None")
+            pix_inds = torch.as_tensor(pix_inds, dtype=torch.long, device=self.device).reshape(-1)
+            if len(pix_inds) == 0 or int(pix_inds.min()) < 0 or int(pix_inds.max()) >= self.Npix \
+                    or len(torch.unique(pix_inds)) != len(pix_inds):
+                raise ValueError('pix_inds must be unique pixel indices in [0, %d)' % self.Npix)
+        ncol = () if contract is not None else (self.Npix if pix_inds is None else len(pix_inds),)
+        P = torch.zeros((self.Nfreqs, self.Npix) + ncol, dtype=rdt, device=self.device)
         Aw = self._init_Aw(rdt) if D is None else None
         for i in range(self.Ntimes):
             op = self._op(i)
             geom, _, beam, cut = op
             w = self.build_w(i).to(rdt)
-            _P = compute_P(geom, w, beam, contract=contract)
-            if contract is not None:
-                P[:, cut] += _P
-            else:
-                P[:, cut[:, None], cut[None, :]] += _P
+            self._add_P(P, op, w, contract, pix_inds)
             if D is None:
                 self._add_Aw(Aw, self._norm_term(w, op, quirk=False), cut)
         if D is None:

@@ -1893,6 +1893,86 @@ def chisq_axis(pred, data, icov, cov_axis, mode='vis', sum_chisq=True):
 
 
 # ---------------------------------------------------------------------------------------
+# full PSF matrix on the fused phasor-Gram kernel (csrc/psf.hip; DESIGN.md, "Full PSF matrix")
+# ---------------------------------------------------------------------------------------
+PSF_TILE = 64        # rime::PSF_TILE: side of the output tile of one work-group
+PSF_BCHUNK = 16      # rime::PSF_BCHUNK: baselines per LDS chunk
+PSF_FLUSH = 1024     # rime::PSF_FLUSH: baselines between two flushes of the accumulators
+
+
+def _psf_index(idx, n, extent, name, device):
+    """an index map of psf_gram as int32 on the device: n unique entries in [0, extent); None stays None"""
+    if idx is None:
+        return None
+    idx = torch.as_tensor(idx, device=device)
+    if idx.dtype not in (torch.int32, torch.int64) or idx.ndim != 1 or idx.numel() != n:
+        raise ValueError('%s must be %d integer indices, got %s %s' % (name, n, idx.dtype, tuple(idx.shape)))
+    if n and (int(idx.min()) < 0 or int(idx.max()) >= extent):
+        raise ValueError('%s has an index outside [0, %d)' % (name, extent))
+    if torch.unique(idx).numel() != n:
+        raise ValueError('%s has a duplicate index: every output element must have one owner' % name)
+    return idx.to(torch.int32).contiguous()
+
+
+@torch.no_grad()
+def psf_gram(geom, w, rs=None, cs=None, geom_q=None, out=None, rows=None, cols=None, accumulate=False):
+    """
+    out[f, rows[i], cols[j]] (= or +=) rs[f, i] cs[f, j] sum_b w[b, f] cos(2 pi nu_f / c (b_b . s_i - b_b . t_j)): the real
+    part of A^T w conj(A) of the fringe matrix, without A (rime_psf_gram).  geom: the FringeGeometry of ONE time step whose
+    first geom.P directions are the rows s_i (imaging.geometry); geom_q: another one over the same baselines and channels
+    for the columns t_j, or None: the rows again (symmetric form, half the tiles computed, each stored twice).
+    w (Nbl, Nf) or (Nbl, 1), real: its dtype is the working dtype.  rs (Nf, P) and cs (Nf, Pq), or None (1).  out
+    (Nf, ldr, ldc), contiguous, of the working dtype, or None: a new (Nf, P, Pq); rows / cols: unique indices into its
+    last two axes, or None (identity).  accumulate: add to out.  Deterministic (no atomics); no autograd.  Shapes, dtypes
+    and index maps are checked first, the device last: every refusal comes before the launch.
+    """
+    dev = w.device
+    if w.dtype not in (torch.float32, torch.float64):
+        raise TypeError('psf_gram: w must be float32 or float64, got %s' % w.dtype)
+    code, rdt = _real_dtype(w)
+    Nbl, Nf = geom.Nbl, geom.Nf
+    if geom.Nt != 1 or (geom_q is not None and geom_q.Nt != 1):
+        raise ValueError('psf_gram takes geometries of one time step')
+    if w.ndim != 2 or w.shape[0] != Nbl or w.shape[1] not in (1, Nf):
+        raise ValueError('psf_gram: w must be (%d, %d) or (%d, 1), got %s' % (Nbl, Nf, Nbl, tuple(w.shape)))
+    if any(s < 0 for s in w.stride()):
+        w = w.contiguous()
+    w_sb, w_sf = (w.stride(0) if Nbl > 1 else 0), (w.stride(1) if w.shape[1] > 1 else 0)
+    Pr = int(getattr(geom, 'P', geom.Pstride))
+    Pq = Pr
+    if geom_q is not None:
+        Pq = int(getattr(geom_q, 'P', geom_q.Pstride))
+        same = lambda a, b: a.data_ptr() == b.data_ptr() and a.shape == b.shape or torch.equal(a, b)
+        if geom_q.Nbl != Nbl or geom_q.Nf != Nf or not same(geom_q.blvecs, geom.blvecs) or not same(geom_q.freqs, geom.freqs):
+            raise ValueError('psf_gram: geom_q must share blvecs and freqs with geom')
+    if Pr <= 0 or Pq <= 0:
+        raise ValueError('psf_gram: no pixels')
+    scale = lambda x, P, name: None if x is None else _dense(torch.broadcast_to(x, (Nf, P)), rdt)
+    rs, cs = scale(rs, Pr, 'rs'), scale(cs, Pq, 'cs')
+    if out is None:
+        if rows is not None or cols is not None or accumulate:
+            raise ValueError('psf_gram: rows, cols and accumulate address an `out` the caller supplies')
+        out = torch.empty(Nf, Pr, Pq, dtype=rdt, device=dev)
+    if out.dtype != rdt:
+        raise TypeError('psf_gram: out is %s, the working dtype (that of w) %s' % (out.dtype, rdt))
+    if out.ndim != 3 or out.shape[0] != Nf or not out.is_contiguous():
+        raise ValueError('psf_gram: out must be contiguous (%d, ldr, ldc), got %s' % (Nf, tuple(out.shape)))
+    ldr, ldc = out.shape[1], out.shape[2]
+    rows = _psf_index(rows, Pr, ldr, 'rows', dev)
+    cols = _psf_index(cols, Pq, ldc, 'cols', dev)
+    if (rows is None and ldr < Pr) or (cols is None and ldc < Pq):
+        raise ValueError('psf_gram: out %s is smaller than the %d x %d pixels' % (tuple(out.shape), Pr, Pq))
+    _require_cuda(geom.blvecs, geom.sdir, geom.freqs, w, rs, cs, out, geom_q.sdir if geom_q is not None else None)
+    with _timed('psf_gram_kernel', Nbl * Nf * Pr * Pq):
+        rc = lib.rime_psf_gram(code, _ptr(geom.blvecs), _ptr(geom.freqs), _ptr(w), w_sb, w_sf, Nbl, Nf,
+                               _ptr(geom.sdir), geom.Pstride, Pr, _ptr(geom_q.sdir if geom_q is not None else None),
+                               geom_q.Pstride if geom_q is not None else 0, Pq if geom_q is not None else 0,
+                               _ptr(rs), _ptr(cs), _ptr(rows), _ptr(cols), _ptr(out), ldr, ldc, int(bool(accumulate)), _stream())
+        check(rc, 'rime_psf_gram')
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # log-priors on the fused prior kernel (csrc/prior.hip; DESIGN.md, "Log-priors")
 # ---------------------------------------------------------------------------------------
 PRIOR_KINDS = {'laplace': 0, 'taper_sigmoid': 1, 'taper_tanh': 2}

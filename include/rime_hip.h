@@ -603,6 +603,26 @@ int rime_icov_bwd(int dtype, const void* y, const void* g, int g_per_batch, long
                   void* gpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Full PSF matrix of the imaging path, P = D A^T w conj(A) with A = conj(fringe) beam (imaging.py:818-861), as a fused
+ * phasor-Gram product: A is never built.
+ *     S[f,i,j] = sum_b w[b,f] cos(2 pi nu_f/c (b_b.s_i - b_b.t_j));   out[f, rows[i], cols[j]] (= or +=) rs[f,i] cs[f,j] S[f,i,j]
+ *   blvecs double [Nbl,3]; freqs double [Nf]; w T, element (b, f) at b w_sb + f w_sf (w_sf 0: one weight per baseline);
+ *   sr double [3, ld_sr]: the Pr row directions s_i; sq double [3, ld_sq]: the Pq column directions t_j, or NULL: the
+ *   rows again (symmetric form: only tile pairs ti <= tj are computed and stored twice, Pq and ld_sq are ignored);
+ *   rs T [Nf, Pr], cs T [Nf, Pq], NULL -> 1;  rows int [Pr], cols int [Pq]: index maps into out, NULL -> identity; the
+ *   caller guarantees unique, in-range entries;  out T [Nf, ldr, ldc];  accumulate 0: =, 1: +=.
+ * The phase is formed in double, reduced to [-1/2, 1/2] turns and evaluated with one sincos of T per channel.  Every
+ * output element is written by one work-group: no atomics, bit-identical from run to run.
+ * RIME_EINVAL, before any HIP call: unknown dtype; a null blvecs / freqs / w / sr / out; Nbl, Nf, Pr (Pq with sq) <= 0;
+ *   Nf > 65535; a negative w stride; ld_sr < Pr, ld_sq < Pq; ldr (ldc) <= 0 or, with the identity map, < Pr (Pq);
+ *   accumulate not 0 / 1.
+ * ------------------------------------------------------------------------------------- */
+int rime_psf_gram(int dtype, const double* blvecs, const double* freqs, const void* w, long long w_sb, long long w_sf,
+                  int Nbl, int Nf, const double* sr, long long ld_sr, int Pr, const double* sq, long long ld_sq, int Pq,
+                  const void* rs, const void* cs, const int* rows, const int* cols, void* out, long long ldr,
+                  long long ldc, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Gain application  V' = G1 V G2^dagger  per (baseline, time, channel) -- the post-RIME calibration
  * step, calibration._apply_cal (calibration.py:2412-2487; complex visibilities, no undo / covariance),
  * SURVEY section 8(f) item 3.  NP = 1 (1-pol) or 2; diag != 0 with NP = 2 is the reference's '2pol' mode

@@ -4,6 +4,7 @@ pixels, Airy PixelBeam; Nt time steps): dirty maps + PSF diagonal + the 'A2w' no
 kernels (A, 8128 x 256 x 98k complex = 1.6 TB per time step, is never built), timed with HIP events; beside it the
 reference's arithmetic (materialised A, einsum) on a bounded sample on the host cores (the CPU oracle).
 usage: python tools/bench_imaging.py [nt] [method]
+       python tools/bench_imaging.py psf [npix] [nf] [reps] [imaging.py of another revision]     (full PSF matrix: main_psf)
 """
 import os
 import sys
@@ -99,5 +100,69 @@ def main():
           % (torch.get_num_threads(), nb, nf, pv, dt, ce / dt, elems / (ms * 1e-3) / (ce / dt)))
 
 
+def load_imaging(path):
+    """another revision's imaging.py (e.g. the parent commit's, saved to a file) as a module of this package: the same
+    library and ops under both, for A/B timings in one session"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bayeslim_amd._imaging_ab', path)
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def main_psf(argv):
+    """the full PSF matrix VisMapper.compute_P(contract=None): hex-37 (666 baselines), nf channels, one time step, npix map
+    pixels all inside the cut, float32.   usage: python tools/bench_imaging.py psf [npix] [nf] [reps] [imaging.py of another revision]"""
+    import json
+    npix = int(argv[0]) if len(argv) > 0 else 2048
+    nf = int(argv[1]) if len(argv) > 1 else 4
+    reps = int(argv[2]) if len(argv) > 2 else 3
+    img = load_imaging(argv[3]) if len(argv) > 3 else imaging
+    dev = torch.device('cuda:0')
+    freqs = torch.linspace(120e6, 160e6, nf, dtype=torch.float32, device=dev)
+    ants, vecs = utils._make_hex(4, D=14.6)
+    antpos = utils.AntposDict(ants, vecs)
+    arr = telescope_model.ArrayModel(antpos, freqs=freqs, cache_s=True, redtol=1.0, device=dev)
+    bls = arr.get_bls(uniq_bls=False, keep_autos=False)
+    tel = telescope_model.TelescopeModel((21.42827, -30.72148))
+    rng = np.random.default_rng(0)
+    zenaz = np.stack([np.rad2deg(np.arccos(rng.uniform(0.5, 1.0, npix))), rng.uniform(0, 360, npix)])
+    gen = torch.Generator(device='cpu').manual_seed(0)
+    Nbl, time = len(bls), 2459861.0
+    data = torch.complex(torch.randn(1, 1, Nbl, 1, nf, generator=gen), torch.randn(1, 1, Nbl, 1, nf, generator=gen)).to(dev)
+    icov = (torch.rand(1, 1, Nbl, 1, nf, generator=gen) + 0.5).to(dev)
+    vd = dataset.VisData()
+    vd.setup_meta(tel, antpos)
+    vd.setup_data(bls, torch.as_tensor([time]), freqs, pol='ee', data=data, icov=icov)
+    vm = img.VisMapper(vd, np.zeros(npix), np.zeros(npix), beam=None, fov=180, cache_A=True)
+    vm.telescope.conv_cache[(time, npix)] = torch.as_tensor(zenaz, dtype=torch.float64)
+    vm.set_normalization('A2w')
+    P = vm.compute_P(contract=None)                            # geometry cache, first launches
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        P = vm.compute_P(contract=None)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / reps
+    assert P.shape == (nf, npix, npix)
+    prof = []
+    ops.PROFILE = prof
+    vm.compute_P(contract=None)
+    ops.PROFILE = None
+    torch.cuda.synchronize()
+    kern = {}
+    for k in prof:
+        kern[k[0]] = kern.get(k[0], 0.0) + k[1].elapsed_time(k[2])
+    chk = [float(P[0, 0, 0]), float(P[-1, npix // 2, npix // 3]), float(P.double().abs().sum())]
+    print(json.dumps(dict(case='psf', imaging=argv[3] if len(argv) > 3 else 'this', Nbl=Nbl, Nf=nf, Npix=npix, reps=reps,
+                          ms_per_call=ms, pair_terms_per_s=Nbl * nf * npix * npix / (ms * 1e-3), kernel_ms=kern, check=chk)))
+
+
 if __name__ == '__main__':
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == 'psf':
+        main_psf(sys.argv[2:])
+    else:
+        main()
